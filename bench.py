@@ -15,6 +15,7 @@ throughput; `e2e_with_sampler` (extra key) times the reference's own window
 
     python bench.py --gpus 1 --steps 20 --warmup 5          # what the round driver runs
     python bench.py                                          # default: 9000 steps (steady state)
+    python bench.py --steps K --warmup W --dump-outputs DIR  # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  `roofline` refers to the 2-hop gather-aggregate
@@ -85,7 +86,13 @@ def parse():
     ap.add_argument("--dp-path", action="store_true", help="1 GPU only: run the data-parallel step chain (backward -> exchange + Adam "
                     "launch with a world of one) to measure what the multi-GPU step costs without the xGMI hop")
     ap.add_argument("--seed", type=int, default=72)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step handed back (loss row, parameters and Adam moments after the "
+                         "update) as DIR/<name>.npy, float32 (rank 0); same arguments, same inputs: two builds compare output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def cpu_fullgraph_baseline(name, budget_s):
@@ -243,6 +250,17 @@ def respawn_command(n_gpus, argv, port=None):
             port = s.getsockname()[1]
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={int(n_gpus)}",
             "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py")] + list(argv)
+
+
+def dump_outputs(out_dir, engine, last_losses):
+    """What the last optimiser step of the timed region returns to a caller of the training path: its {total, cls, margin, rec}
+    loss row and, after its Adam update, the parameters under the model's state_dict names and the two Adam moments (~63 KB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": last_losses, "weight": engine.weight, "enc.weight": engine.enc_weight, "enc.fc.weight": engine.enc_fc_weight,
+              "exp_avg": engine.exp_avg, "exp_avg_sq": engine.exp_avg_sq}
+    for name, x in arrays.items():
+        x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        np.save(os.path.join(out_dir, name + ".npy"), x.astype(np.float32))
 
 
 def main():
@@ -429,6 +447,8 @@ def main():
     n_timed_pairs = len(ev_pairs)
     by_kernel_from = "the timed region"
     losses = trainer.engine.losses(a.steps)                # (before the repeat below overwrites the log slots)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, trainer.engine, losses[-1])          # (before the repeat below trains on)
     if not instrument["all"] and world == 1:
         instrument["all"] = True
         trainer.run_steps(a.steps, prepared=timed, gather_hook=timed_build)
