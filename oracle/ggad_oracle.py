@@ -17,6 +17,11 @@ cosine_similarity/Adam, scipy sparse products) is used through the container's o
 torch 2.10 / scipy 1.15, the same versions the goldens were produced with; the
 reference pins torch==1.11.0 (`requirements.txt:7`).
 
+Precision.  The mini-batch functions (`aggregate_batch`, `encoder_forward`, `batch_loss`) take a ``dtype``: fp32 by default,
+the arithmetic the goldens pin; with float64 every intermediate is float64, the high-precision reference the fp32 kernels are
+checked against (tests/test_oracle_fp64.py pins that mode to the same captures, tests/step_reference.py uses it with
+`adam_f64`, torch.optim.Adam's update restated in float64).
+
 Two formulations are provided where they differ in cost:
   * sparse (CSR / per-edge) -- what the HIP kernels implement;
   * dense-faithful          -- the same dense ops the reference executes (dense batch
@@ -124,15 +129,18 @@ def _closed_rows(rowptr, col, nodes) -> List[np.ndarray]:
     return rows
 
 
-def aggregate_batch(rowptr, col, feat, nodes: Sequence[int], train_flag: bool) -> BatchAgg:
-    """Closed form of the dense-mask aggregation, fp32 accumulate.
+def aggregate_batch(rowptr, col, feat, nodes: Sequence[int], train_flag: bool, dtype=np.float32) -> BatchAgg:
+    """Closed form of the dense-mask aggregation, accumulated in ``dtype`` (fp32 by default; np.float64
+    makes every weight, sum and count of both aggregates fp64: the high-precision reference the fp32 kernels are checked against).
 
     1-hop (`graphsage.py:305-326`): rows = batch nodes, columns = U; mask[i,j]=1 iff j in N(i)+{i};
     weight = 1/(sqrt(rowsum_i) sqrt(colsum_j)),  colsum_j = #rows of THIS batch containing j.
     2-hop (`:335-355`, train only): rows = U, columns = U2 = union N(u) (no self union);
     same normalisation with its own row / column sums.  The CPU branch adds no residual.
     """
-    feat = np.asarray(feat, dtype=np.float32)
+    dt = np.dtype(dtype)
+    one = dt.type(1.0)
+    feat = np.asarray(feat, dtype=dt)
     rows = _closed_rows(rowptr, col, nodes)
     unique = np.unique(np.concatenate(rows)) if rows else np.zeros(0, dtype=np.int64)
     b = len(rows)
@@ -141,32 +149,32 @@ def aggregate_batch(rowptr, col, feat, nodes: Sequence[int], train_flag: bool) -
         ent_ptr[i + 1] = ent_ptr[i] + len(rw)
     ent_col = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
     ent_pos = np.searchsorted(unique, ent_col)
-    c = np.bincount(ent_pos, minlength=len(unique)).astype(np.float32)
-    r = np.diff(ent_ptr).astype(np.float32)
-    to_feats = np.zeros((b, feat.shape[1]), dtype=np.float32)
+    c = np.bincount(ent_pos, minlength=len(unique)).astype(dt)
+    r = np.diff(ent_ptr).astype(dt)
+    to_feats = np.zeros((b, feat.shape[1]), dtype=dt)
     for i in range(b):
         p = ent_pos[ent_ptr[i]:ent_ptr[i + 1]]
-        w = (np.float32(1.0) / np.sqrt(r[i])) / np.sqrt(c[p])      # mask.div(row).div(col)
-        to_feats[i] = (w[:, None] * feat[unique[p]]).sum(0, dtype=np.float32)
+        w = (one / np.sqrt(r[i])) / np.sqrt(c[p])      # mask.div(row).div(col)
+        to_feats[i] = (w[:, None] * feat[unique[p]]).sum(0, dtype=dt)
     to_feats_neigh = None
     if train_flag:
         nrows = [col[rowptr[int(u)]:rowptr[int(u) + 1]].astype(np.int64) for u in unique]   # `:339`
         allk = np.concatenate(nrows) if nrows else np.zeros(0, dtype=np.int64)
         u2, inv = np.unique(allk, return_inverse=True)
-        c2 = np.bincount(inv, minlength=len(u2)).astype(np.float32)
-        to_feats_neigh = np.zeros((len(unique), feat.shape[1]), dtype=np.float32)
+        c2 = np.bincount(inv, minlength=len(u2)).astype(dt)
+        to_feats_neigh = np.zeros((len(unique), feat.shape[1]), dtype=dt)
         off = 0
         with np.errstate(divide="ignore", invalid="ignore"):
             for ui, nb in enumerate(nrows):
                 k = len(nb)
                 pos = inv[off:off + k]
                 off += k
-                rr = np.float32(k)
-                w = (np.float32(1.0) / np.sqrt(rr)) / np.sqrt(c2[pos])
+                rr = dt.type(k)
+                w = (one / np.sqrt(rr)) / np.sqrt(c2[pos])
                 if k == 0:
                     to_feats_neigh[ui] = np.nan          # 0/0 row of the dense mask (quirk 3)
                 else:
-                    to_feats_neigh[ui] = (w[:, None] * feat[nb]).sum(0, dtype=np.float32)
+                    to_feats_neigh[ui] = (w[:, None] * feat[nb]).sum(0, dtype=dt)
     return BatchAgg(to_feats, unique, to_feats_neigh, ent_ptr, ent_pos, np.diff(ent_ptr))
 
 
@@ -261,24 +269,40 @@ class MiniParams:
     def tensors(self):
         return [self.weight, self.enc_weight, self.enc_fc_weight]
 
+    @classmethod
+    def leaves(cls, weight, enc_weight, enc_fc_weight, dtype=torch.float32) -> "MiniParams":
+        """Fresh autograd leaves of ``dtype`` holding copies of the three arrays / tensors."""
+        return cls(*[torch.tensor(np.asarray(t), dtype=_torch_dtype(dtype), requires_grad=True)
+                     for t in (weight, enc_weight, enc_fc_weight)])
 
-def encoder_forward(p: MiniParams, agg: BatchAgg, labels: np.ndarray, train_flag: bool):
-    """GCNEncoder.forward (`graphsage.py:395-454`) on an aggregated batch; torch fp32, autograd-able.
+
+def _np_dtype(dtype) -> np.dtype:
+    return np.dtype(torch.empty(0, dtype=dtype).numpy().dtype) if isinstance(dtype, torch.dtype) else np.dtype(dtype)
+
+
+def _torch_dtype(dtype) -> torch.dtype:
+    return dtype if isinstance(dtype, torch.dtype) else torch.from_numpy(np.zeros(0, dtype=np.dtype(dtype))).dtype
+
+
+def encoder_forward(p: MiniParams, agg: BatchAgg, labels: np.ndarray, train_flag: bool, dtype=np.float32):
+    """GCNEncoder.forward (`graphsage.py:395-454`) on an aggregated batch; torch, autograd-able, every intermediate in ``dtype``
+    (fp32 by default; np.float64 / torch.float64 with a float64 aggregate and float64 parameters: the high-precision reference).
 
     Returns (combined_all (D,B), to_feats_neigh (B,D), anomaly_feat (D,A), anomaly_feat_new (D,A))."""
-    x1 = torch.from_numpy(agg.to_feats)
+    dt, tdt = _np_dtype(dtype), _torch_dtype(dtype)
+    x1 = torch.from_numpy(np.asarray(agg.to_feats, dtype=dt))
     combined = F.relu(p.enc_weight.mm(x1.t()))                            # `:412`
     if not train_flag:
         return combined, None, None, None
-    x2 = torch.from_numpy(agg.to_feats_neigh)
+    x2 = torch.from_numpy(np.asarray(agg.to_feats_neigh, dtype=dt))
     expand = F.relu(p.enc_weight.mm(x2.t()))                              # `:419`  (D, U)
     b = len(agg.r)
     rows = torch.from_numpy(np.repeat(np.arange(b), np.diff(agg.ent_ptr)))
     pos = torch.from_numpy(agg.ent_pos.astype(np.int64))
-    inv_r = torch.from_numpy((np.float32(1.0) / agg.r.astype(np.float32)))
+    inv_r = torch.from_numpy((dt.type(1.0) / agg.r.astype(dt)))
     # mask_row.mm(expand.t()): mean over N(i)+{i} of the 1-hop embeddings      `:421`
     gathered = expand.t()[pos] * inv_r[rows][:, None]
-    nbar = torch.zeros(b, expand.shape[0]).index_add(0, rows, gathered)
+    nbar = torch.zeros(b, expand.shape[0], dtype=tdt).index_add(0, rows, gathered)
     lab = torch.as_tensor(labels)
     anomaly_feat = combined[:, lab == 1]                                  # `:427`
     anomaly_feat2 = nbar.t()[:, lab == 1]                                 # `:428`
@@ -287,11 +311,11 @@ def encoder_forward(p: MiniParams, agg: BatchAgg, labels: np.ndarray, train_flag
     return combined_all, nbar, anomaly_feat, new.t()
 
 
-def batch_loss(p: MiniParams, agg: BatchAgg, labels: np.ndarray):
-    """GCN.loss (`graphsage.py:244-258`): (total, cls, margin, rec), all torch scalars."""
-    combined_all, nbar, a_feat, a_new = encoder_forward(p, agg, labels, True)
+def batch_loss(p: MiniParams, agg: BatchAgg, labels: np.ndarray, dtype=np.float32):
+    """GCN.loss (`graphsage.py:244-258`): (total, cls, margin, rec), all torch scalars of ``dtype`` (see `encoder_forward`)."""
+    combined_all, nbar, a_feat, a_new = encoder_forward(p, agg, labels, True, dtype)
     scores = p.weight.mm(combined_all).t()                                # `:174-176`
-    lab_f = torch.as_tensor(labels, dtype=torch.float32)
+    lab_f = torch.as_tensor(labels, dtype=_torch_dtype(dtype))
     lab = torch.as_tensor(labels)
     cls = torch.mean(F.binary_cross_entropy_with_logits(scores.squeeze(), lab_f, reduction="none",
                                                         pos_weight=torch.tensor([1])))       # `:246`
@@ -423,6 +447,19 @@ def aegis_loss(P, rowptr, col, feat, noise, nodes):
 def make_adam(params: Sequence[torch.Tensor], lr: float, weight_decay: float):
     """The optimiser both entry points use (`run.py:118`, `src/model_handler.py:299-300`)."""
     return torch.optim.Adam(list(params), lr=lr, weight_decay=weight_decay)
+
+
+def adam_f64(p, m, v, g, step: int, lr: float = 1e-3, weight_decay: float = 0.007, betas=(0.9, 0.999), eps: float = 1e-8):
+    """torch.optim.Adam's single-tensor update (no amsgrad, no maximize) restated in float64 numpy, for the optimiser step
+    number ``step`` (1-based, after the increment) from state (p, m, v) with gradient g.  Returns the new (p, m, v)."""
+    p, m, v, g = (np.asarray(t, dtype=np.float64) for t in (p, m, v, g))
+    b1, b2 = betas
+    g = g + weight_decay * p                                          # grad.add(param, alpha=weight_decay)
+    m = m + (1.0 - b1) * (g - m)                                      # exp_avg.lerp_(grad, 1 - beta1)
+    v = b2 * v + (1.0 - b2) * g * g                                   # exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    denom = np.sqrt(v) / np.sqrt(bc2) + eps
+    return p - (lr / bc1) * (m / denom), m, v
 
 
 # ----------------------------------------------------------------------------------

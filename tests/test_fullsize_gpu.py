@@ -15,6 +15,7 @@ import torch
 
 from ggad_amd import synth
 from oracle import ggad_oracle as O
+import step_reference as R
 
 pytestmark = pytest.mark.gpu
 
@@ -87,6 +88,32 @@ def test_sampled_batches_of_the_full_size_chunk_against_the_oracle(full):
         ref = np.concatenate([t.grad.numpy().reshape(-1) for t in p.tensors()])
         np.testing.assert_allclose(eng.grads.cpu().numpy(), ref, atol=5e-6, rtol=5e-5)
         np.testing.assert_allclose(eng.losses(slot + 1)[slot], [tot.item(), cls.item(), mar.item(), rec.item()], atol=2e-5)
+
+
+def test_resident_kernel_on_sampled_full_size_batches_against_float64(full):
+    """The default dense step -- the XCD-resident chunk kernel, at the trainer's 28 workgroups -- on batches 0, 61 and 149 of
+    the full-size chunk (max degree 2,000: hub rows and batches of thousands of entries occur naturally), each as a chunk of one
+    batch, from fresh state and from preloaded moments at step counter 10,000: loss row, moments, parameters and step counter
+    against the float64 oracle and Adam (checks and tolerances: tests/step_reference.py)."""
+    one = BatchChunk(full["graph"], full["table"], D, max_batches=1, rows_cap=256, ent_cap=8192, train=True, feat_dim=F, hop2="ldsw")
+    eng = MiniBatchEngine(F, D, DEV, lr=R.LR, weight_decay=R.WD, resident=True)
+    params = R.init_params(D, 11)
+    p0 = R.flat(*params)
+    for b in (0, 61, 149):
+        nodes, lab = full["batches"][b], full["labels"][b]
+        one.build([nodes], [lab])
+        agg = O.aggregate_batch(full["rowptr"], full["col"], full["feat"], nodes, True, dtype=np.float64)
+        ref_loss, g = R.loss_and_grad64(agg, lab, params)
+        for t0 in (0, 10000):
+            m0, v0 = R.preload_state(g, p0, t0, b + t0)
+            R.load_state(eng, params, m0, v0, t0)
+            eng.xcd_wgs = 28
+            eng.train_chunk(one)
+            st = eng.xcd_status()
+            assert st["error"] == 0 and st["workgroups"] == 28, st
+            what = f"full-size batch {b} t0={t0}"
+            R.check_losses(eng.losses(1)[0], ref_loss, what)
+            R.check_step(eng, (p0, m0, v0, t0), g, what)
 
 
 def test_power_of_two_scaling_is_exact_over_the_whole_chunk(full):
