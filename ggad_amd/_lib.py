@@ -104,6 +104,16 @@ SIGNATURES = {
     "ggad_recon_rows_f32": (c_int32, [_P, _P, _L, _I, _P, _P]),
     "ggad_ocgnn_loss_f32": (c_int32, [_P, _P, _L, _I, _P, _F, _F, _P, _P, _P, _P]),
     "ggad_mb_score": (c_int32, [_P, _I, _I, _P, _I, _P, _P]),
+    "ggad_adae_gat_alpha_f32": (c_int32, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    "ggad_adae_gat_fwd_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "ggad_adae_gat_bwd_f32": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "ggad_adae_colsum_workspace_elems": (c_int64, [_I]),
+    "ggad_adae_colsum_f32": (c_int32, [_P, _P, _L, _I, _P, _P, _P]),
+    "ggad_adae_stru_fwd_workspace_elems": (c_int64, [_I, _I]),
+    "ggad_adae_stru_fwd_f32": (c_int32, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_adae_stru_bwd_workspace_elems": (c_int64, [_I, _I, _I]),
+    "ggad_adae_stru_bwd_f32": (c_int32, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_adae_attr_bwd_f32": (c_int32, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "ggad_gemm_workspace_elems": (c_int64, [_I, _I, _I]),
     "ggad_gemm_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _P, _I, _P, _P]),
     "ggad_spmm_seg_len": (c_int32, []),

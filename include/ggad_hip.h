@@ -194,6 +194,49 @@ int ggad_recon_rows_f32(const float *a, const float *t, int64_t n_rows, int32_t 
 int ggad_ocgnn_loss_f32(const float *emb, const int64_t *idx, int64_t n_idx, int32_t h, const float *center, float r, float beta,
                         float *loss, float *score, float *demb, ggad_stream_t stream);
 
+/* ---- full-graph AnomalyDAE (model_AnomalyDAE.py:115-300, anomalyDAE.py): GAT layer + fused reconstruction loss ----------------
+ * GAT layer = GATConv of torch_geometric 2.1 with the reference's defaults (one head, slope 0.2, stored self loops removed and one
+ * self loop added per node, bias).  Edges run from source r to target i where A_hat[r, i] > 0; target i aggregates over row i
+ * of A_hat^T (tptr / tcol / tval).  y = h W^T (N x F) comes from ggad_gemm_f32.
+ *   ggad_adae_gat_alpha_f32: als[r] = y_r . a_s, ald[r] = y_r . a_d.
+ *   ggad_adae_gat_fwd_f32:   z_i = sum_r softmax_r(leaky(als_r + ald_i)) y_r + bias (bias may be NULL); rmax / rsum = the row's
+ *                            softmax max and denominator, kept for the backward.
+ *   ggad_adae_gat_bwd_f32:   from g = d loss / d z: dals, dald (N each), dy (N x F); dpre = d loss / d pre-activation per edge,
+ *                            float[nnz + N] (slot tptr[i] + i + k: entry k of target row i, the added self loop last); tmap[e] =
+ *                            index in A_hat^T of entry e of A_hat (aptr / acol / aval).
+ *   ggad_adae_colsum_f32:    out[f] = sum_r w[r] M[r, f] (w NULL: 1) in a fixed order; ws = ggad_adae_colsum_workspace_elems(F).
+ * Reconstruction loss on the rows rows[0..n_rows) (int64, duplicate-free) of z (N x F), with rptr / rcol / rval = the compact CSR
+ * of A_hat[rows, :]:
+ *   attr_i = ||x_i - xhat_i||, stru_i = sqrt(sum_{j<N} (A_ij - sigmoid(z_i . z_j))^2), score_i = 0.5 attr_i + 0.5 stru_i,
+ *   loss = mean_i score_i (loss may be NULL: scoring only).  The N x N matrix is never formed; ws = ggad_adae_stru_fwd_workspace_elems;
+ *   s_edge (may be NULL): sigmoid(z_i . z_j) per entry of the compact CSR, what the backward reads.
+ * ggad_adae_stru_bwd_f32: dz (N x F, every row written) = d loss / d z scaled by *gloss (device float); pos[j] = position of node
+ *   j in rows or -1; tptr (N + 1) / trow / tedge = the entries of the compact CSR grouped by column (row position, entry index);
+ *   ws = ggad_adae_stru_bwd_workspace_elems; F <= 768.
+ * ggad_adae_attr_bwd_f32: dxhat rows `rows` = *gloss (0.5 / n_rows) (xhat - x) / attr (other rows untouched). */
+int ggad_adae_gat_alpha_f32(const float *y, const float *a_s, const float *a_d, int32_t n, int32_t F, float *als, float *ald,
+                            ggad_stream_t stream);
+int ggad_adae_gat_fwd_f32(const int32_t *tptr, const int32_t *tcol, const float *tval, const float *y, const float *als,
+                          const float *ald, const float *bias, int32_t n, int32_t F, float *z, float *rmax, float *rsum,
+                          ggad_stream_t stream);
+int ggad_adae_gat_bwd_f32(const int32_t *tptr, const int32_t *tcol, const float *tval, const int32_t *aptr, const int32_t *acol,
+                          const float *aval, const int32_t *tmap, const float *y, const float *als, const float *ald,
+                          const float *rmax, const float *rsum, const float *a_s, const float *a_d, const float *g, int32_t n,
+                          int32_t F, float *dpre, float *dals, float *dald, float *dy, ggad_stream_t stream);
+int64_t ggad_adae_colsum_workspace_elems(int32_t F);
+int ggad_adae_colsum_f32(const float *M, const float *w, int64_t n, int32_t F, float *out, float *ws, ggad_stream_t stream);
+int64_t ggad_adae_stru_fwd_workspace_elems(int32_t n_rows, int32_t n);
+int ggad_adae_stru_fwd_f32(const float *z, int32_t n, int32_t F, const int64_t *rows, int32_t n_rows, const int32_t *rptr,
+                           const int32_t *rcol, const float *rval, const float *x, const float *xhat, float *ws, float *s_edge,
+                           float *attr, float *stru, float *score, float *loss, ggad_stream_t stream);
+int64_t ggad_adae_stru_bwd_workspace_elems(int32_t n_rows, int32_t n, int32_t F);
+int ggad_adae_stru_bwd_f32(const float *z, int32_t n, int32_t F, const int64_t *rows, int32_t n_rows, const int32_t *rptr,
+                           const int32_t *rcol, const float *rval, const float *s_edge, const int32_t *pos, const int32_t *tptr,
+                           const int32_t *trow, const int32_t *tedge, const float *stru, const float *gloss, float *ws, float *dz,
+                           ggad_stream_t stream);
+int ggad_adae_attr_bwd_f32(const float *x, const float *xhat, const int64_t *rows, int32_t n_rows, int32_t F, const float *attr,
+                           const float *gloss, float *dxhat, ggad_stream_t stream);
+
 /* Device-atomic 2-hop stage (fallback of ggad_mb_plan_build, exported for completeness).  One wave per entry for
  * n_entries_cap entries (a host-side upper bound), true count read from *ent_total (= ent_ptr[n_rows]).
  * cnt2[slot][k] += 1 for every k in N(u), u an owner entry: column sums of the U x U2 mask
