@@ -47,14 +47,22 @@ class LinearBiasFn(torch.autograd.Function):
         return dx, gemm(dz, x, True, False), colsum(dz), None
 
 
+def _capturing(dev) -> bool:
+    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+
 def row_structs(adj: FullGraphAdj, idx) -> dict:
     """Device structures of one row list of the loss: the rows (int64), the compact CSR of A_hat[rows, :], the position of every
-    node in the list and the same entries grouped by column.  Cached on `adj` by contents; a list holding a node twice raises."""
+    node in the list and the same entries grouped by column.  Cached on `adj` by contents; a list holding a node twice raises.
+    The cache keeps at most 16 lists, except that a list looked up during a stream capture is pinned and never evicted: the
+    captured graph holds raw pointers to its structures, and nothing else keeps them alive."""
     arr = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).reshape(-1))
     cache = adj.__dict__.setdefault("_adae", {})
     key = ("rows", arr.size, hash(arr.tobytes()))
     s = cache.get(key)
     if s is not None and np.array_equal(s["host"], arr):
+        if _capturing(adj.dev):
+            s["pinned"] = True
         return s
     if arr.size == 0:
         raise ValueError("the loss needs at least one row")
@@ -73,9 +81,10 @@ def row_structs(adj: FullGraphAdj, idx) -> dict:
     dev = adj.dev
     s = dict(host=arr, n_rows=nr, rows=torch.from_numpy(arr).to(dev), rptr=_dev_i32(sub.indptr, dev), rcol=_dev_i32(sub.indices, dev),
              rval=_dev_f32(sub.data.astype(np.float32), dev), nnz=int(sub.nnz), pos=_dev_i32(pos, dev), tptr=_dev_i32(tptr, dev),
-             trow=_dev_i32(rl[order], dev), tedge=_dev_i32(order, dev))
-    if sum(1 for k in cache if isinstance(k, tuple) and k[0] == "rows") >= 16:
-        for k in [k for k in cache if isinstance(k, tuple) and k[0] == "rows"]:
+             trow=_dev_i32(rl[order], dev), tedge=_dev_i32(order, dev), pinned=_capturing(dev))
+    evictable = [k for k in cache if isinstance(k, tuple) and k[0] == "rows" and not cache[k]["pinned"]]
+    if len(evictable) >= 16:
+        for k in evictable:
             del cache[k]
     cache[key] = s
     return s

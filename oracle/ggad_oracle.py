@@ -627,6 +627,90 @@ def full_step_dense(P: Dict[str, torch.Tensor], feat: torch.Tensor, adj: torch.T
 
 
 # ----------------------------------------------------------------------------------
+# AnomalyDAE comparison model (`anomalyDAE.py`, `model_AnomalyDAE.py`), sparse float64 formulation
+# ----------------------------------------------------------------------------------
+ADAE_PARAM_ORDER = ["dense_stru.weight", "dense_stru.bias", "gat_layer.att_src", "gat_layer.att_dst", "gat_layer.bias",
+                    "gat_layer.lin_src.weight", "dense_attr_1.weight", "dense_attr_1.bias", "dense_attr_2.weight", "dense_attr_2.bias"]
+
+
+def _csr_coo(rowptr, col, val, dev):
+    """(row, column, value) per stored entry of a CSR triple, as int64 / float64 tensors on `dev` (explicit zeros kept)."""
+    rp = np.asarray(rowptr, dtype=np.int64)
+    r = torch.from_numpy(np.repeat(np.arange(len(rp) - 1, dtype=np.int64), np.diff(rp))).to(dev)
+    c = torch.from_numpy(np.asarray(col, dtype=np.int64)).to(dev)
+    v = torch.from_numpy(np.asarray(val, dtype=np.float64)).to(dev)
+    return r, c, v
+
+
+def adae_gat(h, W, att_src, att_dst, bias, rowptr, col, val):
+    """torch_geometric 2.1 GATConv with the reference's defaults (`model_AnomalyDAE.py:123,257`) on an edge list: edges run from
+    r to i where A_hat[r, i] > 0 and r != i (`neighList_to_edgeList` of `adj > 0`, then `remove_self_loops`), plus one self
+    loop per node (`add_self_loops`); the softmax runs over each target's incoming edges with 1e-16 in its denominator, then
+    the bias is added.  A_hat = (rowptr, col, val) in CSR, stored zeros and negative entries are not edges.  Never forms
+    N x N: the messages are one row of y per edge, summed per target.  Runs in the dtype / on the device of `h`."""
+    n = h.shape[0]
+    dev = h.device
+    y = h @ W.t()                                                          # lin_src(x)
+    als = (y * att_src.reshape(-1)).sum(-1)
+    ald = (y * att_dst.reshape(-1)).sum(-1)
+    r, c, v = _csr_coo(rowptr, col, val, dev)
+    keep = (v > 0) & (r != c)
+    loop = torch.arange(n, device=dev)
+    src = torch.cat((r[keep], loop))
+    dst = torch.cat((c[keep], loop))
+    e = F.leaky_relu(als[src] + ald[dst], 0.2)
+    emax = torch.full((n,), -np.inf, dtype=e.dtype, device=dev).scatter_reduce(0, dst, e.detach(), "amax")
+    ex = torch.exp(e - emax[dst])
+    den = torch.zeros(n, dtype=e.dtype, device=dev).index_add(0, dst, ex)
+    p = ex / (den[dst] + 1e-16)
+    return torch.zeros(n, y.shape[1], dtype=y.dtype, device=dev).index_add(0, dst, p[:, None] * y[src]) + bias
+
+
+def adae_recon(z, xhat, x, A_hat, rows, chunk_elems: int = 1 << 25):
+    """`double_recon_loss` of `model_AnomalyDAE.py:283-292` (weight 0.5, squared errors) on the rows R of (x, x_hat, A_hat,
+    sigmoid(z z^T)): attr_i = ||x_i - x_hat_i||, stru_i = ||A_hat_i - sigmoid(z_i z^T)||, score = 0.5 attr + 0.5 stru,
+    loss = mean(score).  A_hat = (rowptr, col, val) in CSR.  sigmoid(z[R] z^T) is formed a chunk of rows at a time (at most
+    `chunk_elems` entries) under activation checkpointing, so that no |R| x N block outlives its chunk; the backward recomputes
+    each chunk and the gradients come from autograd.  Returns (loss, score, attr, stru) in the dtype / on the device of z."""
+    from torch.utils.checkpoint import checkpoint
+    dev = z.device
+    n = z.shape[0]
+    rp = np.asarray(A_hat[0], dtype=np.int64)
+    col = np.asarray(A_hat[1], dtype=np.int64)
+    val = np.asarray(A_hat[2], dtype=np.float64)
+    R = np.asarray(rows, dtype=np.int64).reshape(-1)
+    ri = torch.from_numpy(R).to(dev)
+    attr = torch.sqrt(torch.sum((x[ri] - xhat[ri]) ** 2, 1))
+
+    def block(zr, zall, lr, lc, lv):
+        a = torch.zeros(zr.shape[0], n, dtype=zr.dtype, device=dev).index_put_((lr, lc), lv, accumulate=True)
+        return torch.sqrt(torch.sum((a - torch.sigmoid(zr @ zall.t())) ** 2, 1))
+
+    step = max(1, int(chunk_elems) // max(n, 1))
+    stru = []
+    for c0 in range(0, len(R), step):
+        rr = R[c0:c0 + step]
+        cnt = rp[rr + 1] - rp[rr]
+        lr = np.repeat(np.arange(len(rr), dtype=np.int64), cnt)
+        idx = np.arange(cnt.sum(), dtype=np.int64) + np.repeat(rp[rr] - (np.cumsum(cnt) - cnt), cnt)   # entries of the rows rr
+        args = (z[torch.from_numpy(rr).to(dev)], z, torch.from_numpy(lr).to(dev), torch.from_numpy(col[idx]).to(dev),
+                torch.from_numpy(val[idx]).to(device=dev, dtype=z.dtype))
+        stru.append(checkpoint(block, *args, use_reentrant=False) if z.requires_grad else block(*args))
+    stru = torch.cat(stru)
+    score = 0.5 * attr + 0.5 * stru
+    return score.mean(), score, attr, stru
+
+
+def adae_forward(P: Dict[str, torch.Tensor], x: torch.Tensor, A_hat):
+    """`Model.model_enc` (`model_AnomalyDAE.py:249-266`) on the parameters P (state_dict names, ADAE_PARAM_ORDER): h = ReLU(dense_stru
+    x), z = GAT(h), x_hat = dense_attr_2 ReLU(dense_attr_1 x).  Returns (x_hat, z)."""
+    h = F.relu(F.linear(x, P["dense_stru.weight"], P["dense_stru.bias"]))
+    z = adae_gat(h, P["gat_layer.lin_src.weight"], P["gat_layer.att_src"], P["gat_layer.att_dst"], P["gat_layer.bias"], *A_hat)
+    a = F.relu(F.linear(x, P["dense_attr_1.weight"], P["dense_attr_1.bias"]))
+    return F.linear(a, P["dense_attr_2.weight"], P["dense_attr_2.bias"]), z
+
+
+# ----------------------------------------------------------------------------------
 # TAM comparison model (`tam.py`, `model_tam.py`, `utils_tam.py`): truncated affinity maximisation
 # ----------------------------------------------------------------------------------
 def tam_split(ano_labels: np.ndarray, rng) -> Tuple[List[int], np.ndarray]:
