@@ -13,19 +13,22 @@ produced by the reference-exact host sampler beforehand -- `value` is therefore 
 throughput; `e2e_with_sampler` (extra key) times the reference's own window
 (`src/model_handler.py:332-365`) with the sampler thread inside it.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5          # what the round driver runs
+    python bench.py --gpus 1 --steps 20 --warmup 5          # the headline: set up, warm up, time K steps, print the line
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full   # + roofline, value_repeats, the extra legs and the CPU baselines
     python bench.py                                          # default: 9000 steps (steady state)
     python bench.py --steps K --warmup W --dump-outputs DIR  # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  `roofline` refers to the 2-hop gather-aggregate
+Prints ONE JSON line (rank 0).  A plain run measures the timed region only: `roofline`, `cpu_baseline`, `value_repeats` and
+`multi_gpu` are null and the extra keys are absent; `--full` measures them (several minutes), `--full --no-extras` only the
+roofline and its per-kernel entries.  `roofline` refers to the 2-hop gather-aggregate
 (`k_build_groups` + `k_gather2_items` + `k_gather2_combine`, the dominant launches of the path):
 `achieved` = ALGORITHMIC bytes (74 B per gathered neighbour of every (batch, owner) occurrence:
 68-byte feature row + 4-byte id + 2-byte streamed pair count) / launch time measured
 with HIP events on the launch stream.  Because occurrences of a node in several batches of a chunk
 share one fetch of its neighbour rows, algorithmic bytes exceed the HBM traffic; `hbm_bytes_per_neighbour`
 / `hbm_frac` (from the rocprofv3 PMC pass of the same command, profiles/) say what reaches memory.
-Extra keys (single GPU): `steady_state` (long run after the timed region), `e2e_with_sampler`,
+Extra keys (`--full`, single GPU): `steady_state` (long run after the timed region), `e2e_with_sampler`,
 `fullgraph` (epoch times of the four full-graph configs), `cpu_baseline` (dense-faithful CPU port
 of the reference's step on a bounded sample, rank 0).
 """
@@ -79,7 +82,11 @@ def parse():
     ap.add_argument("--fullgraph-epochs", type=int, default=30, help="extra leg: epochs timed per full-graph config (0 = skip)")
     ap.add_argument("--sparse-entries", type=int, default=8_600_000, help="extra leg: directed entries of the public-degree DGraph regime (0 = skip)")
     ap.add_argument("--cpu-fullgraph-budget", type=float, default=12.0, help="seconds of CPU time per variant and full-graph config of the cpu_baseline leg")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed region (no steady-state / e2e / full-graph / CPU legs)")
+    ap.add_argument("--full", action="store_true", help="also measure what goes beyond the headline: the roofline and its per-kernel entries "
+                    "(with an instrumented repeat of a one-chunk window), value_repeats, the steady-state / e2e / sparse-regime / full-graph "
+                    "legs, the CPU baselines and, at N > 1, the multi_gpu block with its alternative legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: the roofline only (no value repeats, steady-state / e2e / "
+                    "full-graph / CPU legs or multi-GPU alternative legs); a plain run has none of them anyway")
     ap.add_argument("--exchange", default="oneshot", choices=["oneshot", "rccl"],
                     help="multi-GPU gradient exchange: oneshot = peer-mapped buffers written inside the Adam launch (falls back to "
                          "rccl when its self-test fails), rccl = torch.distributed all-reduce between backward and Adam")
@@ -377,6 +384,7 @@ def main():
     # A run of ONE chunk (the driver's --steps 20) therefore carries only the two events around the gather inside the timed region;
     # the pair-counting kernel and the resident chunk kernel are event-timed in an instrumented REPEAT of the same window right
     # after it (same batches, same sizes; not part of `value`).  Long runs (many chunks) are instrumented in place: 12 launches.
+    # The events are recorded with or without --full, so that the timed region is the same window either way.
     instrument = {"all": len(trainer.default_ramp(a.steps)) > 1}
 
     def new_event():
@@ -449,7 +457,7 @@ def main():
     losses = trainer.engine.losses(a.steps)                # (before the repeat below overwrites the log slots)
     if a.dump_outputs and rank == 0:
         dump_outputs(a.dump_outputs, trainer.engine, losses[-1])          # (before the repeat below trains on)
-    if not instrument["all"] and world == 1:
+    if a.full and not instrument["all"] and world == 1:
         instrument["all"] = True
         trainer.run_steps(a.steps, prepared=timed, gather_hook=timed_build)
         barrier()
@@ -476,7 +484,7 @@ def main():
     # ---------------- the same window again, R times on FRESH batches (one 1.3 ms sample per headline; box-to-box and
     # run-to-run spread is the size of most changes).  `value` stays the first window above; these are extra keys.
     value_repeats = None
-    if not a.no_extras and not a.dp_path and a.steps <= 3000:
+    if a.full and not a.no_extras and not a.dp_path and a.steps <= 3000:
         reps_n = 7 if a.steps <= 1000 else 3
         vals = []
         for _ in range(reps_n):
@@ -501,7 +509,7 @@ def main():
 
     # ---------------- N > 1: what actually ran (the first multi-GPU run must explain itself)
     multi = None
-    if world > 1:
+    if world > 1 and a.full:
         tl = torch.tensor([elapsed_local], dtype=torch.float64, device=dev)
         alll = [torch.zeros_like(tl) for _ in range(world)]
         dist.all_gather(alll, tl)
@@ -521,125 +529,127 @@ def main():
                                           "values": [float(v) for v in per_rank],
                                           "note": "each rank's own finish of the timed window (before the closing barrier); ms_per_step of the line is the max-over-ranks bracket"}}
 
-    # ---------------- roofline of the dominant kernel
-    gather_ms, gather_nbrs, gather_batches, tile_ms = [], [], [], []
-    tile_nbrs, nbr_cache = [], {}
-    for i, (e0, e1, bn, t0_, t1_) in enumerate(ev_pairs):
-        ms = ctypes.c_float()
-        _lib.check(lib.ggad_event_elapsed_ms(e0, e1, ctypes.byref(ms)), "ggad_event_elapsed_ms")
-        key = (len(bn), bn[0].__array_interface__["data"][0])              # (the repeat builds the same batches again)
-        if key not in nbr_cache:
-            nbr_cache[key] = hop2_neighbours(bn)
-        if i < n_timed_pairs:                                                # (the roofline's launches: the timed region's own)
-            gather_ms.append(float(ms.value))
-            gather_nbrs.append(nbr_cache[key])
-            gather_batches.append(len(bn))
-        if t0_ is not None and lib.ggad_event_elapsed_ms(t0_, t1_, ctypes.byref(ms)) == 0:      # (none inside a one-chunk timed region)
-            tile_ms.append(float(ms.value))
-            tile_nbrs.append(nbr_cache[key])
-    dense_ms = [c0.elapsed_time(c1) for c0, c1, _ in chunk_ev]
-    dense_steps = [nb for _, _, nb in chunk_ev]
+    sizes = trainer.default_ramp(a.steps)
+    overlapped = bool(trainer.overlap and len(sizes) > 1)
+    roofline = None
+    if a.full:
+        # ---------------- roofline of the dominant kernel
+        gather_ms, gather_nbrs, gather_batches, tile_ms = [], [], [], []
+        tile_nbrs, nbr_cache = [], {}
+        for i, (e0, e1, bn, t0_, t1_) in enumerate(ev_pairs):
+            ms = ctypes.c_float()
+            _lib.check(lib.ggad_event_elapsed_ms(e0, e1, ctypes.byref(ms)), "ggad_event_elapsed_ms")
+            key = (len(bn), bn[0].__array_interface__["data"][0])              # (the repeat builds the same batches again)
+            if key not in nbr_cache:
+                nbr_cache[key] = hop2_neighbours(bn)
+            if i < n_timed_pairs:                                                # (the roofline's launches: the timed region's own)
+                gather_ms.append(float(ms.value))
+                gather_nbrs.append(nbr_cache[key])
+                gather_batches.append(len(bn))
+            if t0_ is not None and lib.ggad_event_elapsed_ms(t0_, t1_, ctypes.byref(ms)) == 0:      # (none inside a one-chunk timed region)
+                tile_ms.append(float(ms.value))
+                tile_nbrs.append(nbr_cache[key])
+        dense_ms = [c0.elapsed_time(c1) for c0, c1, _ in chunk_ev]
+        dense_steps = [nb for _, _, nb in chunk_ev]
+        mode = trainer.chunk.last_hop2
+        # algorithmic bytes per gathered neighbour (per occurrence), SURVEY.md section 8d: the feature row (4 F) + the column id (4) =
+        # 72 B at F = 17.  (The 2-byte per-pair count "ldsw" streams besides is this implementation's traffic, not the algorithm's.)
+        per_nbr = 4 * a.feat + 4
+        alg_bytes = [per_nbr * nb for nb in gather_nbrs]
+        ach = (sum(alg_bytes) / 1e9) / (sum(gather_ms) / 1e3) if gather_ms and sum(gather_ms) > 0 else None
+        kname = ("k_build_groups + k_gather2_items + k_gather2_combine (node-major 2-hop gather-aggregate: work items of <= 8 occurrences "
+                 "x 256 neighbours, streamed pair counts)") if mode == "ldsw" else "k_gather2 (2-hop gather-aggregate, device-atomic counters)"
+        # HBM-side bytes per gathered neighbour from the rocprofv3 PMC passes of this command (profiles/, FETCH_SIZE doubled as
+        # MI355X_MICROARCH prescribes for gfx950), keyed by batches per launch; nearest measured chunk size, else null
+        traffic = hbm_per_nbr = hbm_src = tile_hbm_per_nbr = None
+        pmc_name = next((f for f in ("r06_pmc_gather2_items.json", "r05_pmc_gather2_items.json", "r04_pmc_gather2_items.json", "r03_pmc_gather2_items.json")
+                         if os.path.exists(os.path.join(ROOT, "profiles", f))), None)
+        if mode == "ldsw" and pmc_name and gather_nbrs:
+            with open(os.path.join(ROOT, "profiles", pmc_name)) as fh:
+                pmc_doc = json.load(fh)
+                table = pmc_doc.get("by_batches_per_launch", {})
+                pmc_commit = pmc_doc.get("commit", "unknown")
+            if table:
+                mean_b = float(np.mean(gather_batches))
+                key = min(table, key=lambda k: abs(float(k) - mean_b))
+                if abs(float(key) - mean_b) <= 0.5 * mean_b:
+                    hbm_per_nbr = float(table[key]["hbm_bytes_per_neighbour"])
+                    traffic = hbm_per_nbr * float(np.mean(gather_nbrs))
+                    tile_hbm_per_nbr = table[key].get("k_tile_counts_hbm_bytes_per_neighbour")
+                    hbm_src = f"profiles/{pmc_name}[{key} batches per launch] (PMC passes of the build whose gather sources last changed in {pmc_commit})"
+        avg_ms = float(np.mean(gather_ms)) if gather_ms else None
+        roofline = {"kernel": kname, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": (ach / HBM_PEAK_GBS) if ach else None, "traffic": traffic,
+                    "achieved_is": "algorithmic bytes / launch time: every (batch, owner) occurrence is charged its neighbours' rows, "
+                                   "although occurrences of a node in several batches of a launch share one fetch -- not HBM traffic",
+                    "hbm_bytes_per_neighbour": hbm_per_nbr, "hbm_traffic_source": hbm_src,
+                    "hbm_frac": (traffic / 1e9 / (avg_ms / 1e3) / HBM_PEAK_GBS) if (traffic and avg_ms) else None,
+                    "launches": len(gather_ms), "avg_launch_ms": avg_ms,
+                    "batches_per_launch": gather_batches,
+                    "alg_bytes_per_launch": float(np.mean(alg_bytes)) if alg_bytes else None, "alg_bytes_per_neighbour": per_nbr,
+                    "gather_share_of_timed_region": (sum(gather_ms) / 1e3 * (len(sizes) / max(1, len(gather_ms)))) / elapsed if gather_ms else None,
+                    # with overlap the launches run on the plan stream's CU partition while the dense chain of the previous
+                    # chunk runs on the other CUs (the first chunk of a run has nothing to overlap with)
+                    "concurrent_with_dense_chain": overlapped,
+                    "cus": (256 - a.dense_cus) if (overlapped and a.dense_cus > 0) else 256}
+
+        # ---------------- the rest of the timed region, kernel by kernel (the gather is a third of it)
+        n_chunks_run = len(sizes)
+        scale_launches = n_chunks_run / max(1, len(gather_ms))
+        by_kernel = [{"kernel": "k_build_groups + k_gather2_items + k_gather2_combine", "replaces": "src/graphsage.py:335-348 (2-hop mask.mm)",
+                      "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": roofline["frac"], "traffic": traffic,
+                      "avg_launch_ms": avg_ms, "share_of_timed_region": roofline["gather_share_of_timed_region"]}]
+        if tile_ms:
+            # pair counting: reads the 4-byte column id of every (batch, owner) neighbour and writes its 2-byte pair count
+            t_alg = [6.0 * nb for nb in tile_nbrs]
+            t_ach = (sum(t_alg) / 1e9) / (sum(tile_ms) / 1e3)
+            t_traffic = (float(tile_hbm_per_nbr) * float(np.mean(gather_nbrs))) if tile_hbm_per_nbr else None
+            by_kernel.append({"kernel": "k_tile_counts (LDS pair counting per (tile of 32,768 ids, batch))", "replaces": "src/graphsage.py:335-348 (the U x U2 mask)",
+                              "bound": "hbm", "achieved": t_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": t_ach / HBM_PEAK_GBS,
+                              "traffic": t_traffic, "alg_bytes_per_neighbour": 6, "hbm_bytes_per_neighbour": tile_hbm_per_nbr,
+                              "avg_launch_ms": float(np.mean(tile_ms)),
+                              "note": "fetches several times its input (one 139-KB workgroup per CU: no round trip overlaps another, DESIGN 9.2)",
+                              "share_of_timed_region": (sum(tile_ms) / 1e3 * scale_launches) / elapsed})
+        if dense_ms:
+            us_step = 1e3 * sum(dense_ms) / max(1, sum(dense_steps))
+            resident = bool(trainer.engine.resident)
+            # issue time of the chunk kernel's instructions from the hardware counters of THIS command (scripts/pmc_chunk_xcd.sh ->
+            # profiles/r05_pmc_chunk_xcd.json, stamped with the commit of its sources, tests/test_profiles.py): SQ_ACTIVE_INST_ANY x 4
+            # clocks over the 112 SIMDs of the XCD's 28 compute units at 2.4 GHz
+            cx = None
+            cx_path = os.path.join(ROOT, "profiles", "r05_pmc_chunk_xcd.json")
+            if resident and os.path.exists(cx_path):
+                with open(cx_path) as fh:
+                    cx = json.load(fh)
+            issue_us = float(cx["issue_us_per_step"]) if cx and cx.get("issue_us_per_step") else None
+            by_kernel.append({"kernel": ("k_train_chunk_xcd (all optimiser steps of a chunk in one launch resident on one XCD, with its memset and "
+                                         "Adam-scalar launch)" if resident else "launch chain of the dense steps (5 launches per step)"),
+                              "replaces": "src/graphsage.py:395-454,171-258 + src/model_handler.py:356-364 (encoder, loss, backward, Adam)",
+                              "bound": "issue", "us_per_step": us_step, "avg_launch_ms": float(np.mean(dense_ms)),
+                              # < 30 MFLOP and < 2 MB per step: ~1 % of the FP32 and HBM rooflines of the whole chip; what the launch is made of
+                              # is instruction issue on one XCD and waiting (69 % of its wave cycles are parked at a barrier or a load)
+                              "issue_floor_us_per_step": issue_us, "frac": (issue_us / us_step) if issue_us else None,
+                              "issue_floor_source": (f"profiles/r05_pmc_chunk_xcd.json (SQ_ACTIVE_INST_ANY x 4 clocks / 112 SIMDs / 2.4 GHz; PMC passes of the "
+                                                     f"build whose chunk-kernel sources last changed in {cx.get('commit', 'unknown')})") if cx else None,
+                              "wave_instructions_per_wave_per_step": cx.get("wave_instructions_per_wave_per_step") if cx else None,
+                              "waves_parked_frac": (cx["counters"]["SQ_WAIT_ANY"] / cx["counters"]["SQ_WAVE_CYCLES"]) if cx else None,
+                              "flop_per_step": 3.0e7, "bytes_per_step": 2.0e6,
+                              "frac_of_fp32_peak": 3.0e7 / (us_step * 1e-6) / 157.3e12, "frac_of_hbm_peak": 2.0e6 / (us_step * 1e-6) / 8.0e12,
+                              "share_of_timed_region": (sum(dense_ms) / 1e3) / elapsed})
+        if roofline["frac"] and roofline["frac"] > 1.0:
+            roofline["frac_note"] = ("above 1 because `achieved` charges every (batch, owner) occurrence its neighbours' rows (the reference gathers "
+                                     "batch by batch) while a launch of many batches fetches the rows of a node that occurs in several of them "
+                                     "once: `hbm_frac` is the fraction of the HBM peak the launch actually moves")
+        roofline["by_kernel"] = by_kernel
+        roofline["by_kernel_measured_in"] = by_kernel_from
+        roofline["timed_region_accounted"] = float(sum(k["share_of_timed_region"] or 0.0 for k in by_kernel))
     del chunk_ev[:], chunk_ev_pool[:]          # (HIP events must not outlive the runtime: destroyed here, not at interpreter exit)
     for h in ev_pool:
         lib.ggad_event_destroy(h)
-    mode = trainer.chunk.last_hop2
-    sizes = trainer.default_ramp(a.steps)
-    overlapped = bool(trainer.overlap and len(sizes) > 1)
-    # algorithmic bytes per gathered neighbour (per occurrence), SURVEY.md section 8d: the feature row (4 F) + the column id (4) =
-    # 72 B at F = 17.  (The 2-byte per-pair count "ldsw" streams besides is this implementation's traffic, not the algorithm's.)
-    per_nbr = 4 * a.feat + 4
-    alg_bytes = [per_nbr * nb for nb in gather_nbrs]
-    ach = (sum(alg_bytes) / 1e9) / (sum(gather_ms) / 1e3) if gather_ms and sum(gather_ms) > 0 else None
-    kname = ("k_build_groups + k_gather2_items + k_gather2_combine (node-major 2-hop gather-aggregate: work items of <= 8 occurrences "
-             "x 256 neighbours, streamed pair counts)") if mode == "ldsw" else "k_gather2 (2-hop gather-aggregate, device-atomic counters)"
-    # HBM-side bytes per gathered neighbour from the rocprofv3 PMC passes of this command (profiles/, FETCH_SIZE doubled as
-    # MI355X_MICROARCH prescribes for gfx950), keyed by batches per launch; nearest measured chunk size, else null
-    traffic = hbm_per_nbr = hbm_src = tile_hbm_per_nbr = None
-    pmc_name = next((f for f in ("r06_pmc_gather2_items.json", "r05_pmc_gather2_items.json", "r04_pmc_gather2_items.json", "r03_pmc_gather2_items.json")
-                     if os.path.exists(os.path.join(ROOT, "profiles", f))), None)
-    if mode == "ldsw" and pmc_name and gather_nbrs:
-        with open(os.path.join(ROOT, "profiles", pmc_name)) as fh:
-            pmc_doc = json.load(fh)
-            table = pmc_doc.get("by_batches_per_launch", {})
-            pmc_commit = pmc_doc.get("commit", "unknown")
-        if table:
-            mean_b = float(np.mean(gather_batches))
-            key = min(table, key=lambda k: abs(float(k) - mean_b))
-            if abs(float(key) - mean_b) <= 0.5 * mean_b:
-                hbm_per_nbr = float(table[key]["hbm_bytes_per_neighbour"])
-                traffic = hbm_per_nbr * float(np.mean(gather_nbrs))
-                tile_hbm_per_nbr = table[key].get("k_tile_counts_hbm_bytes_per_neighbour")
-                hbm_src = f"profiles/{pmc_name}[{key} batches per launch] (PMC passes of the build whose gather sources last changed in {pmc_commit})"
-    avg_ms = float(np.mean(gather_ms)) if gather_ms else None
-    roofline = {"kernel": kname, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": (ach / HBM_PEAK_GBS) if ach else None, "traffic": traffic,
-                "achieved_is": "algorithmic bytes / launch time: every (batch, owner) occurrence is charged its neighbours' rows, "
-                               "although occurrences of a node in several batches of a launch share one fetch -- not HBM traffic",
-                "hbm_bytes_per_neighbour": hbm_per_nbr, "hbm_traffic_source": hbm_src,
-                "hbm_frac": (traffic / 1e9 / (avg_ms / 1e3) / HBM_PEAK_GBS) if (traffic and avg_ms) else None,
-                "launches": len(gather_ms), "avg_launch_ms": avg_ms,
-                "batches_per_launch": gather_batches,
-                "alg_bytes_per_launch": float(np.mean(alg_bytes)) if alg_bytes else None, "alg_bytes_per_neighbour": per_nbr,
-                "gather_share_of_timed_region": (sum(gather_ms) / 1e3 * (len(sizes) / max(1, len(gather_ms)))) / elapsed if gather_ms else None,
-                # with overlap the launches run on the plan stream's CU partition while the dense chain of the previous
-                # chunk runs on the other CUs (the first chunk of a run has nothing to overlap with)
-                "concurrent_with_dense_chain": overlapped,
-                "cus": (256 - a.dense_cus) if (overlapped and a.dense_cus > 0) else 256}
 
-    # ---------------- the rest of the timed region, kernel by kernel (the gather is a third of it)
-    n_chunks_run = len(sizes)
-    scale_launches = n_chunks_run / max(1, len(gather_ms))
-    by_kernel = [{"kernel": "k_build_groups + k_gather2_items + k_gather2_combine", "replaces": "src/graphsage.py:335-348 (2-hop mask.mm)",
-                  "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": roofline["frac"], "traffic": traffic,
-                  "avg_launch_ms": avg_ms, "share_of_timed_region": roofline["gather_share_of_timed_region"]}]
-    if tile_ms:
-        # pair counting: reads the 4-byte column id of every (batch, owner) neighbour and writes its 2-byte pair count
-        t_alg = [6.0 * nb for nb in tile_nbrs]
-        t_ach = (sum(t_alg) / 1e9) / (sum(tile_ms) / 1e3)
-        t_traffic = (float(tile_hbm_per_nbr) * float(np.mean(gather_nbrs))) if tile_hbm_per_nbr else None
-        by_kernel.append({"kernel": "k_tile_counts (LDS pair counting per (tile of 32,768 ids, batch))", "replaces": "src/graphsage.py:335-348 (the U x U2 mask)",
-                          "bound": "hbm", "achieved": t_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": t_ach / HBM_PEAK_GBS,
-                          "traffic": t_traffic, "alg_bytes_per_neighbour": 6, "hbm_bytes_per_neighbour": tile_hbm_per_nbr,
-                          "avg_launch_ms": float(np.mean(tile_ms)),
-                          "note": "fetches several times its input (one 139-KB workgroup per CU: no round trip overlaps another, DESIGN 9.2)",
-                          "share_of_timed_region": (sum(tile_ms) / 1e3 * scale_launches) / elapsed})
-    if dense_ms:
-        us_step = 1e3 * sum(dense_ms) / max(1, sum(dense_steps))
-        resident = bool(trainer.engine.resident)
-        # issue time of the chunk kernel's instructions from the hardware counters of THIS command (scripts/pmc_chunk_xcd.sh ->
-        # profiles/r05_pmc_chunk_xcd.json, stamped with the commit of its sources, tests/test_profiles.py): SQ_ACTIVE_INST_ANY x 4
-        # clocks over the 112 SIMDs of the XCD's 28 compute units at 2.4 GHz
-        cx = None
-        cx_path = os.path.join(ROOT, "profiles", "r05_pmc_chunk_xcd.json")
-        if resident and os.path.exists(cx_path):
-            with open(cx_path) as fh:
-                cx = json.load(fh)
-        issue_us = float(cx["issue_us_per_step"]) if cx and cx.get("issue_us_per_step") else None
-        by_kernel.append({"kernel": ("k_train_chunk_xcd (all optimiser steps of a chunk in one launch resident on one XCD, with its memset and "
-                                     "Adam-scalar launch)" if resident else "launch chain of the dense steps (5 launches per step)"),
-                          "replaces": "src/graphsage.py:395-454,171-258 + src/model_handler.py:356-364 (encoder, loss, backward, Adam)",
-                          "bound": "issue", "us_per_step": us_step, "avg_launch_ms": float(np.mean(dense_ms)),
-                          # < 30 MFLOP and < 2 MB per step: ~1 % of the FP32 and HBM rooflines of the whole chip; what the launch is made of
-                          # is instruction issue on one XCD and waiting (69 % of its wave cycles are parked at a barrier or a load)
-                          "issue_floor_us_per_step": issue_us, "frac": (issue_us / us_step) if issue_us else None,
-                          "issue_floor_source": (f"profiles/r05_pmc_chunk_xcd.json (SQ_ACTIVE_INST_ANY x 4 clocks / 112 SIMDs / 2.4 GHz; PMC passes of the "
-                                                 f"build whose chunk-kernel sources last changed in {cx.get('commit', 'unknown')})") if cx else None,
-                          "wave_instructions_per_wave_per_step": cx.get("wave_instructions_per_wave_per_step") if cx else None,
-                          "waves_parked_frac": (cx["counters"]["SQ_WAIT_ANY"] / cx["counters"]["SQ_WAVE_CYCLES"]) if cx else None,
-                          "flop_per_step": 3.0e7, "bytes_per_step": 2.0e6,
-                          "frac_of_fp32_peak": 3.0e7 / (us_step * 1e-6) / 157.3e12, "frac_of_hbm_peak": 2.0e6 / (us_step * 1e-6) / 8.0e12,
-                          "share_of_timed_region": (sum(dense_ms) / 1e3) / elapsed})
-    if roofline["frac"] and roofline["frac"] > 1.0:
-        roofline["frac_note"] = ("above 1 because `achieved` charges every (batch, owner) occurrence its neighbours' rows (the reference gathers "
-                                 "batch by batch) while a launch of many batches fetches the rows of a node that occurs in several of them "
-                                 "once: `hbm_frac` is the fraction of the HBM peak the launch actually moves")
-    roofline["by_kernel"] = by_kernel
-    roofline["by_kernel_measured_in"] = by_kernel_from
-    roofline["timed_region_accounted"] = float(sum(k["share_of_timed_region"] or 0.0 for k in by_kernel))
-
-    # ---------------- extra legs (single GPU): steady state, end to end with the sampler, the full-graph programs
+    # ---------------- extra legs (--full, single GPU): steady state, end to end with the sampler, the full-graph programs
     extras = {}
-    if rank == 0 and world == 1 and not a.no_extras and not a.dp_path:
+    if rank == 0 and world == 1 and a.full and not a.no_extras and not a.dp_path:
         if a.steady_steps > a.steps:
             # (300 untimed steps first: the buffers of 150-batch chunks grow on first use -- a device synchronisation each --, the
             #  timed region above only planned 20 batches)
@@ -677,7 +687,7 @@ def main():
                     except Exception as exc:
                         extras["fullgraph"][name]["cpu_baseline"] = {"error": repr(exc)}
 
-    if world > 1 and not a.no_extras and a.e2e_steps > 0:
+    if world > 1 and a.full and not a.no_extras and a.e2e_steps > 0:
         # multi-GPU: `value` above runs on a pre-generated schedule; what a ModelHandler.train() user sees has the sampler inside the
         # window -- per sampler mode, on every rank (all ranks take part; rank 0 reports)
         legs = {}
@@ -693,9 +703,9 @@ def main():
         legs["default_mode"] = a.dp_sampler
         extras["e2e_with_sampler"] = legs
 
-    # ---------------- CPU baseline: dense-faithful port of the reference's step, bounded sample
+    # ---------------- CPU baseline (--full): dense-faithful port of the reference's step, bounded sample
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_batches > 0 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and a.cpu_batches > 0 and not a.no_extras:
         from oracle import ggad_oracle as O
         ncores = os.cpu_count() or 1
         threads = min(24, ncores)                                       # README.md:21 "24-core CPU"
@@ -782,14 +792,14 @@ def main():
             "gpu_over_cpu": (value / cpu["value"]) if cpu else None,
             "gpu_over_cpu_is": "value / cpu_baseline.value (dense-faithful port of the reference's step)" if cpu else None,
             "gpu_over_cpu_sparse": (value / cpu["sparse_variant"]["value"]) if (cpu and cpu.get("sparse_variant")) else None,
-            "first_loss": float(losses[0][0]), "last_loss": float(losses[-1][0]), "setup_s": setup_s,
+            "first_loss": float(losses[0][0]), "last_loss": float(losses[-1][0]), "setup_s": setup_s, "full": a.full,
         }
         out.update(extras)
     else:
         out = None
     # ---------------- N > 1: the same window under the CONTRACTED design beside the default (RCCL all-reduce, one shared
     # schedule) -- three short legs on fresh batches.  Every rank takes part; a watchdog prints the line without them if a leg hangs.
-    if world > 1 and not a.no_extras:
+    if world > 1 and a.full and not a.no_extras:
         import threading
         done_flag = threading.Event()
 

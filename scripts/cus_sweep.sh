@@ -9,5 +9,5 @@ def run(args):
     except Exception as e:
         return out[-300:]
 for cus in "56 64 72 80 96 112".split():
-    print("dense_cus", cus, run(["--steps", "4500", "--warmup", "150", "--no-extras", "--dense-cus", cus]), flush=True)
+    print("dense_cus", cus, run(["--steps", "4500", "--warmup", "150", "--full", "--no-extras", "--dense-cus", cus]), flush=True)
 PY

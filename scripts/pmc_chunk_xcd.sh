@@ -1,6 +1,6 @@
 #!/bin/bash
 # Regenerates profiles/r0N_pmc_chunk_xcd.json from THIS build: hardware counters of k_train_chunk_xcd (the dense steps of a chunk as one
-# launch resident on one XCD) in the K = 20 command the driver runs -- bench.py --steps 20 --warmup 5 --no-extras --, one rocprofv3 pass
+# launch resident on one XCD) in the K = 20 window and its instrumented repeat -- bench.py --full --steps 20 --warmup 5 --no-extras --, one rocprofv3 pass
 # per counter group (--kernel-trace only).  bench.py reads its `issue_us_per_step` for the chunk kernel's `by_kernel` entry.
 # Usage (GPU box): GGAD_COMMIT=$(git log -1 --format=%h -- ggad_amd/csrc/step_xcd.hip ggad_amd/csrc/step_common.h) bash scripts/pmc_chunk_xcd.sh [tag]
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -9,10 +9,10 @@ cd /tmp && export TMPDIR=/tmp
 OUT=/tmp/cx
 rm -rf $OUT; mkdir -p $OUT
 i=0
-rocprofv3 --kernel-trace -d $OUT/t -o t -- python $R/bench.py --steps 20 --warmup 5 --no-extras > $OUT/t.log 2>&1
+rocprofv3 --kernel-trace -d $OUT/t -o t -- python $R/bench.py --full --steps 20 --warmup 5 --no-extras > $OUT/t.log 2>&1
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_MFMA SQ_INSTS_SMEM" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS" "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" "GRBM_GUI_ACTIVE SQ_WAVES SQ_LDS_IDX_ACTIVE"; do
   i=$((i+1))
-  timeout 300 rocprofv3 --kernel-trace --pmc $grp -d $OUT/p$i -o p -- python $R/bench.py --steps 20 --warmup 5 --no-extras > $OUT/p$i.log 2>&1 || echo "pass $i ($grp) failed"
+  timeout 300 rocprofv3 --kernel-trace --pmc $grp -d $OUT/p$i -o p -- python $R/bench.py --full --steps 20 --warmup 5 --no-extras > $OUT/p$i.log 2>&1 || echo "pass $i ($grp) failed"
 done
 python3 - <<PY
 import glob, json, sqlite3
@@ -37,7 +37,7 @@ for d in dbs("$OUT/p*/**/*.db"):
         ctr[cn] = [dd[k] for k in sorted(dd)]
 steps = 20
 pick = lambda v: float(sum(v[-2:]) / len(v[-2:])) if v else None      # the two 20-step launches (timed window + its repeat)
-out = {"note": "k_train_chunk_xcd in bench.py --steps 20 --warmup 5 --no-extras: rocprofv3 PMC, one counter group per run (--kernel-trace only); values = mean "
+out = {"note": "k_train_chunk_xcd in bench.py --full --steps 20 --warmup 5 --no-extras: rocprofv3 PMC, one counter group per run (--kernel-trace only); values = mean "
                "of the two 20-step launches, whole launch (all workgroups, including the 7 x 28 that leave at once).  SQ_* cycle counters are in "
                "quad-cycles (MI355X_MICROARCH.md), instruction counters in wave-instructions.  issue_us_per_step = SQ_ACTIVE_INST_ANY x 4 clocks / "
                "(28 CUs x 4 SIMDs) / 2.4 GHz / 20 steps: the time the launch's instructions need if every SIMD of the XCD issued one of them at a time "

@@ -10,7 +10,7 @@ def run(args):
         return out[-300:]
 # one process per variant is slow (setup 20 s each): do a few only
 for ramp in ["7,7", "14", "10", "20", "12"]:
-    print("ramp", ramp, run(["--steps", "20", "--warmup", "5", "--no-extras", "--ramp", ramp]), flush=True)
-print("default600", run(["--steps", "600", "--warmup", "150", "--no-extras"]), flush=True)
-print("default9000", run(["--no-extras"]), flush=True)
+    print("ramp", ramp, run(["--steps", "20", "--warmup", "5", "--full", "--no-extras", "--ramp", ramp]), flush=True)
+print("default600", run(["--steps", "600", "--warmup", "150", "--full", "--no-extras"]), flush=True)
+print("default9000", run(["--full", "--no-extras"]), flush=True)
 PY

@@ -260,7 +260,7 @@ def test_bench_launch_line_two_ranks_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "30",
            "--nodes", "200000", "--entries", "4000000", "--chunk", "30",
-           "--e2e-steps", "60", "--e2e-reps", "2"]
+           "--e2e-steps", "60", "--e2e-reps", "2", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
