@@ -1,0 +1,203 @@
+#!/usr/bin/env python3
+"""Full-graph AEGIS comparison run on one MI355X:  python aegis.py --dataset reddit [--synthetic]
+
+Same command line, per-dataset defaults (lr 1e-3 Amazon / reddit, 5e-4 t_finance; epochs reddit 500 / t_finance 1500 / Amazon 800;
+elsewhere --lr and --num_epoch are required), seeding and prints as the reference's `aegis.py`:
+
+- pre-training, `recon_num_epoch` epochs on normal_label_idx: loss_ae backward and a step of `optimiser_ae` (all parameters, lr
+  1e-3) with NO zero_grad, so the gradients accumulate across these epochs, as there; one `ae_loss` line per epoch;
+- main loop on all_idx (the shuffled permutation of the split): zero_grad of `optimiser` (all parameters, --lr) and `optimiser_gen`
+  (the generator, --lr, no weight decay), loss_g and loss_ae backpropagated, `optimiser` then `optimiser_gen` stepped -- the
+  generator gets two Adam updates from one gradient.  The reference pins torch 1.11, whose zero_grad zeroes gradients instead of
+  dropping them; here every parameter with a gradient gets a fresh one each main epoch, so FlatAdam.zero_grad (None) gives the
+  same updates;
+- every 5 main epochs: train_loss (the reference prints loss_ae under that name), AUROC / AP of the epoch's test scores (from the
+  training forward, before the step) and the total time.
+Pre-training runs eager; the main epoch is captured as a hipGraph at main epoch 2 and replayed (unless --no_graph).  The forward's
+noise is drawn from the CPU generator every epoch in the reference's order and copied into the buffer the captured epoch reads.
+`--affinity_dir DIR`: at the epochs the reference plots (every 20), the three arrays it hands to draw_pdf_methods go to
+DIR/aegis_<dataset>_affinity_<epoch>.npz (normal, generated, anomalous); the 'anomalous' nodes are np.array(all_idx)[ano_label == 1]
+as the reference writes it -- with all_idx shuffled these are not the anomalies (a reference quirk, kept).  Plotting is out of scope.
+`--synthetic` / `--device` / `--quiet` / `--no_graph` as in `anomalyDAE.py`.
+"""
+import argparse
+import os
+import random
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ggad_amd import synth  # noqa: E402
+from ggad_amd.fullgraph import FlatAdam, FullGraphAdj  # noqa: E402
+from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
+from ggad_amd.model_aegis import Model  # noqa: E402
+from ggad_amd.utils import load_mat, normalize_adj, preprocess_features, split_nodes  # noqa: E402
+from run import SIZES  # noqa: E402
+
+LR = {"Amazon": 1e-3, "t_finance": 5e-4, "reddit": 1e-3}
+EPOCHS = {"reddit": 500, "t_finance": 1500, "Amazon": 800}
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description="")
+    p.add_argument("--dataset", type=str, default="reddit")
+    p.add_argument("--lr", type=float)
+    p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--embedding_dim", type=int, default=300)
+    p.add_argument("--num_epoch", type=int)
+    p.add_argument("--recon_num_epoch", type=int, default=10)
+    p.add_argument("--drop_prob", type=float, default=0.0)
+    p.add_argument("--batch_size", type=int, default=300)
+    p.add_argument("--subgraph_size", type=int, default=4)
+    p.add_argument("--readout", type=str, default="avg")
+    p.add_argument("--auc_test_rounds", type=int, default=256)
+    p.add_argument("--negsamp_ratio", type=int, default=1)
+    p.add_argument("--synthetic", action="store_true", help="generate a graph of the dataset's size instead of loading ./dataset/*.mat")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--quiet", action="store_true")
+    p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the main training epoch")
+    p.add_argument("--affinity_dir", type=str, default=None, help="write the arrays the reference plots every 20 epochs here")
+    a = p.parse_args(argv)
+    if a.lr is None:
+        a.lr = LR.get(a.dataset)
+    if a.num_epoch is None:
+        a.num_epoch = EPOCHS.get(a.dataset)
+    if a.lr is None or a.num_epoch is None:
+        p.error("no default lr / num_epoch for dataset {!r}: pass --lr and --num_epoch".format(a.dataset))
+    return a
+
+
+def load(args):
+    """(adj, features, ano_label, all_idx, idx_test, normal_label_idx) as the reference's load_mat returns them."""
+    if args.synthetic or not os.path.exists("./dataset/{}.mat".format(args.dataset)):
+        if not args.synthetic:
+            print("./dataset/{}.mat not found: using a synthetic graph of the same size".format(args.dataset))
+        n, ne, f, rate = SIZES[args.dataset]
+        rowptr, col = synth.make_graph(n, ne, args.seed, kind="powerlaw", max_degree=max(64, n // 8), exact=True)
+        adj = synth.csr_to_scipy(rowptr, col, n)
+        feat = sp.lil_matrix(synth.make_features(n, f, args.seed))
+        ano = synth.make_labels(n, rate, args.seed)
+        all_idx, _, _, idx_test, normal_idx, _ = split_nodes(ano, args.dataset, verbose=not args.quiet)
+        return adj, feat, ano, all_idx, idx_test, normal_idx
+    adj, feat, _, all_idx, _, _, idx_test, ano, _, _, normal_idx, _ = load_mat(args.dataset)
+    return adj, feat, ano, all_idx, idx_test, normal_idx
+
+
+def setup(args, dev):
+    """Graph, features, model and the three optimisers as aegis.py:71-100 builds them (CSR adjacency in HBM)."""
+    adj, features, ano_label, all_idx, idx_test, normal_idx = load(args)
+    if args.dataset in ["Amazon", "tf_finace", "reddit", "elliptic"]:                 # aegis.py:77 (typo kept: never T-Finance)
+        features = preprocess_features(features)
+    else:
+        features = np.asarray(features.todense())
+    nb_nodes, ft_size = features.shape
+    full = FullGraphAdj(normalize_adj(adj) + sp.eye(nb_nodes), adj + sp.eye(nb_nodes), dev)     # :86-90
+    feats = torch.FloatTensor(np.asarray(features, dtype=np.float32)[np.newaxis]).to(dev)
+    model = Model(ft_size, args.embedding_dim, "prelu", args.negsamp_ratio, args.readout).to(dev)
+    optimiser_ae = FlatAdam(model.parameters(), lr=1e-3, weight_decay=args.weight_decay)
+    optimiser = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
+    optimiser_gen = FlatAdam(model.generator.parameters(), lr=args.lr)
+    return (full, feats, model, optimiser_ae, optimiser, optimiser_gen, np.asarray(ano_label), list(all_idx),
+            np.asarray(idx_test, dtype=np.int64), list(normal_idx))
+
+
+def draw_arrays(affinity1, affinity2, all_idx, ano_label):
+    """The three arrays aegis.py:155-166 hands to draw_pdf_methods."""
+    real_abn = np.array(all_idx)[np.argwhere(ano_label == 1).squeeze()].tolist()
+    real_nrm = np.array(all_idx)[np.argwhere(ano_label == 0).squeeze()].tolist()
+    return affinity1[real_nrm], affinity2[:500], np.sort(affinity1[real_abn], kind="stable")[:50]
+
+
+def make_main_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test):
+    def main_epoch():
+        optimiser.zero_grad()
+        optimiser_gen.zero_grad()
+        loss_ae, loss_g, score, z, z_gen, _ = model.train_forward(feats, full, all_idx, idx_test)
+        torch.autograd.backward([loss_g, loss_ae])                 # loss_g.backward(); loss_dis.backward() (loss_dis is loss_ae)
+        optimiser.step()
+        optimiser_gen.step()
+        return loss_ae.detach(), score.detach(), z.detach(), z_gen.detach()
+    return main_epoch
+
+
+def main():
+    args = parse()
+    print("Dataset: ", args.dataset)
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    random.seed(args.seed)
+    if not torch.cuda.is_available():
+        sys.exit("aegis.py needs an MI355X: there is no CPU fallback")
+    torch.set_num_threads(min(8, os.cpu_count() or 1))
+    dev = torch.device("cuda", args.device)
+    torch.cuda.set_device(dev)      # the C-ABI launches on the CURRENT device's stream: it must be the one the tensors live on
+    full, feats, model, optimiser_ae, optimiser, optimiser_gen, ano_label, all_idx, idx_test, normal_idx = setup(args, dev)
+    y_test_dev = torch.as_tensor(ano_label[idx_test].astype(np.int64), device=dev)
+    n = full.n
+    for epoch in range(args.recon_num_epoch):                        # aegis.py:118-124
+        loss_ae = model.train_forward(feats, full, normal_idx, idx_test)[0]
+        loss_ae.backward()
+        optimiser_ae.step()
+        loss_ae = loss_ae.detach()          # (nothing of an eager autograd graph may survive into the capture)
+        print("Epoch:", "%04d" % epoch, "ae_loss=", "{:.5f}".format(loss_ae.item()))
+    main_epoch = make_main_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test)
+    total_time, epoch_times = 0.0, []
+    graph, static, noise_buf = None, None, None
+    if args.affinity_dir:
+        os.makedirs(args.affinity_dir, exist_ok=True)
+    for epoch in range(args.num_epoch):
+        start_time = time.time()
+        model.train()
+        if not args.no_graph and graph is None and epoch == 2:
+            noise_buf = torch.zeros(n, model.noise_dim, device=dev)
+            model.noise_override = noise_buf
+            # nothing of the eager epochs' autograd graphs may survive into the capture (their AccumulateGrad nodes are bound to
+            # the default stream)
+            loss_ae = score = z = z_gen = None
+            optimiser_ae.zero_grad()
+            optimiser.zero_grad()
+            optimiser_gen.zero_grad()
+            import gc
+            gc.collect()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                static = main_epoch()
+            model.noise_override = None
+            print("training epoch captured as a hipGraph", flush=True)
+        if graph is not None:
+            noise_buf.copy_(torch.randn(n, model.noise_dim))       # this epoch's draw (model_AEGIS.py:226), in the reference's order
+            graph.replay()
+            loss_ae, score, z, z_gen = static
+        else:
+            loss_ae, score, z, z_gen = main_epoch()
+        if epoch % 20 == 0 and args.affinity_dir:                   # aegis.py:148-166 (the arrays; no plot)
+            a1 = Model.affinity(z, full).cpu().numpy()
+            a2 = Model.affinity(z_gen, full).cpu().numpy()
+            nrm, gen, abn = draw_arrays(a1, a2, all_idx, ano_label)
+            np.savez(os.path.join(args.affinity_dir, "aegis_{}_affinity_{}.npz".format(args.dataset, epoch)), normal=nrm, generated=gen,
+                     anomalous=abn)
+        if epoch % 5 == 0:
+            print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss_ae.item()))
+            model.eval()
+            sc = score.view(-1)
+            print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(sc, y_test_dev)))
+            print("Testing AP:", average_precision(sc, y_test_dev))
+            if not args.quiet:
+                print("Total time is", total_time)
+        torch.cuda.synchronize()
+        epoch_times.append(time.time() - start_time)
+        total_time += epoch_times[-1]
+    if epoch_times:
+        med = float(np.median(epoch_times))
+        print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. one-off structure building / module load)".format(
+            med * 1e3, n / med, epoch_times[0] * 1e3))
+
+
+if __name__ == "__main__":
+    main()

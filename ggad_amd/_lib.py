@@ -114,6 +114,16 @@ SIGNATURES = {
     "ggad_adae_stru_bwd_workspace_elems": (c_int64, [_I, _I, _I]),
     "ggad_adae_stru_bwd_f32": (c_int32, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ggad_adae_attr_bwd_f32": (c_int32, [_P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "ggad_aegis_bn_channels": (c_int32, []),
+    "ggad_aegis_bn_groups": (c_int32, [_L]),
+    "ggad_aegis_bn_rows_per_group": (c_int32, []),
+    "ggad_aegis_bn_workspace_elems": (c_int64, [_L, _I]),
+    "ggad_aegis_bn_fwd_f32": (c_int32, [_P, _L, _L, _P, _L, _L, _I, _P, _P, _F, _F, _P, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P,
+                                        _P, _P, _P]),
+    "ggad_aegis_bn_bwd_f32": (c_int32, [_P, _L, _L, _I, _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_aegis_loss_workspace_elems": (c_int64, [_L, _L]),
+    "ggad_aegis_loss_fwd_f32": (c_int32, [_P, _L, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P]),
+    "ggad_aegis_loss_bwd_f32": (c_int32, [_P, _L, _P, _P, _P, _I, _P, _L, _P, _L, _P, _P, _P, _P]),
     "ggad_gemm_workspace_elems": (c_int64, [_I, _I, _I]),
     "ggad_gemm_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _P, _I, _P, _P]),
     "ggad_spmm_seg_len": (c_int32, []),

@@ -237,6 +237,44 @@ int ggad_adae_stru_bwd_f32(const float *z, int32_t n, int32_t F, const int64_t *
 int ggad_adae_attr_bwd_f32(const float *x, const float *xhat, const int64_t *rows, int32_t n_rows, int32_t F, const float *attr,
                            const float *gloss, float *dxhat, ggad_stream_t stream);
 
+/* ---- full-graph AEGIS (model_AEGIS.py, aegis.py): the batch-norm heads of its two MLPs and its two losses ----------------------
+ * ggad_aegis_bn_fwd_f32: BatchNorm1d in training mode over the M = m1 + m2 rows of two row blocks h1 (m1 x C, row stride ld1) and h2
+ *   (m2 x C, ld2; m2 = 0: one block), the statistics of their concatenation, fused with act (0 = ReLU, 1 = sigmoid):
+ *     y = act(gamma (h - mean) invstd + beta),  invstd = 1 / sqrt(var + eps), var biased;
+ *   mean / invstd (C floats each) are written for the backward; running_mean / running_var (unbiased variance, momentum) and the
+ *   int64 num_batches_tracked are updated in place (each may be NULL: not updated).  Output rows k = rows[k] of the concatenation
+ *   (rows NULL: k < n_out <= M): y (row stride ldy) when w2 is NULL, else the head p[k] = sigmoid(y . w2 + b2) without y.
+ *   M < 2 -> GGAD_E_INVALID (torch: more than 1 value per channel); C != ggad_aegis_bn_channels() -> GGAD_E_UNSUPPORTED, nothing
+ *   launched.  Rows are 16-byte aligned (strides multiples of 4).  ws = ggad_aegis_bn_workspace_elems(M, C) floats; ticket = one
+ *   zeroed int32 the kernels leave zero.  Two launches.
+ * ggad_aegis_bn_bwd_f32: the backward of one block (h: M x C, ldh) from dy (M x C, lddy) or, with the head (w2 non-NULL), from p and
+ *   dp = d loss / d p: dh (lddh), dgamma, dbeta and dw2 (C), db2 (1).  Same refusals, workspace and ticket.  Two launches.
+ * ggad_aegis_loss_fwd_f32: loss_g = mean_{i<n} -max(log1p(-p_i), -100) (BCE against 0) and loss_ae = mean_k ||x_r - zd_r||, r =
+ *   rows[k] (x: n x F, zd: row stride ldz >= F); attr[k] = ||x_r - zd_r|| is kept for the backward.  One launch; ws =
+ *   ggad_aegis_loss_workspace_elems(n, n_rows); ticket as above.
+ * ggad_aegis_loss_bwd_f32: dp[i] = *gloss_g p_i / max(p_i (1 - p_i), 1e-12) / n (dp may be NULL) and dzd (n x ldz, every element
+ *   written: *gloss_ae (zd - x) / (n_rows attr) on the listed rows (pos[i] = position in rows or -1) below column F, 0 elsewhere;
+ *   dzd may be NULL).  One launch. */
+int32_t ggad_aegis_bn_channels(void);
+int32_t ggad_aegis_bn_groups(int64_t M);
+int32_t ggad_aegis_bn_rows_per_group(void);
+int64_t ggad_aegis_bn_workspace_elems(int64_t M, int32_t C);
+int ggad_aegis_bn_fwd_f32(const float *h1, int64_t m1, int64_t ld1, const float *h2, int64_t m2, int64_t ld2, int32_t C,
+                          const float *gamma, const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                          int64_t *num_batches_tracked, int32_t act, const int64_t *rows, int64_t n_out, float *y, int64_t ldy,
+                          const float *w2, const float *b2, float *p, float *mean, float *invstd, float *ws, int32_t *ticket,
+                          ggad_stream_t stream);
+int ggad_aegis_bn_bwd_f32(const float *h, int64_t M, int64_t ldh, int32_t C, const float *gamma, const float *beta, const float *mean,
+                          const float *invstd, int32_t act, const float *dy, int64_t lddy, const float *w2, const float *p,
+                          const float *dp, float *dh, int64_t lddh, float *dgamma, float *dbeta, float *dw2, float *db2, float *ws,
+                          int32_t *ticket, ggad_stream_t stream);
+int64_t ggad_aegis_loss_workspace_elems(int64_t n, int64_t n_rows);
+int ggad_aegis_loss_fwd_f32(const float *p, int64_t n, const float *x, int32_t F, const float *zd, int64_t ldz, const int64_t *rows,
+                            int64_t n_rows, float *attr, float *loss_g, float *loss_ae, float *ws, int32_t *ticket, ggad_stream_t stream);
+int ggad_aegis_loss_bwd_f32(const float *p, int64_t n, const float *gloss_g, float *dp, const float *x, int32_t F, const float *zd,
+                            int64_t ldz, const int32_t *pos, int64_t n_rows, const float *attr, const float *gloss_ae, float *dzd,
+                            ggad_stream_t stream);
+
 /* Device-atomic 2-hop stage (fallback of ggad_mb_plan_build, exported for completeness).  One wave per entry for
  * n_entries_cap entries (a host-side upper bound), true count read from *ent_total (= ent_ptr[n_rows]).
  * cnt2[slot][k] += 1 for every k in N(u), u an owner entry: column sums of the U x U2 mask
