@@ -275,6 +275,27 @@ int ggad_aegis_loss_bwd_f32(const float *p, int64_t n, const float *gloss_g, flo
                             int64_t ldz, const int32_t *pos, int64_t n_rows, const float *attr, const float *gloss_ae, float *dzd,
                             ggad_stream_t stream);
 
+/* ---- full-graph GAAN (model_gaan.py, gaan.py): the edge loss over A_hat --------------------------------------------------------
+ * The edge set E holds m entries (erow[e], ecol[e]) in the reference's order: the rows of the duplicate-free row list in list order,
+ * each with its columns j ascending where (normalize_adj(A) + I)[i, j] > 0.  emb and z are N x C, row-major, 16-byte aligned.
+ * ggad_gaan_edge_fwd_f32: a_e = sigmoid(<emb_i, emb_j>) (written to a_out, m floats, for the backward), a'_e = sigmoid(<z_i, z_j>);
+ *   loss[1] = mean_e -max(log1p(-a'_e), -100) (BCE against 0), loss[2] = mean_e -max(log(a_e), -100) (BCE against 1),
+ *   loss[0] = (loss[1] + loss[2]) / 2.  ws = ggad_gaan_edge_fwd_workspace_elems(m) floats.  Two launches.
+ * ggad_gaan_edge_bwd_f32: dE (N x C, every row written) = G emb + G^T emb with G_e = ((*gloss / 2 / m) (a_e - 1) /
+ *   max((1 - a_e) a_e, 1e-12)) (1 - a_e) a_e on E.  pos[k] = position of node k in the row list (-1: absent), rptr (n_rows + 1) the
+ *   row list's offsets into E; tptr (N + 1) / trow / tedge: the entries (i, k) of E grouped by k, trow = i, tedge = e, ascending e.
+ *   small (n_small) and big (n_big) partition the N nodes: a node of `small` has at most ggad_gaan_bwd_small_count() entries on its
+ *   row and column sides together.  One launch.
+ * Both: C != ggad_gaan_edge_channels() -> GGAD_E_UNSUPPORTED, nothing launched.  No atomics: every sum has a fixed order. */
+int32_t ggad_gaan_edge_channels(void);
+int32_t ggad_gaan_bwd_small_count(void);
+int64_t ggad_gaan_edge_fwd_workspace_elems(int64_t m);
+int ggad_gaan_edge_fwd_f32(const float *emb, const float *z, int64_t n, int32_t C, const int32_t *erow, const int32_t *ecol, int64_t m,
+                           float *a_out, float *ws, float *loss, ggad_stream_t stream);
+int ggad_gaan_edge_bwd_f32(const float *emb, int64_t n, int32_t C, const int32_t *pos, const int32_t *rptr, const int32_t *ecol,
+                           const int32_t *tptr, const int32_t *trow, const int32_t *tedge, const float *a, int64_t m, const float *gloss,
+                           const int32_t *small, int64_t n_small, const int32_t *big, int64_t n_big, float *dE, ggad_stream_t stream);
+
 /* Device-atomic 2-hop stage (fallback of ggad_mb_plan_build, exported for completeness).  One wave per entry for
  * n_entries_cap entries (a host-side upper bound), true count read from *ent_total (= ent_ptr[n_rows]).
  * cnt2[slot][k] += 1 for every k in N(u), u an owner entry: column sums of the U x U2 mask
