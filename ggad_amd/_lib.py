@@ -129,6 +129,13 @@ SIGNATURES = {
     "ggad_gaan_edge_fwd_workspace_elems": (c_int64, [_L]),
     "ggad_gaan_edge_fwd_f32": (c_int32, [_P, _P, _L, _I, _P, _P, _L, _P, _P, _P, _P]),
     "ggad_gaan_edge_bwd_f32": (c_int32, [_P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P, _L, _P, _L, _P, _P]),
+    "ggad_dominant_ae_supported": (c_int32, [_I, _I]),
+    "ggad_dominant_tickets": (c_int32, []),
+    "ggad_dominant_ae_workspace_elems": (c_int64, [_L, _L, _I, _I]),
+    "ggad_dominant_ae_f32": (c_int32, [_P, _I, _P, _L, _L, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_dominant_recon_workspace_elems": (c_int64, [_L, _L, _L]),
+    "ggad_dominant_recon_f32": (c_int32, [_P, _P, _L, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_dominant_scale_f32": (c_int32, [_P, _L, _P, _P, _P]),
     "ggad_gemm_workspace_elems": (c_int64, [_I, _I, _I]),
     "ggad_gemm_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _P, _I, _P, _P]),
     "ggad_spmm_seg_len": (c_int32, []),

@@ -296,6 +296,28 @@ int ggad_gaan_edge_bwd_f32(const float *emb, int64_t n, int32_t C, const int32_t
                            const int32_t *tptr, const int32_t *trow, const int32_t *tedge, const float *a, int64_t m, const float *gloss,
                            const int32_t *small, int64_t n_small, const int32_t *big, int64_t n_big, float *dE, ggad_stream_t stream);
 
+/* ---- full-graph DOMINANT (model_domaint.py, dominant.py): the attribute autoencoder x_ = W2 relu(W1 x + b1) + b2 and its loss -----
+ * x is N x F row-major; rows (int64) holds the train list (m >= 1 rows) followed by the test list (t_rows >= 0 rows).  W1 is H x F,
+ * W2 F x H (nn.Linear weights), b1 (H), b2 (F).  e_r = ||x_r - x_r_hat||.
+ * ggad_dominant_ae_f32: one launch: loss[0] = mean of e over the train rows, score[k] = e of test row k, and the gradients at
+ *   d loss = 1 (dW1 H x F, dB1 H, dW2 F x H, dB2 F; every element written).  Only the listed rows are evaluated.  (F, H) outside
+ *   ggad_dominant_ae_supported -> GGAD_E_UNSUPPORTED, nothing launched.  ws = ggad_dominant_ae_workspace_elems(m, t_rows, F, H)
+ *   floats; tickets = ggad_dominant_tickets() int32, zero, left zero.  Fixed-order sums, no float atomics.
+ * ggad_dominant_recon_f32: one launch from a computed x_ (xh, N x F): loss[0], score as above and dxh (N x F, every element
+ *   written) = (xh - x) / (e m) on the train rows (pos[i] = position of node i in the train list, -1 off it), 0 elsewhere.
+ *   ws = ggad_dominant_recon_workspace_elems(n, m, t_rows) floats; ticket = one zeroed int32, left zero.
+ * ggad_dominant_scale_f32: dst[i] = src[i] * g[0] for i < n (g in device memory).  One launch. */
+int32_t ggad_dominant_ae_supported(int32_t F, int32_t H);
+int32_t ggad_dominant_tickets(void);
+int64_t ggad_dominant_ae_workspace_elems(int64_t m, int64_t t_rows, int32_t F, int32_t H);
+int ggad_dominant_ae_f32(const float *x, int32_t F, const int64_t *rows, int64_t m, int64_t t_rows, const float *W1, const float *b1,
+                         const float *W2, const float *b2, int32_t H, float *score, float *loss, float *dW1, float *dB1, float *dW2,
+                         float *dB2, float *ws, int32_t *tickets, ggad_stream_t stream);
+int64_t ggad_dominant_recon_workspace_elems(int64_t n, int64_t m, int64_t t_rows);
+int ggad_dominant_recon_f32(const float *x, const float *xh, int64_t n, int32_t F, const int64_t *rows, int64_t m, int64_t t_rows,
+                            const int32_t *pos, float *score, float *loss, float *dxh, float *ws, int32_t *ticket, ggad_stream_t stream);
+int ggad_dominant_scale_f32(const float *src, int64_t n, const float *g, float *dst, ggad_stream_t stream);
+
 /* Device-atomic 2-hop stage (fallback of ggad_mb_plan_build, exported for completeness).  One wave per entry for
  * n_entries_cap entries (a host-side upper bound), true count read from *ent_total (= ent_ptr[n_rows]).
  * cnt2[slot][k] += 1 for every k in N(u), u an owner entry: column sums of the U x U2 mask
