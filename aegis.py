@@ -18,7 +18,8 @@ noise is drawn from the CPU generator every epoch in the reference's order and c
 `--affinity_dir DIR`: at the epochs the reference plots (every 20), the three arrays it hands to draw_pdf_methods go to
 DIR/aegis_<dataset>_affinity_<epoch>.npz (normal, generated, anomalous); the 'anomalous' nodes are np.array(all_idx)[ano_label == 1]
 as the reference writes it -- with all_idx shuffled these are not the anomalies (a reference quirk, kept).  Plotting is out of scope.
-`--synthetic` / `--device` / `--quiet` / `--no_graph` as in `anomalyDAE.py`.
+`--device_noise` (opt-in): from the main loop on, the same stream continues on the device (ggad_amd.rng) and the draw opens the captured
+epoch.  `--synthetic` / `--device` / `--quiet` / `--no_graph` as in `anomalyDAE.py`.
 """
 import argparse
 import os
@@ -62,6 +63,8 @@ def parse(argv=None):
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the main training epoch")
     p.add_argument("--affinity_dir", type=str, default=None, help="write the arrays the reference plots every 20 epochs here")
+    p.add_argument("--device_noise", action="store_true", help="draw the per-epoch noise on the device from torch's own CPU stream "
+                   "(ggad_amd.rng): the draw is the first node of the captured epoch; values agree with the host's to float32 rounding")
     a = p.parse_args(argv)
     if a.lr is None:
         a.lr = LR.get(a.dataset)
@@ -150,49 +153,70 @@ def main():
     graph, static, noise_buf = None, None, None
     if args.affinity_dir:
         os.makedirs(args.affinity_dir, exist_ok=True)
-    for epoch in range(args.num_epoch):
-        start_time = time.time()
-        model.train()
-        if not args.no_graph and graph is None and epoch == 2:
-            noise_buf = torch.zeros(n, model.noise_dim, device=dev)
-            model.noise_override = noise_buf
-            # nothing of the eager epochs' autograd graphs may survive into the capture (their AccumulateGrad nodes are bound to
-            # the default stream)
-            loss_ae = score = z = z_gen = None
-            optimiser_ae.zero_grad()
-            optimiser.zero_grad()
-            optimiser_gen.zero_grad()
-            import gc
-            gc.collect()
+    # --device_noise: the CPU generator continues on the device from here on; the draw opens every epoch (and the captured one), and
+    # the host generator gets the advanced state back when the loop ends
+    mt = None
+    if args.device_noise:
+        from ggad_amd.rng import DeviceMT
+        mt = DeviceMT.from_host(dev)
+        noise_buf = torch.zeros(n, model.noise_dim, device=dev)
+        model.noise_override = noise_buf
+        host_epoch = main_epoch
+
+        def main_epoch():
+            mt.randn_(noise_buf)                                # this epoch's draw (model_AEGIS.py:226), in the reference's order
+            return host_epoch()
+    try:
+        for epoch in range(args.num_epoch):
+            start_time = time.time()
+            model.train()
+            if not args.no_graph and graph is None and epoch == 2:
+                if mt is None:
+                    noise_buf = torch.zeros(n, model.noise_dim, device=dev)
+                    model.noise_override = noise_buf
+                # nothing of the eager epochs' autograd graphs may survive into the capture (their AccumulateGrad nodes are bound to
+                # the default stream)
+                loss_ae = score = z = z_gen = None
+                optimiser_ae.zero_grad()
+                optimiser.zero_grad()
+                optimiser_gen.zero_grad()
+                import gc
+                gc.collect()
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    static = main_epoch()
+                if mt is None:
+                    model.noise_override = None
+                print("training epoch captured as a hipGraph", flush=True)
+            if graph is not None:
+                if mt is None:
+                    noise_buf.copy_(torch.randn(n, model.noise_dim))       # this epoch's draw (model_AEGIS.py:226), in the reference's order
+                graph.replay()
+                loss_ae, score, z, z_gen = static
+            else:
+                loss_ae, score, z, z_gen = main_epoch()
+            if epoch % 20 == 0 and args.affinity_dir:                   # aegis.py:148-166 (the arrays; no plot)
+                a1 = Model.affinity(z, full).cpu().numpy()
+                a2 = Model.affinity(z_gen, full).cpu().numpy()
+                nrm, gen, abn = draw_arrays(a1, a2, all_idx, ano_label)
+                np.savez(os.path.join(args.affinity_dir, "aegis_{}_affinity_{}.npz".format(args.dataset, epoch)), normal=nrm, generated=gen,
+                         anomalous=abn)
+            if epoch % 5 == 0:
+                print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss_ae.item()))
+                model.eval()
+                sc = score.view(-1)
+                print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(sc, y_test_dev)))
+                print("Testing AP:", average_precision(sc, y_test_dev))
+                if not args.quiet:
+                    print("Total time is", total_time)
             torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static = main_epoch()
+            epoch_times.append(time.time() - start_time)
+            total_time += epoch_times[-1]
+    finally:
+        if mt is not None:
             model.noise_override = None
-            print("training epoch captured as a hipGraph", flush=True)
-        if graph is not None:
-            noise_buf.copy_(torch.randn(n, model.noise_dim))       # this epoch's draw (model_AEGIS.py:226), in the reference's order
-            graph.replay()
-            loss_ae, score, z, z_gen = static
-        else:
-            loss_ae, score, z, z_gen = main_epoch()
-        if epoch % 20 == 0 and args.affinity_dir:                   # aegis.py:148-166 (the arrays; no plot)
-            a1 = Model.affinity(z, full).cpu().numpy()
-            a2 = Model.affinity(z_gen, full).cpu().numpy()
-            nrm, gen, abn = draw_arrays(a1, a2, all_idx, ano_label)
-            np.savez(os.path.join(args.affinity_dir, "aegis_{}_affinity_{}.npz".format(args.dataset, epoch)), normal=nrm, generated=gen,
-                     anomalous=abn)
-        if epoch % 5 == 0:
-            print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss_ae.item()))
-            model.eval()
-            sc = score.view(-1)
-            print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(sc, y_test_dev)))
-            print("Testing AP:", average_precision(sc, y_test_dev))
-            if not args.quiet:
-                print("Total time is", total_time)
-        torch.cuda.synchronize()
-        epoch_times.append(time.time() - start_time)
-        total_time += epoch_times[-1]
+            mt.to_host()
     if epoch_times:
         med = float(np.median(epoch_times))
         print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. one-off structure building / module load)".format(

@@ -13,7 +13,8 @@ reference's `gaan.py`:
   time of the epochs before this one.
 The epoch is captured as a hipGraph at epoch 2 and replayed (unless --no_graph), both optimisers inside it.  The forward's noise is
 drawn from the CPU generator every epoch in the reference's order and copied into the buffer the captured epoch reads.
-`--synthetic` / `--device` / `--quiet` / `--no_graph` as in `aegis.py`.
+`--device_noise` (opt-in): the same stream continues on the device (ggad_amd.rng) and the draw opens the captured epoch; the host does
+nothing between replays.  `--synthetic` / `--device` / `--quiet` / `--no_graph` as in `aegis.py`.
 """
 import argparse
 import os
@@ -55,6 +56,8 @@ def parse(argv=None):
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the training epoch")
+    p.add_argument("--device_noise", action="store_true", help="draw the per-epoch noise on the device from torch's own CPU stream "
+                   "(ggad_amd.rng): the draw is the first node of the captured epoch; values agree with the host's to float32 rounding")
     a = p.parse_args(argv)
     if a.lr is None:
         a.lr = LR.get(a.dataset)
@@ -126,42 +129,63 @@ def main():
     epoch_fn = make_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test)
     total_time, epoch_times = 0.0, []
     graph, static, noise_buf = None, None, None
-    for epoch in range(args.num_epoch):
-        start_time = time.time()
-        model.train()
-        if not args.no_graph and graph is None and epoch == 2:
-            noise_buf = torch.zeros(n, model.noise_dim, device=dev)
-            model.noise_override = noise_buf
-            # nothing of the eager epochs' autograd graphs may survive into the capture
-            loss = score = None
-            model.emb = None
-            optimiser.zero_grad()
-            optimiser_gen.zero_grad()
-            import gc
-            gc.collect()
+    # --device_noise: the CPU generator continues on the device from here on; the draw opens every epoch (and the captured one), and
+    # the host generator gets the advanced state back when the loop ends
+    mt = None
+    if args.device_noise:
+        from ggad_amd.rng import DeviceMT
+        mt = DeviceMT.from_host(dev)
+        noise_buf = torch.zeros(n, model.noise_dim, device=dev)
+        model.noise_override = noise_buf
+        host_epoch = epoch_fn
+
+        def epoch_fn():
+            mt.randn_(noise_buf)                                # this epoch's draw (model_gaan.py:311), in the reference's order
+            return host_epoch()
+    try:
+        for epoch in range(args.num_epoch):
+            start_time = time.time()
+            model.train()
+            if not args.no_graph and graph is None and epoch == 2:
+                if mt is None:
+                    noise_buf = torch.zeros(n, model.noise_dim, device=dev)
+                    model.noise_override = noise_buf
+                # nothing of the eager epochs' autograd graphs may survive into the capture
+                loss = score = None
+                model.emb = None
+                optimiser.zero_grad()
+                optimiser_gen.zero_grad()
+                import gc
+                gc.collect()
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    static = epoch_fn()
+                if mt is None:
+                    model.noise_override = None
+                print("training epoch captured as a hipGraph", flush=True)
+            if graph is not None:
+                if mt is None:
+                    noise_buf.copy_(torch.randn(n, model.noise_dim))       # this epoch's draw (model_gaan.py:311), in the reference's order
+                graph.replay()
+                loss, score = static
+            else:
+                loss, score = epoch_fn()
+            if epoch % 5 == 0:
+                print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss.item()))
+                model.eval()
+                sc = score.view(-1)
+                print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(sc, y_test_dev)))
+                print("Testing AP:", average_precision(sc, y_test_dev))
+                if not args.quiet:
+                    print("Total time is", total_time)
             torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static = epoch_fn()
+            epoch_times.append(time.time() - start_time)
+            total_time += epoch_times[-1]
+    finally:
+        if mt is not None:
             model.noise_override = None
-            print("training epoch captured as a hipGraph", flush=True)
-        if graph is not None:
-            noise_buf.copy_(torch.randn(n, model.noise_dim))       # this epoch's draw (model_gaan.py:311), in the reference's order
-            graph.replay()
-            loss, score = static
-        else:
-            loss, score = epoch_fn()
-        if epoch % 5 == 0:
-            print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss.item()))
-            model.eval()
-            sc = score.view(-1)
-            print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(sc, y_test_dev)))
-            print("Testing AP:", average_precision(sc, y_test_dev))
-            if not args.quiet:
-                print("Total time is", total_time)
-        torch.cuda.synchronize()
-        epoch_times.append(time.time() - start_time)
-        total_time += epoch_times[-1]
+            mt.to_host()
     if epoch_times:
         med = float(np.median(epoch_times))
         print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. one-off structure building / module load)".format(

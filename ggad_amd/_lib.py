@@ -214,6 +214,9 @@ SIGNATURES = {
     "ggad_mt_getrandbits32": (c_uint32, [c_void_p]),
     "ggad_sched_batches": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32,
                                      c_void_p, c_void_p]),
+    "ggad_mt_state_words": (c_int32, []),
+    "ggad_mt_randn_scratch_elems": (c_int64, [_L]),
+    "ggad_mt_randn_f32": (c_int32, [_P, _P, _L, _F, _F, _P, _P]),
 }
 
 

@@ -9,7 +9,8 @@ Same constructor order (so the same seed gives the same initial weights: every n
 then xavier'd, unused gcn3 / fc5 / fc6 / disc consume RNG too), same parameter names (state_dict interchange),
 same output shapes.  `adj` may be the reference's dense (1,N,N) tensor -- converted once and cached -- or,
 preferably, a `ggad_amd.fullgraph.FullGraphAdj`.  The N(mean,var) noise of `model.py:143` is drawn from the CPU
-generator exactly like the reference (also in eval mode) and then moved to the GPU.
+generator exactly like the reference (also in eval mode) and then moved to the GPU -- or, with the attribute `device_noise` set to a
+`ggad_amd.rng.DeviceMT`, drawn on the GPU from that same stream (same words consumed, values equal to float32 rounding).
 """
 from __future__ import annotations
 
@@ -133,6 +134,13 @@ class Model(nn.Module):
             hit = cache[key] = (arr, torch.from_numpy(arr).to(dev))
         return hit[1]
 
+    def _noise_buf(self, n_abn, width, dev):
+        """The buffer `device_noise` draws into: allocated once per shape (the eager epochs before a capture create it)."""
+        buf = self.__dict__.get("_dn_buf")
+        if buf is None or buf.shape != (1, n_abn, width) or buf.device != dev:
+            buf = self.__dict__["_dn_buf"] = torch.empty(1, n_abn, width, device=dev)
+        return buf
+
     def _score(self, x):
         if mlp_score_supported(self.fc1.weight, self.fc2.weight, self.fc3.weight):
             return MlpScoreFn.apply(x, self.fc1.weight, self.fc2.weight, self.fc3.weight)      # model.py:176-180 in one launch
@@ -147,6 +155,7 @@ class Model(nn.Module):
         h_1 = GcnLayerFn.apply(x, self.gcn1.fc.weight, self.gcn1.bias, self.gcn1.act.weight, fa)
         emb = GcnLayerFn.apply(h_1, self.gcn2.fc.weight, self.gcn2.bias, self.gcn2.act.weight, fa)      # (N, H)
         override = self.__dict__.get("noise_override")
+        device_noise = self.__dict__.get("device_noise")
         if train_flag and self.__dict__.get("fused_head", True):
             hs = fa.head_structs(normal_idx, sample_abnormal_idx)
             if hs is not None:
@@ -154,6 +163,8 @@ class Model(nn.Module):
                 # accumulation fused.  The noise is the reference's CPU draw (:143) or the captured epoch's static buffer.
                 if override is not None:
                     noise = override
+                elif device_noise is not None:
+                    noise = device_noise.randn_(self._noise_buf(hs["n_abn"], emb.shape[1], dev), args.var, args.mean)
                 else:
                     noise = (torch.randn(1, hs["n_abn"], emb.shape[1]) * args.var + args.mean).to(dev)
                 emb_out, emb_combine, f_3, emb_con, emb_abn = GgadHeadFn.apply(
@@ -166,6 +177,9 @@ class Model(nn.Module):
         if override is not None:
             # captured epoch (run.py): the caller drew the very same CPU noise and copied it into this static device buffer
             emb_abnormal = emb_abnormal + override
+        elif device_noise is not None:
+            # the same draw on the device (ggad_amd.rng): the evaluation forward lands here and consumes the same words as the host's
+            emb_abnormal = emb_abnormal + device_noise.randn_(self._noise_buf(emb_abnormal.shape[1], emb.shape[1], dev), args.var, args.mean)
         else:
             noise = torch.randn(emb_abnormal.size()) * args.var + args.mean                             # CPU generator, :143
             emb_abnormal = emb_abnormal + noise.to(dev)

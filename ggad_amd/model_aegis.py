@@ -274,11 +274,17 @@ class Model(nn.Module):
         self.discriminator2 = MLP(n_h, hid_dim, 1, encoder_layers, 0.0, torch.sigmoid)
         self.n_in = n_in
         self.noise_override = None
+        self.device_noise = None
 
     # ------------------------------------------------------------------------------------------------ pieces
     def _noise(self, n, dev):
         if self.noise_override is not None:
             return self.noise_override.reshape(n, self.noise_dim)
+        if self.device_noise is not None:                                                   # the same draw on the device (ggad_amd.rng)
+            buf = self.__dict__.get("_dn_buf")
+            if buf is None or buf.shape != (n, self.noise_dim) or buf.device != dev:
+                buf = self.__dict__["_dn_buf"] = torch.empty(n, self.noise_dim, device=dev)
+            return self.device_noise.randn_(buf)
         return torch.randn(n, self.noise_dim).to(dev)                                       # model_AEGIS.py:226: the CPU generator
 
     def _check_mode(self):

@@ -206,11 +206,17 @@ class Model(nn.Module):
         self.generator = MLP(noise_dim, hid_dim, n_in, generator_layers, 0.0, F.relu)
         self.discriminator = MLP(n_in, hid_dim, hid_dim, encoder_layers, 0.0, F.relu)
         self.noise_override = None
+        self.device_noise = None
         self.emb = None
 
     def _noise(self, n, dev):
         if self.noise_override is not None:
             return self.noise_override.reshape(n, self.noise_dim)
+        if self.device_noise is not None:                                                   # the same draw on the device (ggad_amd.rng)
+            buf = self.__dict__.get("_dn_buf")
+            if buf is None or buf.shape != (n, self.noise_dim) or buf.device != dev:
+                buf = self.__dict__["_dn_buf"] = torch.empty(n, self.noise_dim, device=dev)
+            return self.device_noise.randn_(buf)
         return torch.randn(n, self.noise_dim).to(dev)                                       # model_gaan.py:311: the CPU generator
 
     def train_forward(self, seq1, adj, idx_train, idx_test):

@@ -833,6 +833,20 @@ int ggad_sched_batches(ggad_mt19937 *, int64_t *train, int64_t n_train, int64_t 
                        int32_t n_pseudo, int32_t batches_per_epoch, int32_t *in_epoch_io, int32_t count, int64_t *out_nodes,
                        int32_t *out_len);
 
+/* ------------------------------------------------------------------------------------
+ * torch.randn's CPU stream continued on the DEVICE (rng.hip).  `state`: ggad_mt_state_words() uint32 in device memory -- the 624
+ * MT19937 words of torch's CPU generator, then at [624] the number of words of that block already consumed (0..624; 624: the next
+ * draw regenerates the block first, which is also what a freshly seeded generator asks for).  One call is what
+ * `torch.randn(n) * scale + shift` (float32, n >= 16) computes on the host: it advances `state` in place by n words, or n + 16 when
+ * n % 16 != 0 (torch redraws the last 16 outputs), and writes out[i] = normal_i * scale + shift, product and sum rounded
+ * separately.  Values agree with the host's to float32 rounding of log / sin / cos, not bit for bit; the state is exact.  Everything
+ * stays on the device: a captured launch draws fresh values at every replay.  `scratch`: ggad_mt_randn_scratch_elems(n) uint32
+ * (the raw words).  n < 16 (a different algorithm in torch) or a null pointer -> GGAD_E_INVALID, nothing launched.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_mt_state_words(void);
+int64_t ggad_mt_randn_scratch_elems(int64_t n);
+int ggad_mt_randn_f32(uint32_t *state, float *out, int64_t n, float scale, float shift, uint32_t *scratch, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

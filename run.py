@@ -7,7 +7,8 @@ seeding, same prints, same evaluation cadence (AUROC / AP on idx_test every 10 e
 arithmetic of the epoch -- two GCN layers, outlier generation, scorer MLP, BCE + local-affinity margin +
 reconstruction loss, backward, Adam -- runs in the HIP kernels of libggad_hip.so (sparse CSR / edge-parallel
 instead of the reference's dense N x N tensors).  Extra flags: `--synthetic` (no dataset ships with this repo:
-builds a graph of the dataset's published size from the seed), `--device`.
+builds a graph of the dataset's published size from the seed), `--device`, `--device_noise` (opt-in: the N(mean, var)
+noise is drawn on the device from torch's own CPU stream, `ggad_amd/rng.py`; the draw opens the captured epoch).
 """
 import argparse
 import os
@@ -51,6 +52,9 @@ def parse():
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--no_graph", action="store_true", help="launch every kernel of every epoch from Python instead of replaying a "
                    "captured hipGraph of the training epoch (same kernels, same order, same results)")
+    p.add_argument("--device_noise", action="store_true", help="draw the N(mean, var) noise on the device from torch's own CPU stream "
+                   "(ggad_amd.rng): the draw becomes the first node of the captured epoch; values agree with the host's to float32 "
+                   "rounding")
     a = p.parse_args()
     if a.lr is None:
         a.lr = 1e-3
@@ -103,6 +107,27 @@ def main():
 
 
 def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history=None):
+    """`_fit`, on the host's noise (the default) or -- `args.device_noise`, or GGAD_DEVICE_NOISE=1 where `args` does not say -- with the
+    CPU generator continued on the device (ggad_amd.rng): snapshotted before the first epoch, handed back when the loop ends, also
+    on an exception."""
+    device_noise = getattr(args, "device_noise", None)
+    if device_noise is None:
+        device_noise = os.environ.get("GGAD_DEVICE_NOISE", "0") == "1"
+    if not device_noise:
+        return _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history)
+    from ggad_amd.rng import DeviceMT
+    mt = DeviceMT.from_host(dev)
+    model.device_noise = mt
+    if history is not None:
+        history["noise"] = "device"
+    try:
+        return _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history, mt)
+    finally:
+        model.device_noise = model.noise_override = None
+        mt.to_host()
+
+
+def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history=None, device_mt=None):
     """The training loop of the reference's script (`run.py:137-240`): Adam, `num_epoch` epochs, an evaluation forward (which draws
     noise too, quirk 5) every 10th epoch.  `history` (a dict, tests / the end-of-training parity report): filled with the four loss
     terms of every epoch, the AUROC / AP of every evaluation, and -- one extra evaluation after the last epoch, which the reference
@@ -122,10 +147,15 @@ def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx
     n_abn = len(abnormal_label_idx)
 
     one = torch.ones((), dtype=torch.float32, device=dev)
+    device_buf = torch.zeros(1, n_abn, args.embedding_dim, device=dev) if device_mt is not None else None
 
     def train_epoch():
+        if device_mt is not None:                # the first launches of the epoch: this epoch's draw, on the device
+            model.noise_override = device_mt.randn_(device_buf, args.var, args.mean)
         optimiser.zero_grad()
         emb, emb_combine, logits, emb_con, emb_abnormal = model(feats, full, abnormal_label_idx, normal_label_idx, True, args)
+        if device_mt is not None:
+            model.noise_override = None          # (the evaluation forward draws for itself: model.device_noise)
         out = ggad_loss(emb, logits, emb_con, emb_abnormal, full, ls, 0.7)
         out[0].backward(gradient=one)            # (d loss / d loss = 1 from a kept tensor: autograd would fill a new one every epoch)
         optimiser.step()
@@ -136,8 +166,9 @@ def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx
         model.train()
         # (where launch gaps matter: an eager epoch under 20 ms -- T-Finance size, 5.3 ms of kernels, still gains 2.5 %)
         if not args.no_graph and graph is None and epoch == 2 and epoch_times[1] < float(os.environ.get("GGAD_CAPTURE_BELOW_S", "20e-3")):
-            noise_buf = torch.zeros(1, n_abn, args.embedding_dim, device=dev)
-            model.noise_override = noise_buf
+            if device_mt is None:
+                noise_buf = torch.zeros(1, n_abn, args.embedding_dim, device=dev)
+                model.noise_override = noise_buf
             # nothing of the eager epochs' autograd graphs may survive into the capture (their AccumulateGrad nodes are
             # bound to the default stream)
             loss = loss_margin = loss_bce = loss_rec = None
@@ -149,8 +180,13 @@ def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx
             with torch.cuda.graph(graph):
                 static = train_epoch()
             model.noise_override = None
+            if device_mt is not None:
+                print("training epoch captured as a hipGraph", flush=True)
             # the capture itself does not execute: fall through and replay it for this epoch
-        if graph is not None:
+        if graph is not None and device_mt is not None:
+            graph.replay()              # the draw is the first node of the captured epoch: nothing to do on the host
+            loss, loss_margin, loss_bce, loss_rec = static
+        elif graph is not None:
             noise = pending_noise
             if noise is None:
                 noise = torch.randn(1, n_abn, args.embedding_dim) * args.var + args.mean  # same draw as Model.forward
