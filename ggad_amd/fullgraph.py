@@ -643,10 +643,20 @@ class FullGraphAdj:
             pos_n[J[:nn_]] = np.arange(nn_, dtype=np.int32)
             pos_a[J[nn_:]] = np.arange(nn_, len(J), dtype=np.int32)
             seg_unique = len(np.unique(J[:nn_])) == nn_ and len(np.unique(J[nn_:])) == len(J) - nn_
+            # a node twice INSIDE a list (never drawn by run.py): the scatter-add of c_j S_j onto the rows J goes in rounds, round k
+            # holding the k-th occurrence of every node -- duplicate-free, so no two waves of one launch write the same row
+            rounds = None
+            if not seg_unique:
+                order = np.argsort(J, kind="stable")
+                first = np.concatenate(([True], J[order][1:] != J[order][:-1]))
+                start = np.maximum.accumulate(np.where(first, np.arange(len(J)), 0))
+                occ = np.empty(len(J), dtype=np.int64)
+                occ[order] = np.arange(len(J)) - start
+                rounds = [(_dev_i32(np.flatnonzero(occ == k), self.dev), _dev_i32(J[occ == k], self.dev)) for k in range(int(occ.max()) + 1)]
             s = dict(J=_dev_i32(J, self.dev), n_normal=len(key[0]), n_out=len(key[1]), distinct=bool(len(np.unique(J)) == len(J)),
                      r_inv_J=_dev_f32(self.r_inv_host[J], self.dev), RJ=Csr(sub.T.tocsr(), self.dev),
                      Rt_plan=self.Rt.plan(J, key=("rows", key)), pos_n=_dev_i32(pos_n, self.dev), pos_a=_dev_i32(pos_a, self.dev),
-                     seg_unique=bool(seg_unique))
+                     seg_unique=bool(seg_unique), rounds=rounds)
             self._loss[key] = s
         return s
 
@@ -1265,10 +1275,18 @@ class GgadLossFn(torch.autograd.Function):
         xc = torch.empty(L, h, dtype=torch.float32, device=en.device)
         call("ggad_rows_scale_f32", ptr(en), ptr(J), ptr(c), L, h, 0, ptr(xc))            # c_j e_hat_j
         den = spmm(ls["RJ"], xc)                                                          # sum_j R_ij c_j e_hat_j
-        # + c_j S_j on rows J; normal and abnormal segments are each duplicate-free
+        # + c_j S_j on rows J
         if ls.get("distinct"):                                                            # no node in both lists (run.py's draws): one launch
             call("ggad_rows_scale_f32", ptr(s_j), ptr(J), ptr(c), L, h, 1, ptr(den))
-        else:
+        elif ls.get("rounds") is not None:                                                # a node twice inside a list: round by round
+            for pos, rows in ls["rounds"]:
+                k = int(pos.numel())
+                c_k = torch.empty(k, dtype=torch.float32, device=en.device)
+                s_k = torch.empty(k, h, dtype=torch.float32, device=en.device)
+                call("ggad_rows_scale_f32", ptr(c), ptr(pos), 0, k, 1, 0, ptr(c_k))      # c[pos], S[pos]: gathers (coefficient 1)
+                call("ggad_rows_scale_f32", ptr(s_j), ptr(pos), 0, k, h, 0, ptr(s_k))
+                call("ggad_rows_scale_f32", ptr(s_k), ptr(rows), ptr(c_k), k, h, 1, ptr(den))
+        else:                                                                             # normal and abnormal segments are each duplicate-free
             call("ggad_rows_scale_f32", ptr(s_j), ptr(J), ptr(c), nn_, h, 1, ptr(den))
             call("ggad_rows_scale_f32", s_j.data_ptr() + 4 * nn_ * h, J.data_ptr() + 4 * nn_, c.data_ptr() + 4 * nn_, L - nn_, h, 1,
                  ptr(den))

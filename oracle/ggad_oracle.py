@@ -20,7 +20,8 @@ reference pins torch==1.11.0 (`requirements.txt:7`).
 Precision.  The mini-batch functions (`aggregate_batch`, `encoder_forward`, `batch_loss`) take a ``dtype``: fp32 by default,
 the arithmetic the goldens pin; with float64 every intermediate is float64, the high-precision reference the fp32 kernels are
 checked against (tests/test_oracle_fp64.py pins that mode to the same captures, tests/step_reference.py uses it with
-`adam_f64`, torch.optim.Adam's update restated in float64).
+`adam_f64`, torch.optim.Adam's update restated in float64).  The full-graph functions (`_spmm`, `gcn_layer`, `full_head`, `full_forward`, both forms of
+`full_loss`) take it too: float64 operands, adjacency values, noise and autograd -- the reference of tests/test_fullgraph_branches_gpu.py.
 
 Two formulations are provided where they differ in cost:
   * sparse (CSR / per-edge) -- what the HIP kernels implement;
@@ -470,34 +471,42 @@ FULL_PARAM_ORDER = ["gcn1.bias", "gcn1.fc.weight", "gcn1.act.weight", "gcn2.bias
                     "gcn2.act.weight", "fc1.weight", "fc2.weight", "fc3.weight", "fc4.weight"]
 
 
-def _spmm(rowptr, col, val, x: torch.Tensor) -> torch.Tensor:
+def _spmm(rowptr, col, val, x: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     a = torch.sparse_csr_tensor(torch.from_numpy(rowptr.astype(np.int64)), torch.from_numpy(col.astype(np.int64)),
-                                torch.from_numpy(np.asarray(val, dtype=np.float32)),
+                                torch.from_numpy(np.asarray(val, dtype=_np_dtype(dtype))),
                                 size=(len(rowptr) - 1, x.shape[0]))
     return torch.sparse.mm(a, x)
 
 
-def full_forward(P: Dict[str, torch.Tensor], feat: torch.Tensor, adjn, abn_idx, normal_idx,
-                 noise: torch.Tensor, train_flag: bool):
-    """Model.forward (`model.py:133-191`) with the adjacency in CSR.
+def _relu(x: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ReLU; with ``mask`` (bool, True = the unit is on) the branch per entry is the caller's, not the sign of x -- a float64 run
+    then takes the branches a float32 run took (the two disagree legitimately within round-off of 0)."""
+    return F.relu(x) if mask is None else torch.where(mask, x, torch.zeros_like(x))
 
-    ``adjn`` = (rowptr, col, val) of normalize_adj(A)+I; ``noise`` = the N(mean,var) draw of
-    `model.py:143` (A x H), supplied by the caller so that RNG parity is the caller's business.
-    Returns (emb_after_overwrite, emb_combine, logits, emb_con, emb_abnormal)."""
+
+def gcn_layer(x: torch.Tensor, weight, bias, prelu_a, adjn, dtype=torch.float32, mask: Optional[torch.Tensor] = None,
+              want_pre: bool = False):
+    """GCN.forward (`model.py:26-35`): PReLU(A_hat (x W^T) + b) with the adjacency in CSR, every operand in ``dtype``.
+    ``mask`` (N x H bool, True = positive branch): see `_relu`.  ``want_pre``: also return the pre-activation."""
     rp, ci, va = adjn
+    t = x.to(_torch_dtype(dtype)).mm(weight.t())                          # `model.py:27`
+    z = _spmm(rp, ci, va, t, dtype)                                       # `:31`
+    if bias is not None:
+        z = z + bias                                                      # `:33`
+    out = F.prelu(z, prelu_a) if mask is None else torch.where(mask, z, prelu_a * z)      # `:35`
+    return (out, z) if want_pre else out
 
-    def gcn(x, pre):
-        t = x.mm(P[pre + ".fc.weight"].t())                               # `model.py:27`
-        out = _spmm(rp, ci, va, t) + P[pre + ".bias"]                     # `:31-33`
-        return F.prelu(out, P[pre + ".act.weight"])                       # `:35`
 
-    emb = gcn(gcn(feat, "gcn1"), "gcn2")
+def full_head(P: Dict[str, torch.Tensor], emb: torch.Tensor, adjn, abn_idx, normal_idx, noise: torch.Tensor,
+              dtype=torch.float32, masks: Optional[Dict[str, torch.Tensor]] = None, want_hidden: bool = False):
+    """The training forward from ``emb`` on (`model.py:140-182`).  ``masks``: optional ReLU branches ("con", "f1", "f2": see
+    `_relu`).  Index lists may overlap.  Returns (emb_after_overwrite, emb_combine, logits, emb_con, emb_abnormal), with
+    ``want_hidden`` also the dict of the three ReLU pre-activations ("con", "f1", "f2")."""
+    rp, ci, va = adjn
+    masks = masks or {}
     abn = torch.as_tensor(np.asarray(abn_idx), dtype=torch.long)
     nrm = torch.as_tensor(np.asarray(normal_idx), dtype=torch.long)
-    emb_abnormal = emb[abn] + noise                                       # `:141-144`
-    if not train_flag:
-        f3 = F.relu(F.relu(emb.mm(P["fc1.weight"].t())).mm(P["fc2.weight"].t())).mm(P["fc3.weight"].t())
-        return emb, None, f3[:, 0], None, emb_abnormal
+    emb_abnormal = emb[abn] + noise.to(_torch_dtype(dtype))               # `:141-144`
     # rows abn of the normalised adjacency times emb                      `:151-155`
     sub_rp = np.zeros(len(abn_idx) + 1, dtype=np.int64)
     cols, vals = [], []
@@ -507,13 +516,39 @@ def full_forward(P: Dict[str, torch.Tensor], feat: torch.Tensor, adjn, abn_idx, 
         vals.append(va[s:e])
         sub_rp[k + 1] = sub_rp[k] + (e - s)
     sub = torch.sparse_csr_tensor(torch.from_numpy(sub_rp), torch.from_numpy(np.concatenate(cols).astype(np.int64)),
-                                  torch.from_numpy(np.concatenate(vals).astype(np.float32)),
+                                  torch.from_numpy(np.concatenate(vals).astype(_np_dtype(dtype))),
                                   size=(len(abn_idx), emb.shape[0]))
-    emb_con = F.relu(torch.sparse.mm(sub, emb).mm(P["fc4.weight"].t()))   # `:155-156`
+    pre_con = torch.sparse.mm(sub, emb).mm(P["fc4.weight"].t())           # `:155`
+    emb_con = _relu(pre_con, masks.get("con"))                            # `:156`
     emb_combine = torch.cat((emb[nrm], emb_con), 0)                       # `:159`
-    f3 = F.relu(F.relu(emb_combine.mm(P["fc1.weight"].t())).mm(P["fc2.weight"].t())).mm(P["fc3.weight"].t())
+    pre_f1 = emb_combine.mm(P["fc1.weight"].t())
+    pre_f2 = _relu(pre_f1, masks.get("f1")).mm(P["fc2.weight"].t())
+    f3 = _relu(pre_f2, masks.get("f2")).mm(P["fc3.weight"].t())
     emb2 = emb.index_copy(0, abn, emb_con)                                # `:182` in-place overwrite
+    if want_hidden:
+        return emb2, emb_combine, f3[:, 0], emb_con, emb_abnormal, {"con": pre_con, "f1": pre_f1, "f2": pre_f2}
     return emb2, emb_combine, f3[:, 0], emb_con, emb_abnormal
+
+
+def full_forward(P: Dict[str, torch.Tensor], feat: torch.Tensor, adjn, abn_idx, normal_idx,
+                 noise: torch.Tensor, train_flag: bool, dtype=torch.float32):
+    """Model.forward (`model.py:133-191`) with the adjacency in CSR.
+
+    ``adjn`` = (rowptr, col, val) of normalize_adj(A)+I; ``noise`` = the N(mean,var) draw of
+    `model.py:143` (A x H), supplied by the caller so that RNG parity is the caller's business.
+    ``dtype``: float32 by default (the arithmetic the goldens pin); with float64 the features, the adjacency values, the noise and
+    every intermediate are float64 (P must hold float64 leaves) -- the high-precision reference of the full-graph kernels.
+    Returns (emb_after_overwrite, emb_combine, logits, emb_con, emb_abnormal)."""
+    def gcn(x, pre):
+        return gcn_layer(x, P[pre + ".fc.weight"], P[pre + ".bias"], P[pre + ".act.weight"], adjn, dtype)
+
+    emb = gcn(gcn(feat, "gcn1"), "gcn2")
+    if not train_flag:
+        abn = torch.as_tensor(np.asarray(abn_idx), dtype=torch.long)
+        emb_abnormal = emb[abn] + noise.to(_torch_dtype(dtype))           # `:141-144`
+        f3 = F.relu(F.relu(emb.mm(P["fc1.weight"].t())).mm(P["fc2.weight"].t())).mm(P["fc3.weight"].t())
+        return emb, None, f3[:, 0], None, emb_abnormal
+    return full_head(P, emb, adjn, abn_idx, normal_idx, noise, dtype)
 
 
 def ocgnn_forward(P: Dict[str, torch.Tensor], feat: torch.Tensor, adjn) -> torch.Tensor:
@@ -533,19 +568,23 @@ def ocgnn_loss(emb: torch.Tensor, r: float = 0.0, beta: float = 0.5):
     return r ** 2 + 1 / beta * torch.mean(torch.relu(score)), score
 
 
-def full_loss(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, margin_c: float = 0.7, by_column: bool = False):
+def full_loss(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, margin_c: float = 0.7, by_column: bool = False,
+              dtype=torch.float32):
     """Loss block of `run.py:165-210`, affinity as a per-edge SDDMM over raw_adj + I.
 
     affinity_j = sum_i cos(emb_i, emb_j) R_ij / sum_i R_ij   (column sums, `run.py:182-188`).
     loss_rec reduces over the OUTLIER axis (quirk 4, `run.py:207-208`).
     ``by_column``: the same sums associated per column, affinity_j = <e_hat_j, (R^T e_hat)_j> / colsum_j -- one sparse product
     instead of an (edges x H) intermediate (21 M x 300 floats at T-Finance size do not fit a host); pinned against the
-    per-edge form and the reference's vectors in tests/test_oracle_golden.py."""
+    per-edge form and the reference's vectors in tests/test_oracle_golden.py.
+    ``dtype``: float32 by default; float64 with float64 operands: labels, adjacency values and every sum are float64 (see
+    `full_forward`).  A column of ``raw`` may sum to 0 (r_inv inf -> 0, `run.py:185-186`) and the two index lists may overlap."""
     rp, ci, va = raw
     if by_column:
-        return _full_loss_by_column(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, margin_c)
+        return _full_loss_by_column(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, margin_c, dtype)
+    tdt = _torch_dtype(dtype)
     n_norm, n_out = len(normal_idx), emb_con.shape[0]
-    lbl = torch.cat((torch.zeros(n_norm), torch.ones(n_out)))
+    lbl = torch.cat((torch.zeros(n_norm, dtype=tdt), torch.ones(n_out, dtype=tdt)))
     l_bce = torch.mean(F.binary_cross_entropy_with_logits(logits, lbl, reduction="none",
                                                           pos_weight=torch.tensor([1])))
     inv = torch.pow(torch.norm(emb, dim=-1, keepdim=True), -1)
@@ -553,10 +592,10 @@ def full_loss(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, marg
     en = emb * inv
     rows = torch.from_numpy(np.repeat(np.arange(len(rp) - 1), np.diff(rp)).astype(np.int64))
     cols = torch.from_numpy(ci.astype(np.int64))
-    vals = torch.from_numpy(np.asarray(va, dtype=np.float32))
+    vals = torch.from_numpy(np.asarray(va, dtype=_np_dtype(dtype)))
     per_edge = (en[rows] * en[cols]).sum(1) * vals
-    colsum = torch.zeros(emb.shape[0]).index_add(0, cols, per_edge)
-    rsum = torch.zeros(emb.shape[0]).index_add(0, cols, vals)
+    colsum = torch.zeros(emb.shape[0], dtype=tdt).index_add(0, cols, per_edge)
+    rsum = torch.zeros(emb.shape[0], dtype=tdt).index_add(0, cols, vals)
     r_inv = torch.pow(rsum, -1)
     r_inv = torch.where(torch.isinf(r_inv), torch.zeros_like(r_inv), r_inv)
     aff = colsum * r_inv
@@ -568,20 +607,21 @@ def full_loss(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, marg
     return l_margin + l_bce + l_rec, l_margin, l_bce, l_rec, aff
 
 
-def _full_loss_by_column(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, margin_c):
+def _full_loss_by_column(emb, logits, emb_con, emb_abnormal, raw, abn_idx, normal_idx, margin_c, dtype=torch.float32):
     import scipy.sparse as sp
     rp, ci, va = raw
     n = emb.shape[0]
+    ndt, tdt = _np_dtype(dtype), _torch_dtype(dtype)
     n_norm, n_out = len(normal_idx), emb_con.shape[0]
-    lbl = torch.cat((torch.zeros(n_norm), torch.ones(n_out)))
+    lbl = torch.cat((torch.zeros(n_norm, dtype=tdt), torch.ones(n_out, dtype=tdt)))
     l_bce = torch.mean(F.binary_cross_entropy_with_logits(logits, lbl, reduction="none", pos_weight=torch.tensor([1])))
     inv = torch.pow(torch.norm(emb, dim=-1, keepdim=True), -1)
     inv = torch.where(torch.isinf(inv), torch.zeros_like(inv), inv)
     en = emb * inv
-    rt = sp.csr_matrix((np.asarray(va, dtype=np.float32), ci.astype(np.int64), rp.astype(np.int64)), shape=(n, n)).T.tocsr()
+    rt = sp.csr_matrix((np.asarray(va, dtype=ndt), ci.astype(np.int64), rp.astype(np.int64)), shape=(n, n)).T.tocsr()
     rt.sort_indices()
-    rten = _spmm(rt.indptr, rt.indices, rt.data, en)                      # (R^T e_hat)_j = sum_i R_ij e_hat_i
-    rsum = torch.from_numpy(np.asarray(rt.sum(1), dtype=np.float32).reshape(-1))
+    rten = _spmm(rt.indptr, rt.indices, rt.data, en, dtype)               # (R^T e_hat)_j = sum_i R_ij e_hat_i
+    rsum = torch.from_numpy(np.asarray(rt.sum(1), dtype=ndt).reshape(-1))
     r_inv = torch.pow(rsum, -1)
     r_inv = torch.where(torch.isinf(r_inv), torch.zeros_like(r_inv), r_inv)
     aff = (en * rten).sum(1) * r_inv
