@@ -217,6 +217,14 @@ SIGNATURES = {
     "ggad_mt_state_words": (c_int32, []),
     "ggad_mt_randn_scratch_elems": (c_int64, [_L]),
     "ggad_mt_randn_f32": (c_int32, [_P, _P, _L, _F, _F, _P, _P]),
+    "ggad_pcgnn_supported": (c_int32, [_I, _I]),
+    "ggad_pcgnn_max_feat_dim": (c_int32, []),
+    "ggad_pcgnn_scan_elems": (c_int64, [_L]),
+    "ggad_pcgnn_plan": (c_int32, [_P, _P, _L, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_pcgnn_plan_reset": (c_int32, [_P, _P, _P, _P, _I, _P, _P, _P]),
+    "ggad_pcgnn_hop_f32": (c_int32, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    "ggad_pcgnn_nb_fwd_f32": (c_int32, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
+    "ggad_pcgnn_nb_bwd_f32": (c_int32, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 
 

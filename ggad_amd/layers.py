@@ -14,6 +14,7 @@ from torch.nn import init
 
 from ._lib import call, ptr
 from .fullgraph import LinearFn
+from .graph import DeviceGraph
 from .graphsage import _features, _node_array
 
 
@@ -108,8 +109,15 @@ class InterAgg(nn.Module):
         self.weight = nn.Parameter(w.to(dev))
         self.label_clf = nn.Linear(self.feat_dim, 2).to(dev)                                       # :54
         self.weights_log, self.thresholds_log, self.relation_score_log = [], [self.thresholds], []
+        # relations kept as CSR in HBM: plan, both aggregations and the per-relation projection in HIP (pcgnn_device.py)
+        self.device_path = None
+        if isinstance(adj_lists, (list, tuple)) and len(adj_lists) == 3 and all(isinstance(a, DeviceGraph) for a in adj_lists):
+            from .pcgnn_device import PcgnnDevice
+            self.device_path = PcgnnDevice(self.features, self.feat_dim, self.embed_dim, adj_lists)
 
     def forward(self, nodes, labels, train_flag=True):
+        if self.device_path is not None:
+            return self.device_path.forward(self, nodes)
         nodes = [int(v) for v in _node_array(nodes)]
         r_feats, nb_feats = [], []
         for agg, adj in zip((self.intra_agg1, self.intra_agg2, self.intra_agg3), self.adj_lists):

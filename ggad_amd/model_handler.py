@@ -295,7 +295,9 @@ class ModelHandler(object):
         (1) `adj_lists` must be a list of THREE relation adjacencies -- config key `relations` (dicts of sets / (rowptr, col) pairs),
         or `data = ([r1, r2, r3], feat, labels)`; (2) `test_pcgnn` = `test_sage`'s protocol on `PCALayer.to_prob(nodes, labels,
         train_flag=False)[0][:, 1]` (the class-1 GNN score).  No vectors of the reference exist for this loop (it never ran): the
-        modules are pinned (tests/golden/minibatch_pcgnn.npz), the loop is checked for self-consistency (tests/test_dropin_gpu.py)."""
+        modules are pinned (tests/golden/minibatch_pcgnn.npz), the loop is checked for self-consistency (tests/test_dropin_gpu.py).
+        Config key `pcgnn_device` (default False): the relations become `DeviceGraph`s and `InterAgg` runs from the CSR in HBM
+        (pcgnn_device.py); without it nothing here changes."""
         from .fullgraph import FlatAdam
         from .layers import InterAgg, IntraAgg, PCALayer
         from . import synth
@@ -312,7 +314,13 @@ class ModelHandler(object):
         if relations is None or len(relations) != 3:
             raise ValueError("model 'PCGNN' needs three relation graphs: config key `relations` = [r1, r2, r3] "
                              "(dict of neighbour sets, or (rowptr, col)); the reference's branch never ran (its handler passes one)")
-        adjs = [synth.csr_to_adj_lists(r[0], r[1]) if isinstance(r, tuple) else r for r in relations]
+        if bool(getattr(args, "pcgnn_device", False)):
+            # relations stay CSR in HBM (pcgnn_device.py): no dict of sets is built; `InterAgg` checks every relation once
+            from .graph import DeviceGraph
+            adjs = [DeviceGraph(r[0], r[1], dev) if isinstance(r, tuple) else DeviceGraph.from_adj_lists(r, feat_data.shape[0], dev)
+                    for r in relations]
+        else:
+            adjs = [synth.csr_to_adj_lists(r[0], r[1]) if isinstance(r, tuple) else r for r in relations]
         idx_train = list(self.dataset["idx_train"])
         idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
                                                 self.dataset["idx_test"], self.dataset["y_test"])   # :260-261

@@ -847,6 +847,42 @@ int32_t ggad_mt_state_words(void);
 int64_t ggad_mt_randn_scratch_elems(int64_t n);
 int ggad_mt_randn_f32(uint32_t *state, float *out, int64_t n, float scale, float shift, uint32_t *scratch, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * PC-GNN comparison model from a CSR relation graph in device memory (pcgnn.hip; reference src/layers.py:62-153,179-244).
+ * rowptr / col: int32 CSR of n_nodes rows, every row non-empty, sorted and duplicate-free, every column in [0, n_nodes) (the
+ * caller checks once).  batch: n_batch int32 node ids on the device; a node listed twice is two rows.  cap: capacity in rows of
+ * every |U|-sized buffer, min(n_nodes, sum of the batch rows' degrees) -- known on the host; |U| itself stays on the device in
+ * n_unique[0].  No entry point uses floating-point atomics: equal inputs give equal bits.
+ *
+ * ggad_pcgnn_plan   U = union of the batch rows in ASCENDING id order: unique[p] (cap ints, -1 past |U|), pos[v] = p for v in U,
+ *                   row_count[p] = |N(unique[p])| (0 past |U|), cnt[v] = |{u in U : v in N(u)}|.  scan: ggad_pcgnn_scan_elems(n_nodes)
+ *                   ints, all zero on entry and all-zero again on return (the bitmap part).  pos (n_nodes ints, all -1) and cnt
+ *                   (n_nodes ints, all 0) are put back by ggad_pcgnn_plan_reset, which walks the same rows.
+ * ggad_pcgnn_hop_f32  a[r] = sum over the entries v of CSR row rows[r] of w * feat[v], t[r] = relu(a[r] W) for r < cap; W is
+ *                   (feat_dim, embed_dim) row-major.  cnt NULL: w = 1 / |row| (the mean), every one of the cap rows is read.
+ *                   cnt given: w = (1 / sqrt |row|) / sqrt cnt[v] in float32, and rows at or past n_rows[0] are written as zeros.
+ *                   ggad_pcgnn_supported(feat_dim, embed_dim) = 0: GGAD_E_UNSUPPORTED, nothing launched.
+ * ggad_pcgnn_nb_fwd_f32  nb[i] = sum over u in N(batch[i]) of t2[pos[u]] / |N(batch[i])|.
+ * ggad_pcgnn_nb_bwd_f32  dz2[p] = [t2[p] > 0] * sum over the i with unique[p] in N(batch[i]), ascending, of dnb[i] / |N(batch[i])|
+ *                   for p < |U|, zeros for the other rows up to cap: the transpose of nb_fwd through relu.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_pcgnn_supported(int32_t feat_dim, int32_t embed_dim);
+int32_t ggad_pcgnn_max_feat_dim(void);
+int64_t ggad_pcgnn_scan_elems(int64_t n_nodes);
+int ggad_pcgnn_plan(const int32_t *rowptr, const int32_t *col, int64_t n_nodes, const int32_t *batch, int32_t n_batch, int32_t cap,
+                    int32_t *scan, int32_t *pos, int32_t *cnt, int32_t *unique, int32_t *row_count, int32_t *n_unique,
+                    ggad_stream_t stream);
+int ggad_pcgnn_plan_reset(const int32_t *rowptr, const int32_t *col, int32_t *unique, const int32_t *n_unique, int32_t cap,
+                          int32_t *pos, int32_t *cnt, ggad_stream_t stream);
+int ggad_pcgnn_hop_f32(const float *feat, int32_t feat_dim, const int32_t *rowptr, const int32_t *col, const int32_t *rows,
+                       const int32_t *n_rows, int32_t cap, const int32_t *cnt, const float *w, int32_t embed_dim, float *a, float *t,
+                       ggad_stream_t stream);
+int ggad_pcgnn_nb_fwd_f32(const float *t2, int32_t embed_dim, const int32_t *rowptr, const int32_t *col, const int32_t *batch,
+                          int32_t n_batch, const int32_t *pos, float *nb, ggad_stream_t stream);
+int ggad_pcgnn_nb_bwd_f32(const float *dnb, const float *t2, int32_t embed_dim, const int32_t *rowptr, const int32_t *col,
+                          const int32_t *batch, int32_t n_batch, const int32_t *unique, const int32_t *n_unique, int32_t cap,
+                          float *dz2, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
