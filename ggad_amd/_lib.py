@@ -214,6 +214,8 @@ SIGNATURES = {
     "ggad_mt_getrandbits32": (c_uint32, [c_void_p]),
     "ggad_sched_batches": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32,
                                      c_void_p, c_void_p]),
+    "ggad_pyset_order_i32": (c_int32, [c_void_p, c_int64, c_void_p]),
+    "ggad_mt_sample_rows": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "ggad_mt_state_words": (c_int32, []),
     "ggad_mt_randn_scratch_elems": (c_int64, [_L]),
     "ggad_mt_randn_f32": (c_int32, [_P, _P, _L, _F, _F, _P, _P]),
@@ -225,6 +227,11 @@ SIGNATURES = {
     "ggad_pcgnn_hop_f32": (c_int32, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "ggad_pcgnn_nb_fwd_f32": (c_int32, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "ggad_pcgnn_nb_bwd_f32": (c_int32, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "ggad_sage_supported": (c_int32, [_I, _I, _I]),
+    "ggad_sage_bwd_parts": (c_int32, []),
+    "ggad_sage_bwd_workspace_elems": (c_int64, [_I, _I]),
+    "ggad_sage_fwd_f32": (c_int32, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_sage_bwd_f32": (c_int32, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 

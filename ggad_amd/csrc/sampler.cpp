@@ -11,6 +11,7 @@
 //   * _randbelow(n): k = n.bit_length(); draw getrandbits(k) until < n;
 //   * shuffle: for i = len-1 .. 1: j = _randbelow(i+1); swap(x[i], x[j])  (CPython Lib/random.py).
 // Pinned by tests/golden/sampler_shuffle.npz (captured from CPython 3.10 itself).
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -607,6 +608,137 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
     g->index = idx;
   }
   *in_epoch_io = ie;
+  return GGAD_OK;
+}
+
+}  // extern "C"
+
+// ---- random.sample over a python set of ints, without python ---------------------------------------------------------------
+// The set path of the GraphSAGE baseline draws `random.sample(tuple(adj[v]), k)` per batch row (graphsage.py, MeanAggregator):
+// the result depends on the ITERATION ORDER of the set adj[v], which is the order of its hash table.  For distinct non-negative
+// int32 keys inserted in ascending order (how `synth.csr_to_adj_lists` and `Encoder.forward` fill the sets; an int hashes to
+// itself) that order follows from the table rules, restated here from their description and the interpreter's observable behaviour:
+//   * the table starts with 8 slots; after every insert, if fill * 5 >= mask * 3, it is rebuilt into the smallest power of two
+//     greater than 4 * used (2 * used once used > 50000; the search starts from 8), re-inserting the entries in old-table order;
+//   * insert: i = h & mask, perturb = h; scan slot i -- and the next 9 slots only when i + 9 <= mask -- for an empty one; otherwise
+//     perturb >>= 5, i = (i * 5 + 1 + perturb) & mask, and again;
+//   * iteration is table order.
+// random.sample(pop, k), n = len(pop): n <= setsize -> a pool copy, j = randbelow(n - i), res[i] = pool[j], pool[j] = pool[n - i - 1];
+// else j = randbelow(n) until it has not been selected yet, res[i] = pop[j].  `setsize` comes from the caller (python evaluates
+// 21 + 4 ** ceil(log(3k, 4)) itself: no floating-point log is restated here).  Pinned against the running interpreter by
+// tests/test_sage_device_cpu.py.
+namespace {
+constexpr int SET_LINEAR_PROBES = 9;
+
+inline void set_insert_clean(int32_t *tab, uint64_t mask, int32_t key) {
+  uint64_t perturb = (uint64_t)key, i = (uint64_t)key & mask;
+  for (;;) {
+    const uint64_t last = (i + SET_LINEAR_PROBES <= mask) ? i + SET_LINEAR_PROBES : i;
+    for (uint64_t s = i; s <= last; ++s)
+      if (tab[s] < 0) { tab[s] = key; return; }
+    perturb >>= 5;
+    i = (i * 5 + 1 + perturb) & mask;
+  }
+}
+
+// iteration order of set(keys[0], keys[1], ...) for strictly ascending non-negative keys; out holds n ints
+void pyset_order(const int32_t *keys, int64_t n, int32_t *out, std::vector<int32_t> &tab, std::vector<int32_t> &old) {
+  uint64_t size = 8;
+  tab.assign(size, -1);
+  int64_t used = 0;
+  for (int64_t t = 0; t < n; ++t) {
+    set_insert_clean(tab.data(), size - 1, keys[t]);
+    ++used;                                                        // no deletions: fill == used
+    if ((uint64_t)used * 5 < (size - 1) * 3) continue;
+    const uint64_t minused = used > 50000 ? (uint64_t)used * 2 : (uint64_t)used * 4;
+    uint64_t newsize = 8;
+    while (newsize <= minused) newsize <<= 1;
+    old.swap(tab);
+    tab.assign(newsize, -1);
+    for (uint64_t s = 0; s < size; ++s)
+      if (old[s] >= 0) set_insert_clean(tab.data(), newsize - 1, old[s]);
+    size = newsize;
+  }
+  int64_t c = 0;
+  for (uint64_t s = 0; s < size; ++s)
+    if (tab[s] >= 0) out[c++] = tab[s];
+}
+
+inline uint32_t mt_randbelow(ggad_mt19937 *g, uint32_t n) {        // _randbelow(n), 1 <= n < 2^31
+  const int sh = __builtin_clz(n);                                 // 32 - n.bit_length()
+  uint32_t r = mt_next(g) >> sh;
+  while (r >= n) r = mt_next(g) >> sh;
+  return r;
+}
+
+inline bool strictly_ascending_nonneg(const int32_t *k, int64_t n) {
+  if (n > 0 && k[0] < 0) return false;
+  for (int64_t t = 1; t < n; ++t)
+    if (k[t] <= k[t - 1]) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int ggad_pyset_order_i32(const int32_t *keys, int64_t n, int32_t *out) {
+  if (n < 0 || n > 0x3fffffffLL || (n > 0 && (!keys || !out))) return GGAD_E_INVALID;
+  if (!strictly_ascending_nonneg(keys, n)) return GGAD_E_INVALID;
+  std::vector<int32_t> tab, old;
+  pyset_order(keys, n, out, tab, old);
+  return GGAD_OK;
+}
+
+int ggad_mt_sample_rows(ggad_mt19937 *g, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
+                        const int64_t *nodes, int64_t n_rows, int32_t k, int32_t setsize, int32_t *nbr_out, int32_t *cnt_out) {
+  if (!g || !rowptr_host || !nodes || !nbr_out || !cnt_out) return GGAD_E_INVALID;
+  if (n_nodes < 1 || n_nodes > 0x7fffffffLL || n_rows < 0 || k < 1 || k > 4096 || setsize < 21) return GGAD_E_INVALID;
+  // everything is checked before the first draw: a refused call leaves the generator where it was
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const int64_t v = nodes[r];
+    if (v < 0 || v >= n_nodes) return GGAD_E_INVALID;
+    const int64_t e0 = rowptr_host[v], e1 = rowptr_host[v + 1];
+    if (e0 < 0 || e1 < e0) return GGAD_E_INVALID;
+    if (e1 > e0 && (!col_host || !strictly_ascending_nonneg(col_host + e0, e1 - e0))) return GGAD_E_INVALID;
+  }
+  std::vector<int32_t> tab, old, order, pool;
+  std::vector<uint32_t> picked((size_t)k);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const int64_t v = nodes[r];
+    const int64_t e0 = rowptr_host[v];
+    const int64_t n = rowptr_host[v + 1] - e0;
+    int32_t *dst = nbr_out + r * (int64_t)k;
+    if (n < k) {                                                   // the whole neighbourhood, no draw (graphsage.py: `else tn`)
+      for (int64_t t = 0; t < n; ++t) dst[t] = col_host[e0 + t];
+      for (int64_t t = n; t < k; ++t) dst[t] = -1;
+      cnt_out[r] = (int32_t)n;
+      continue;
+    }
+    if ((int64_t)order.size() < n) order.resize((size_t)n);
+    pyset_order(col_host + e0, n, order.data(), tab, old);
+    if (n <= setsize) {
+      pool.assign(order.begin(), order.begin() + n);
+      for (int32_t i = 0; i < k; ++i) {
+        const uint32_t j = mt_randbelow(g, (uint32_t)(n - i));
+        dst[i] = pool[j];
+        pool[j] = pool[(size_t)(n - i - 1)];
+      }
+    } else {
+      for (int32_t i = 0; i < k; ++i) {
+        uint32_t j;
+        bool seen;
+        do {
+          j = mt_randbelow(g, (uint32_t)n);
+          seen = false;
+          for (int32_t q = 0; q < i; ++q) seen |= picked[(size_t)q] == j;
+        } while (seen);
+        picked[(size_t)i] = j;
+        dst[i] = order[j];
+      }
+    }
+    std::sort(dst, dst + k);                                       // the set path hands `sorted(s)` to the segment mean
+    cnt_out[r] = k;
+  }
   return GGAD_OK;
 }
 

@@ -324,8 +324,12 @@ class MeanAggregator(nn.Module):
 
 
 class Encoder(nn.Module):
+    """``sage_device``: a `sage_device.SageDevice` (or ``True``: one is built on python's global `random` stream) moves sampling
+    and arithmetic to the device path; ``adj_lists`` must then be a `DeviceGraph`.  Draws are bit-exact with the set path's for
+    CSR input and for dicts whose sets were filled in ascending id order (see `sage_device`); without it nothing changes."""
+
     def __init__(self, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample=10, base_model=None,
-                 gcn=False, cuda=False, feature_transform=False):
+                 gcn=False, cuda=False, feature_transform=False, sage_device=None):
         super().__init__()
         self.features = _features(features)
         self.feat_dim = feature_dim
@@ -342,8 +346,26 @@ class Encoder(nn.Module):
         w = torch.empty(embed_dim, self.feat_dim if self.gcn else 2 * self.feat_dim)
         init.xavier_uniform_(w)
         self.weight = nn.Parameter(w.to(self.features.weight.device))
+        self.device_path = None
+        if sage_device is not None and sage_device is not False:
+            from .sage_device import SageDevice
+            if sage_device is True:
+                sage_device = SageDevice(adj_lists, self.features, feature_dim, embed_dim, num_sample, rng=None, gcn=gcn)
+            if not isinstance(sage_device, SageDevice) or sage_device.graph is not adj_lists or gcn or \
+                    (sage_device.F, sage_device.D, sage_device.k) != (feature_dim, embed_dim, num_sample):
+                raise ValueError("sage_device: expected a SageDevice built on this encoder's DeviceGraph, widths and num_sample "
+                                 "(gcn=False)")
+            self.device_path = sage_device
 
     def forward(self, nodes):
+        if self.device_path is not None:
+            # embeddings only; the gradient path of the device route is GraphSage.forward / GraphSage.loss
+            if torch.is_grad_enabled() and self.weight.requires_grad:
+                raise RuntimeError("Encoder.forward on the device path returns embeddings without a gradient: call it under "
+                                   "torch.no_grad(), or differentiate GraphSage.forward / GraphSage.loss")
+            dp = self.device_path
+            out = dp.forward(dp.batch(nodes), self.weight.detach(), torch.zeros(2, self.embed_dim, device=self.weight.device))
+            return out["emb"].t()
         nodes_np = _node_array(nodes)
         adj = self.adj_lists
         # the reference hands the adjacency's own set objects to the aggregator (`:137`): `random.sample` walks a set in ITS
@@ -364,17 +386,30 @@ class GraphSage(nn.Module):
     def __init__(self, num_classes, enc):
         super().__init__()
         self.enc = enc
+        if getattr(enc, "device_path", None) is not None and num_classes != 2:
+            raise ValueError("the GraphSAGE device path takes 2 classes")
         self.xent = nn.CrossEntropyLoss()
         w = torch.empty(num_classes, enc.embed_dim)
         init.xavier_uniform_(w)
         self.weight = nn.Parameter(w.to(enc.weight.device))
 
     def forward(self, nodes):
+        dp = getattr(self.enc, "device_path", None)
+        if dp is not None:
+            from .sage_device import SageScoresFn
+            return SageScoresFn.apply(self.enc.weight, self.weight, dp, dp.batch(nodes))
         embeds = self.enc(nodes)                                            # (D, B)
         return LinearFn.apply(embeds.t().contiguous(), self.weight, False)  # scores.t() = (weight . embeds)^T   (`:32-35`)
 
     def to_prob(self, nodes):
+        """On the device path `nodes` may be a whole sweep: one sampler call, one forward launch (the `random` stream depends on
+        the order of the rows only, so the result equals the chunked one)."""
         return torch.sigmoid(self.forward(nodes))
 
     def loss(self, nodes, labels):
+        dp = getattr(self.enc, "device_path", None)
+        if dp is not None:
+            from .sage_device import SageStepFn
+            lab = labels.squeeze() if isinstance(labels, torch.Tensor) else np.asarray(labels).squeeze()
+            return SageStepFn.apply(self.enc.weight, self.weight, dp, dp.batch(nodes, labels=lab))
         return self.xent(self.forward(nodes), torch.as_tensor(labels, device=self.weight.device).long().squeeze())

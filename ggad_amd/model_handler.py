@@ -235,6 +235,8 @@ class ModelHandler(object):
             adj_lists = DeviceGraph(adj_lists[0], adj_lists[1], dev)
         features = FeatureTable(torch.FloatTensor(np.asarray(feat_data, dtype=np.float32)))
         agg_sage = MeanAggregator(features, cuda=True)
+        if bool(getattr(args, "sage_device", False)):
+            return self._train_sage_device(dev, adj_lists, features, agg_sage)
         enc_sage = Encoder(features, f, args.emb_size, adj_lists, agg_sage, gcn=False, cuda=True)
         enc_sage.num_samples = 5                                       # :291 (a new attribute: the encoder keeps num_sample = 10)
         gnn_model = GraphSage(2, enc_sage).to(dev)
@@ -286,6 +288,74 @@ class ModelHandler(object):
             print("Model path: {}".format(path_saver))
             gnn_model.load_state_dict(torch.load(path_saver))
         return self._test_graphsage(idx_test, y_test, gnn_model, args.batch_size, args.thres)
+
+    def _train_sage_device(self, dev, adj_lists, features, agg_sage):
+        """`_train_sage` with config key `sage_device: true` (sage_device.py): the adjacency is a `DeviceGraph` (a (rowptr, col)
+        pair as it is, a dict of sets through `DeviceGraph.from_adj_lists`), ONE native generator continues python's `random`
+        stream for the epoch shuffle, the pool shuffle and the neighbour samples, and a step is one sampler call, one upload and the
+        fused kernels of csrc/sage.hip; a validation sweep is one sampler call and one forward launch.  Same loop, same prints,
+        same checkpoints.  The draws equal the set path's bit for bit for CSR input and for dicts whose sets were filled in
+        ascending id order; the stream is handed back to `random` before this returns."""
+        from .fullgraph import FlatAdam
+        from .sage_device import SageDevice
+        args = self.args
+        n, f = self.dataset["feat_data"].shape
+        if not isinstance(adj_lists, DeviceGraph):
+            adj_lists = DeviceGraph.from_adj_lists(adj_lists, n, dev)
+        idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
+                                                self.dataset["idx_test"], self.dataset["y_test"])   # :260-261
+        rng = PyCompatRandom.from_python_state(random.getstate())
+        try:
+            sage = SageDevice(adj_lists, features, f, args.emb_size, 10, rng=rng)      # the encoder's default num_sample (:291 sets
+            enc_sage = Encoder(features, f, args.emb_size, adj_lists, agg_sage, gcn=False, cuda=True, sage_device=sage)   # another name)
+            enc_sage.num_samples = 5
+            gnn_model = GraphSage(2, enc_sage).to(dev)
+            features.to(dev)
+            optimizer = FlatAdam([p for p in gnn_model.parameters() if p.requires_grad], lr=args.lr, weight_decay=args.weight_decay)
+            self.model = gnn_model
+            num_batches = int(getattr(args, "num_batches", 150))           # :317
+            n_pseudo = int(getattr(args, "n_pseudo", 50))
+            idx_train = np.array(list(self.dataset["idx_train"]), dtype=np.int64)
+            idx_anomaly = np.array(list(self.dataset["idx_anomaly"]), dtype=np.int64)
+            labels = self.dataset["labels"]
+            timestamp = datetime.datetime.fromtimestamp(int(time.time())).strftime("%Y-%m-%d %H-%M-%S")
+            dir_saver = args.save_dir + timestamp
+            path_saver = os.path.join(dir_saver, "{}_{}.pkl".format(args.data_name, args.model))
+            f1_mac_best, auc_best, ep_best = 0, 0, -1
+            self.sage_losses = []
+            for epoch in range(args.num_epochs):
+                rng.shuffle(idx_train)                                     # :314
+                loss_sum, epoch_time = 0.0, 0.0
+                for batch in range(num_batches):
+                    t0 = time.time()
+                    i0, i1 = batch * args.batch_size, min((batch + 1) * args.batch_size, len(idx_train))
+                    rng.shuffle(idx_anomaly)                               # :341
+                    batch_nodes = np.concatenate([idx_train[i0:i1], idx_anomaly[:n_pseudo]])     # :342,347
+                    optimizer.zero_grad()
+                    loss = gnn_model.loss(batch_nodes, labels[batch_nodes])
+                    loss.backward()
+                    optimizer.step()
+                    epoch_time += time.time() - t0
+                    self.sage_losses.append(float(loss.item()))
+                    loss_sum += self.sage_losses[-1]
+                print(f"Epoch: {epoch}, loss: {loss_sum / num_batches}, time: {epoch_time}s")
+                if epoch % args.valid_epochs == 0:
+                    print("Valid at epoch {}".format(epoch))
+                    f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val = self._test_graphsage(idx_valid, y_valid, gnn_model,
+                                                                                              args.batch_size, args.thres)
+                    if auc_val > auc_best:
+                        f1_mac_best, auc_best, ep_best = f1_mac_val, auc_val, epoch
+                        if not os.path.exists(dir_saver):
+                            os.makedirs(dir_saver)
+                        print("  Saving model ...")
+                        torch.save(gnn_model.state_dict(), path_saver)
+            if ep_best >= 0:
+                print("Restore model from epoch {}".format(ep_best))
+                print("Model path: {}".format(path_saver))
+                gnn_model.load_state_dict(torch.load(path_saver))
+            return self._test_graphsage(idx_test, y_test, gnn_model, args.batch_size, args.thres)
+        finally:
+            random.setstate(rng.to_python_state())       # hand the stream back to python `random`
 
     def _train_pcgnn(self):
         """`model: 'PCGNN'`: IntraAgg x 3 -> InterAgg -> PCALayer(2, inter1, alpha) as `src/model_handler.py:269-277,287-288` builds
@@ -411,11 +481,16 @@ class ModelHandler(object):
         test_cases = list(test_cases)
         probs = []
         with torch.no_grad():
-            for it in range(int(len(test_cases) / batch_size) + 1):
-                chunk = test_cases[it * batch_size:min((it + 1) * batch_size, len(test_cases))]
-                if not chunk:
-                    continue
-                probs.append(model.to_prob(chunk)[:, 1])
+            if getattr(model.enc, "device_path", None) is not None:
+                # the device path scores a sweep in one sampler call and one forward launch: the stream, and so every sample, depends on
+                # the order of the rows only
+                probs.append(model.to_prob(test_cases)[:, 1])
+            else:
+                for it in range(int(len(test_cases) / batch_size) + 1):
+                    chunk = test_cases[it * batch_size:min((it + 1) * batch_size, len(test_cases))]
+                    if not chunk:
+                        continue
+                    probs.append(model.to_prob(chunk)[:, 1])
         probs = torch.cat(probs)
         r = binary_report(probs, torch.as_tensor(np.asarray(labels), device=probs.device), thres)
         print(f"   GNN F1-binary-1: {r['f1_1']:.4f}\tF1-binary-0: {r['f1_0']:.4f}" +

@@ -60,3 +60,52 @@ class PyCompatRandom:
 
     def getrandbits32(self) -> int:
         return int(self._lib.ggad_mt_getrandbits32(self._h))
+
+    # ---- neighbour sampling of the GraphSAGE baseline (`random.sample` over python sets, csrc/sampler.cpp)
+    def pyset_order(self, keys) -> np.ndarray:
+        """Iteration order of ``set(int(c) for c in keys)`` for strictly ascending, non-negative int32 keys."""
+        return pyset_order(keys)
+
+    def sample_rows(self, rowptr: np.ndarray, col: np.ndarray, nodes, num_sample: int):
+        """``sorted(random.sample(tuple(adj[v]), num_sample))`` for every v of ``nodes`` in list order, where ``adj[v]`` is the set
+        filled with CSR row v in ascending order; a row shorter than ``num_sample`` is taken whole and draws nothing.  Returns
+        ``(nbr, cnt)``: (len(nodes), num_sample) int32 padded with -1, and the row lengths.  One call may cover any number of
+        batches: the stream depends only on the order of the rows."""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        nodes = np.ascontiguousarray(np.asarray(nodes, dtype=np.int64).reshape(-1))
+        k = int(num_sample)
+        if k < 1:
+            raise ValueError("num_sample must be a positive integer")
+        n_nodes = len(rowptr) - 1
+        if n_nodes < 1 or int(rowptr[-1]) != len(col):
+            raise ValueError("rowptr is not a CSR row pointer of col")
+        if len(nodes) and (nodes.min() < 0 or nodes.max() >= n_nodes):
+            raise ValueError(f"node ids must lie in [0, {n_nodes})")
+        nbr = np.empty((len(nodes), k), dtype=np.int32)
+        cnt = np.empty(len(nodes), dtype=np.int32)
+        rc = self._lib.ggad_mt_sample_rows(self._h, rowptr.ctypes.data, col.ctypes.data, n_nodes, nodes.ctypes.data, len(nodes), k,
+                                           sample_setsize(k), nbr.ctypes.data, cnt.ctypes.data)
+        if rc != 0:
+            raise ValueError("ggad_mt_sample_rows: a CSR row is not strictly ascending and non-negative (the sets the set path "
+                             "samples from are filled in ascending order)")
+        return nbr, cnt
+
+
+def sample_setsize(k: int) -> int:
+    """The population size up to which `random.sample` copies the population into a pool (CPython Lib/random.py), evaluated with
+    the interpreter's own expression so that no floating-point logarithm is restated in C."""
+    from math import ceil, log
+    setsize = 21
+    if k > 5:
+        setsize += 4 ** ceil(log(k * 3, 4))
+    return setsize
+
+
+def pyset_order(keys) -> np.ndarray:
+    keys = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1)
+    out = np.empty(len(keys), dtype=np.int32)
+    rc = _lib.load().ggad_pyset_order_i32(keys.ctypes.data, len(keys), out.ctypes.data)
+    if rc != 0:
+        raise ValueError("ggad_pyset_order_i32 wants strictly ascending, non-negative int32 keys")
+    return out

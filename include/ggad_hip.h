@@ -832,6 +832,17 @@ int ggad_apply_swaps_i64(int64_t *data_host, int64_t n, const int32_t *targets_h
 int ggad_sched_batches(ggad_mt19937 *, int64_t *train, int64_t n_train, int64_t *pool, int64_t n_pool, int32_t batch_size,
                        int32_t n_pseudo, int32_t batches_per_epoch, int32_t *in_epoch_io, int32_t count, int64_t *out_nodes,
                        int32_t *out_len);
+/* Iteration order of the python set built by adding keys[0..n) one by one: strictly ascending, non-negative int32 keys (an int
+ * hashes to itself); out holds n ints.  Restated from the set-table rules (sampler.cpp); anything else -> GGAD_E_INVALID. */
+int ggad_pyset_order_i32(const int32_t *keys_host, int64_t n, int32_t *out_host);
+/* Neighbour sampling of the GraphSAGE baseline (`random.sample(tuple(adj[v]), k)` per row, reference src/graphsage.py:75-78) over a
+ * host CSR whose rows are strictly ascending -- the sets the set path samples from are filled in that order.  For each of the n_rows
+ * ids of `nodes`, in list order: a row of degree >= k draws a sample, a shorter row is taken whole and consumes no generator output;
+ * a node listed twice is sampled twice.  nbr_out: n_rows x k int32, each row sorted ascending and padded with -1; cnt_out: the row
+ * lengths.  setsize: 21, plus 4 ** ceil(log(3k, 4)) when k > 5, evaluated by the caller.  The stream depends only on the order of
+ * the rows, not on how they are cut into calls.  Ids outside [0, n_nodes), an unsorted row, k < 1: GGAD_E_INVALID before any draw. */
+int ggad_mt_sample_rows(ggad_mt19937 *, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
+                        const int64_t *nodes_host, int64_t n_rows, int32_t k, int32_t setsize, int32_t *nbr_out, int32_t *cnt_out);
 
 /* ------------------------------------------------------------------------------------
  * torch.randn's CPU stream continued on the DEVICE (rng.hip).  `state`: ggad_mt_state_words() uint32 in device memory -- the 624
@@ -882,6 +893,31 @@ int ggad_pcgnn_nb_fwd_f32(const float *t2, int32_t embed_dim, const int32_t *row
 int ggad_pcgnn_nb_bwd_f32(const float *dnb, const float *t2, int32_t embed_dim, const int32_t *rowptr, const int32_t *col,
                           const int32_t *batch, int32_t n_batch, const int32_t *unique, const int32_t *n_unique, int32_t cap,
                           float *dz2, ggad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * GraphSAGE comparison model (reference src/graphsage.py:19-154), one optimiser step on a sampled batch (sage.hip).
+ * feat: n_nodes x feat_dim table; nodes: n_batch int32 ids; nbr: n_batch x k int32 sample table (ggad_mt_sample_rows; entries at
+ * or past cnt[i] are never read); w_enc: embed_dim x 2 feat_dim; w_cls: 2 x embed_dim; labels: n_batch int32 in {0, 1} or NULL.
+ *
+ * ggad_sage_fwd_f32  combined[i] = [feat[nodes[i]] || sum_j feat[nbr[i][j]] * (1 / cnt[i])] (table order, one fused multiply-add per
+ *                    term; cnt[i] = 0 gives 0 * (1 / 0) = NaN in the second half, as ggad_seg_mean does), emb = relu(combined
+ *                    w_enc^T), scores = emb w_cls^T.  With labels: loss (1 + n_batch floats) gets the mean cross entropy over the
+ *                    batch in loss[0] (lane l of one wave adds rows l, l + 64, ...; the lanes are added in butterfly order) and the
+ *                    rows' own cross entropies behind it, dscores = (softmax - onehot) / n_batch; without: both may be NULL.
+ * ggad_sage_bwd_f32  d_cls = dscores^T emb, dZ = (dscores w_cls) * [emb > 0], d_enc = dZ^T combined.  Partial sums over
+ *                    ggad_sage_bwd_parts() row ranges go to `ws` (ggad_sage_bwd_workspace_elems floats) and are added in range order.
+ * No floating-point atomics: equal inputs give equal bits.  ggad_sage_supported(feat_dim, embed_dim, n_classes): 1 <= feat_dim <= 64,
+ * 1 <= embed_dim <= ggad_max_embed_dim(), n_classes == 2; anything else is GGAD_E_UNSUPPORTED and nothing is launched.  The caller
+ * range-checks the node ids.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_sage_supported(int32_t feat_dim, int32_t embed_dim, int32_t n_classes);
+int32_t ggad_sage_bwd_parts(void);
+int64_t ggad_sage_bwd_workspace_elems(int32_t feat_dim, int32_t embed_dim);
+int ggad_sage_fwd_f32(const float *feat, int32_t feat_dim, const int32_t *nodes, const int32_t *nbr, const int32_t *cnt,
+                      int32_t n_batch, int32_t k, const float *w_enc, int32_t embed_dim, const float *w_cls, const int32_t *labels,
+                      float *combined, float *emb, float *scores, float *loss, float *dscores, ggad_stream_t stream);
+int ggad_sage_bwd_f32(const float *combined, const float *emb, const float *dscores, const float *w_cls, int32_t n_batch,
+                      int32_t feat_dim, int32_t embed_dim, float *ws, float *d_enc, float *d_cls, ggad_stream_t stream);
 
 #ifdef __cplusplus
 }
