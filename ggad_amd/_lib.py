@@ -232,6 +232,12 @@ SIGNATURES = {
     "ggad_sage_bwd_workspace_elems": (c_int64, [_I, _I]),
     "ggad_sage_fwd_f32": (c_int32, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ggad_sage_bwd_f32": (c_int32, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "ggad_aegis_mb_max_rows": (c_int32, []),
+    "ggad_aegis_mb_supported": (c_int32, [_I, _I, _I]),
+    "ggad_aegis_mb_scratch_elems": (c_int64, [_L]),
+    "ggad_aegis_mb_fwd_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_aegis_mb_bwd_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_aegis_mb_fold_f32": (c_int32, [_P, _I, _F, _P, _P, _P, _P]),
 }
 
 

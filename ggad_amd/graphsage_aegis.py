@@ -21,6 +21,9 @@ oracle's restatement of the same stack (tests/test_baselines_gpu.py), not with t
 The aggregation is the plan + `ggad_mb_gather1` kernels of the GGAD path (`BatchChunk`, x1), once per table; every projection and
 MLP layer runs on the exact-f32 MFMA GEMM with autograd (`LinearFn`); batch norm, the sigmoids and the two BCE means are torch
 elementwise kernels on a (2B, 64) matrix.  No CPU path.
+
+Opt-in device path (`GCNEncoder(..., aegis_device=True)`, `ggad_amd/aegis_device.py`): everything after the aggregation -- both
+projections, both batch-norm calls, heads, BCE means, the backward into the seven tensors -- is two launches of `csrc/aegis_mb.hip`.
 """
 from __future__ import annotations
 
@@ -136,7 +139,7 @@ class GCNAggregator(nn.Module):
 
 class GCNEncoder(nn.Module):
     def __init__(self, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample=10, base_model=None, gcn=False,
-                 cuda=False, feature_transform=False):
+                 cuda=False, feature_transform=False, aegis_device=None):
         super().__init__()
         self.features = _features(features)
         self.feat_dim = feature_dim
@@ -162,9 +165,18 @@ class GCNEncoder(nn.Module):
         self.discriminator2 = MLP(in_dim, hid_dim, 1, encoder_layers, 0.0, torch.sigmoid).to(dev)
         if embed_dim != in_dim:
             raise ValueError("the reference's discriminator reads 64 channels: emb_size must be 64 (`src/graphsage_aegis.py:270`)")
+        # aegis_device: None / False = the path above; True or an `AegisDevice` = the fused step kernels (`csrc/aegis_mb.hip`)
+        self.aegis_device = None
+        if aegis_device is not None and aegis_device is not False:
+            from .aegis_device import AegisDevice
+            if aegis_device is not True and not isinstance(aegis_device, AegisDevice):
+                raise ValueError("aegis_device must be True or an AegisDevice")
+            self.aegis_device = (AegisDevice() if aegis_device is True else aegis_device).bind(self)
 
     def discriminate(self, x_feat, x_noise):
         """From the two aggregates of a batch: (logits_all, logits_gen, label) of `:307-318`."""
+        if self.aegis_device is not None:
+            return self.aegis_device.discriminate(x_feat, x_noise)
         combined = LinearFn.apply(x_feat, self.weight, True)                     # relu(W agg^T)^T: (B, embed)
         combined_noise = LinearFn.apply(x_noise, self.weight, True)
         emb_all = torch.cat([combined, combined_noise], 0)
@@ -201,8 +213,15 @@ class GCN(nn.Module):
         return loss_dis, loss_g
 
     def loss(self, nodes):
+        if self.enc.aegis_device is not None:
+            x_feat, x_noise, _ = self.enc.aggregator.aggregate([nodes], self.enc.adj_lists)
+            return self.loss_rows(x_feat, x_noise)
         return self.losses(*self.forward(nodes))
 
     def loss_rows(self, x_feat, x_noise):
-        """The same pair from already aggregated rows (a slice of a multi-batch plan): what the chunked trainer calls."""
+        """The same pair from already aggregated rows (a slice of a multi-batch plan): what the chunked trainer calls.  On the device
+        path the pair comes from `AegisDevice.step`, which has already left the gradients in `.grad` (there is no graph to
+        back-propagate)."""
+        if self.enc.aegis_device is not None:
+            return self.enc.aegis_device.step(x_feat, x_noise)
         return self.losses(*self.enc.discriminate(x_feat, x_noise))

@@ -51,7 +51,8 @@ class ModelHandler(_Base):
         m = self.model_module
         features = FeatureTable(torch.FloatTensor(np.asarray(feat_data, dtype=np.float32)))
         agg_gcn = m.GCNAggregator(features, feat_data, cuda=True)                                    # :110 (draws the noise table)
-        enc_gcn = m.GCNEncoder(features, f, args.emb_size, graph, agg_gcn, gcn=True, cuda=True)     # :111-112
+        dev_path = True if bool(getattr(args, "aegis_device", False)) else None
+        enc_gcn = m.GCNEncoder(features, f, args.emb_size, graph, agg_gcn, gcn=True, cuda=True, aegis_device=dev_path)     # :111-112
         return graph, features, m.GCN(2, enc_gcn)
 
     def train(self):
@@ -74,6 +75,8 @@ class ModelHandler(_Base):
         rng = PyCompatRandom.from_python_state(random.getstate())
         self.epoch_losses, self.epoch_times, self.valid_history = [], [], []
         losses = torch.empty(num_batches, 2, dtype=torch.float32, device=dev)
+        if enc.aegis_device is not None:
+            return self._train_device(gnn_model, graph, optimizer, base, rng, losses, num_batches, bs)
         for epoch in range(args.num_epochs):
             sampled = base.copy()                                                # :132 a fresh concatenation every epoch
             rng.shuffle(sampled)                                                 # :133
@@ -86,6 +89,55 @@ class ModelHandler(_Base):
                 (loss_g + loss_gen).backward()                                   # :156-157: two backward passes into the same .grad
                 optimizer.step()
                 losses[b, 0], losses[b, 1] = loss_g.detach(), loss_gen.detach()
+            torch.cuda.synchronize()
+            epoch_time = time.time() - t0
+            l = losses.cpu().numpy().astype(np.float64)
+            self.epoch_losses.append(l)
+            self.epoch_times.append(epoch_time)
+            print(f"Epoch: {epoch}, loss_g: {l[:, 0].sum() / num_batches}, loss_gen: {l[:, 1].sum() / num_batches}, time: {epoch_time}s")
+            if epoch % args.valid_epochs == 0:
+                print("Valid at epoch {}".format(epoch))
+                auc, ap = test_aegis(idx_valid, y_valid, gnn_model, bs, args.thres)
+                self.valid_history.append((epoch, auc, ap))
+        random.setstate(rng.to_python_state())
+        return None
+
+    def _train_device(self, gnn_model, graph, optimizer, base, rng, losses, num_batches, bs):
+        """The same loop with config key `aegis_device: true` (aegis_device.py): per batch one forward and one backward launch of
+        `csrc/aegis_mb.hip` and the flat Adam kernel, one fold of the batch norm's running buffers per epoch.  Epoch 0 runs eagerly
+        (it creates the Adam state and sizes every buffer); after it the `num_batches` steps of an epoch are ONE hipGraph, replayed on
+        the plan buffers of the new epoch as `model_handler_dominate.py` does (fixed addresses, fixed batch boundaries; config key
+        `capture: false` turns it off; a plan buffer that moves is captured again).  Same schedule, same `random` stream."""
+        args = self.args
+        enc, ad = gnn_model.enc, gnn_model.enc.aegis_device
+        idx_valid, y_valid = self.dataset["idx_valid"], self.dataset["y_valid"]
+        capture = bool(getattr(args, "capture", True))
+        epoch_graph, graph_at = None, None
+        ad.reserve(min(bs, len(base)), num_batches)
+
+        def run_batches(x_feat, x_noise, bp):
+            for b in range(num_batches):
+                optimizer.zero_grad()
+                ad.step(x_feat[bp[b]:bp[b + 1]], x_noise[bp[b]:bp[b + 1]], out=losses[b], slot=b, fold=False)
+                optimizer.step()
+            ad.fold(num_batches, 0)
+
+        for epoch in range(args.num_epochs):
+            sampled = base.copy()                                                # :132 a fresh concatenation every epoch
+            rng.shuffle(sampled)                                                 # :133
+            t0 = time.time()
+            batches = [sampled[b * bs:min((b + 1) * bs, len(sampled))] for b in range(num_batches)]
+            x_feat, x_noise, bp = enc.aggregator.aggregate(batches, graph, num_batches)
+            at = (x_feat.data_ptr(), x_noise.data_ptr())
+            if capture and epoch >= 1 and (epoch_graph is None or graph_at != at):
+                torch.cuda.synchronize()
+                epoch_graph, graph_at = torch.cuda.CUDAGraph(), at
+                with torch.cuda.graph(epoch_graph):
+                    run_batches(x_feat, x_noise, bp)
+            if epoch_graph is not None and graph_at == at:
+                epoch_graph.replay()
+            else:
+                run_batches(x_feat, x_noise, bp)
             torch.cuda.synchronize()
             epoch_time = time.time() - t0
             l = losses.cpu().numpy().astype(np.float64)

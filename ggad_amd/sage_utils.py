@@ -183,6 +183,9 @@ def aegis_scores(model, test_cases: Sequence[int], batch_size: int, batches_per_
         for g0 in range(0, len(slices), batches_per_launch):
             grp = slices[g0:g0 + batches_per_launch]
             x_feat, x_noise, bp = enc.aggregator.aggregate(grp, enc.adj_lists, len(grp))
+            if getattr(enc, "aegis_device", None) is not None:          # one forward launch + one fold for the whole group
+                out.append(enc.aegis_device.score_many(x_feat, x_noise, bp[:len(grp) + 1]))
+                continue
             for b in range(len(grp)):
                 logits, _, _ = enc.discriminate(x_feat[bp[b]:bp[b + 1]], x_noise[bp[b]:bp[b + 1]])
                 out.append(logits[:int(len(logits) / 2), 0].clone())

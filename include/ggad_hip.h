@@ -919,6 +919,42 @@ int ggad_sage_fwd_f32(const float *feat, int32_t feat_dim, const int32_t *nodes,
 int ggad_sage_bwd_f32(const float *combined, const float *emb, const float *dscores, const float *w_cls, int32_t n_batch,
                       int32_t feat_dim, int32_t embed_dim, float *ws, float *d_enc, float *d_cls, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Mini-batch AEGIS comparison model (reference src/graphsage_aegis.py:167-173, 298-323), the discriminator step on the two 1-hop
+ * aggregates of a batch (aegis_mb.hip).  x_feat / x_noise: total_rows x feat_dim tables; batch i owns rows
+ * [batch_ptr[i], batch_ptr[i + 1]) of both (B_i rows, 2 <= B_i <= ggad_aegis_mb_max_rows(); a batch outside that is left alone).
+ * Parameters: w_enc (64 x feat_dim), w0 (64 x 64), b0, gamma, beta (64), w1 (64), b1 (1).
+ *
+ * ggad_aegis_mb_fwd_f32   one workgroup per batch.  E = relu([x_feat; x_noise] w_enc^T), H = E w0^T + b0; call 1 over the 2B rows
+ *                         and call 2 over the B noise rows: batch statistics (two-pass), sigmoid(BN(H)), p = sigmoid(. w1 + b1).
+ *                         mode 0: p_all (2 total_rows floats: batch i at 2 batch_ptr[i], real rows then noise rows), p_gen (total_rows),
+ *                         losses (2 per batch: loss_dis, loss_g), stats (256 per batch: mu, unbiased var, mu', unbiased var').
+ *                         mode 1: also what the backward reads -- scratch (ggad_aegis_mb_scratch_elems floats, row-indexed like
+ *                         p_all) and inv_std (128 per batch).  mode 2: scores only -- p_all gets total_rows floats, the real rows'
+ *                         p at their table row; p_gen and losses may be NULL; stats as before.
+ * ggad_aegis_mb_bwd_f32   one workgroup, the batch batch_ptr[0 .. 1] (pass batch_ptr + i, stats + 256 i, inv_std + 128 i): the seven
+ *                         gradients of loss_dis + loss_g.  Overwrites the scratch of that batch.
+ * ggad_aegis_mb_fold_f32  running <- momentum * batch + (1 - momentum) * running for call 1 then call 2 of every batch, in batch
+ *                         order; num_batches_tracked (int64, may be NULL) += 2 n_batches.
+ * No floating-point atomics, no allocation, no synchronisation: equal inputs give equal bits, eager or replayed.
+ * ggad_aegis_mb_supported(feat_dim, embed_dim, max_rows): 1 <= feat_dim <= 64, embed_dim == 64, 2 <= max_rows <=
+ * ggad_aegis_mb_max_rows(); anything else is GGAD_E_UNSUPPORTED and nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_aegis_mb_max_rows(void);
+int32_t ggad_aegis_mb_supported(int32_t feat_dim, int32_t embed_dim, int32_t max_rows);
+int64_t ggad_aegis_mb_scratch_elems(int64_t total_rows);
+int ggad_aegis_mb_fwd_f32(const float *x_feat, const float *x_noise, const int32_t *batch_ptr, int32_t n_batches, int32_t total_rows,
+                          int32_t max_rows, int32_t feat_dim, int32_t embed_dim, const float *w_enc, const float *w0, const float *b0,
+                          const float *gamma, const float *beta, const float *w1, const float *b1, int32_t mode, float *p_all,
+                          float *p_gen, float *losses, float *stats, float *scratch, float *inv_std, ggad_stream_t stream);
+int ggad_aegis_mb_bwd_f32(const float *x_feat, const float *x_noise, const int32_t *batch_ptr, int32_t total_rows, int32_t max_rows,
+                          int32_t feat_dim, int32_t embed_dim, const float *w0, const float *gamma, const float *beta, const float *w1,
+                          const float *p_all, const float *p_gen, const float *stats, float *scratch, const float *inv_std,
+                          float *d_w_enc, float *d_w0, float *d_b0, float *d_gamma, float *d_beta, float *d_w1, float *d_b1,
+                          ggad_stream_t stream);
+int ggad_aegis_mb_fold_f32(const float *stats, int32_t n_batches, float momentum, float *running_mean, float *running_var,
+                           int64_t *num_batches_tracked, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
