@@ -100,6 +100,34 @@ int ggad_int_gemm_slab(const float *A, const float *B, float *C, int M, int N, i
 int64_t ggad_int_wgrad_tn_ws(int R, int m, int n);
 int ggad_int_wgrad_tn(const float *P, int64_t ldp, const float *Q, int64_t ldq, int R, int m, int n, float *D, float *ws, hipStream_t st);
 
+// ---- step_wide.hip: the layered step chain for 64 < D <= 256 (and chain 3 at any D <= 256); arguments and buffer contracts of the
+// ggad_mb_* entry points of the same names (step.hip forwards to these)
+constexpr int GGAD_MB_BWD_PARTS = 256;           // partial dW blocks of bwd_flat (both variants: ggad_mb_bwd_parts())
+struct ggad_xchg_view;
+bool ggad_int_wide_ok(int D, int F);
+int ggad_int_wide_project(const float *params, int32_t D, int32_t F, const float *x2, const int32_t *ent_own, int32_t ent0,
+                          int32_t n_ents, float *h2, ggad_stream_t stream);
+int ggad_int_wide_fwd_rows(const float *params, int32_t D, int32_t F, const float *x1, const float *h2, const int32_t *ent_ptr,
+                           const int32_t *ent_own, const int32_t *labels, int32_t row0, int32_t n_rows, int32_t ent0, float *h1,
+                           float *nbar, float *gen, ggad_stream_t stream);
+int ggad_int_wide_loss(const float *params, int32_t D, int32_t F, const float *h1, const float *nbar, const float *gen,
+                       const int32_t *labels, const int32_t *pos_meta, const int32_t *row_pos, const int32_t *ent_ptr,
+                       int32_t row0, int32_t n_rows, float *loss_ws, float *losses8, float *d_h1, float *d_gen, float *d_nbar,
+                       float *dz, float *coef_a, float *coef_g, int32_t *step_counter, ggad_stream_t stream);
+int ggad_int_wide_row_coefs(const float *params, int32_t D, int32_t F, const int32_t *labels, const int32_t *ent_ptr,
+                            int32_t row0, int32_t n_rows, const float *h1, const float *gen, const float *d_h1,
+                            const float *d_gen, const float *d_nbar, float *dz, float *coef_a, float *coef_g,
+                            ggad_stream_t stream);
+int ggad_int_wide_bwd_flat(int32_t D, int32_t F, const float *x1, const float *x2, const float *h2, const int32_t *ent_own,
+                           const int32_t *ent_row, int32_t row0, int32_t n_rows, int32_t ent0, int32_t n_ents,
+                           const float *coef_a, const float *coef_g, float *dw_part, ggad_stream_t stream);
+int ggad_int_wide_grad_reduce(int32_t D, int32_t F, const int32_t *pos_meta, int32_t row0, int32_t n_rows, const float *losses8,
+                              const float *nbar, const float *dw_part, const float *dz, const float *loss_ws, float *grads,
+                              int mode, float *params, float *m, float *v, float lr, float wd, const int32_t *step_counter,
+                              const ggad_xchg_view *xv, uint32_t xstep, float grad_scale, ggad_stream_t stream);
+int ggad_int_wide_rows(const float *params, int32_t D, int32_t F, const float *x1, int32_t n_rows, float *out, int score,
+                       ggad_stream_t stream);
+
 // ---- one-shot gradient exchange (exchange.cpp owns the handle, step.hip the kernel)
 constexpr int GGAD_XCHG_MAX_WORLD = 16;
 struct ggad_xchg_view {                          // what the kernel needs, passed by value

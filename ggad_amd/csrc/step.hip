@@ -27,7 +27,7 @@
 
 namespace {
 
-constexpr int BWD_PARTS = 256;   // workgroups (= partial dW blocks) of bwd_flat (dense chain alone: 64 -> 37.5, 128 -> 33.6, 192 -> 32.0, 256 -> 31.5, 384 -> 31.1 us per step)
+constexpr int BWD_PARTS = GGAD_MB_BWD_PARTS;   // 256: workgroups (= partial dW blocks) of bwd_flat (dense chain alone: 64 -> 37.5, 128 -> 33.6, 192 -> 32.0, 256 -> 31.5, 384 -> 31.1 us per step)
 
 // W^T column of this lane, either in registers (FT > 0: compile-time F) or read from LDS.
 template <int FT>
@@ -855,6 +855,9 @@ __global__ void __launch_bounds__(256) k_loss_pos_ck(const float *__restrict__ p
 }
 
 bool dims_ok(int D, int F) { return D >= 1 && D <= GGAD_MAX_D && F >= 1 && (size_t)(4 * F * D + 512) * 4 <= 150 * 1024; }
+// D > GGAD_MAX_D: the entry points forward to the wide chain (step_wide.hip)
+bool is_wide(int D) { return D > GGAD_MAX_D; }
+bool dims_any(int D, int F) { return is_wide(D) ? ggad_int_wide_ok(D, F) : dims_ok(D, F); }
 
 }  // namespace
 
@@ -868,7 +871,7 @@ int64_t ggad_mb_param_count(int32_t D, int32_t F) { return (int64_t)D + (int64_t
 int64_t ggad_mb_param_block_elems(int32_t D, int32_t F) { return ggad_mb_param_count(D, F) + (int64_t)F * D + (int64_t)D * D; }
 
 int ggad_mb_params_sync(float *params, int32_t D, int32_t F, ggad_stream_t stream) {
-  GGAD_REQUIRE(params && dims_ok(D, F));
+  GGAD_REQUIRE(params && dims_any(D, F));
   ParamLayout L{D, F};
   k_params_sync<<<dim3((L.n_train() + 255) / 256), dim3(256), 0, as_stream(stream)>>>(params, L);
   GGAD_CHECK_LAUNCH("mb_params_sync");
@@ -877,6 +880,7 @@ int ggad_mb_params_sync(float *params, int32_t D, int32_t F, ggad_stream_t strea
 
 int ggad_mb_project(const float *params, int32_t D, int32_t F, const float *x2, const int32_t *ent_own, int32_t ent0,
                     int32_t n_ents, float *h2, ggad_stream_t stream) {
+  if (is_wide(D)) return ggad_int_wide_project(params, D, F, x2, ent_own, ent0, n_ents, h2, stream);
   GGAD_REQUIRE(params && x2 && ent_own && h2 && dims_ok(D, F) && ent0 >= 0 && n_ents >= 0);
   if (n_ents == 0) return GGAD_OK;
   ParamLayout L{D, F};
@@ -892,6 +896,8 @@ int ggad_mb_project(const float *params, int32_t D, int32_t F, const float *x2, 
 int ggad_mb_fwd_rows(const float *params, int32_t D, int32_t F, const float *x1, const float *h2, const int32_t *ent_ptr,
                      const int32_t *ent_own, const int32_t *labels, int32_t row0, int32_t n_rows, int32_t ent0, float *h1,
                      float *nbar, float *gen, ggad_stream_t stream) {
+  if (is_wide(D))
+    return ggad_int_wide_fwd_rows(params, D, F, x1, h2, ent_ptr, ent_own, labels, row0, n_rows, ent0, h1, nbar, gen, stream);
   GGAD_REQUIRE(params && x1 && h2 && ent_ptr && ent_own && labels && h1 && nbar && gen && dims_ok(D, F));
   GGAD_REQUIRE(n_rows >= 0 && row0 >= 0 && ent0 >= 0);
   if (n_rows == 0) return GGAD_OK;
@@ -907,14 +913,17 @@ int ggad_mb_fwd_rows(const float *params, int32_t D, int32_t F, const float *x1,
 }
 
 int64_t ggad_mb_loss_workspace_elems(int32_t n_rows) {
-  // pos_scal[n_rows][8] | part[nwg][8] | gw: [nwg][64] (sized for n_rows workgroups)
-  return (int64_t)n_rows * 8 + (int64_t)loss_nwg(n_rows) * 8 + (int64_t)n_rows * 64;
+  // pos_scal[n_rows][8] | part[nwg][8] | gw: [nwg][64], or [nwg][64 ceil(D / 64)] on the wide chain (sized for its widest: 256)
+  return (int64_t)n_rows * 8 + (int64_t)loss_nwg(n_rows) * 8 + (int64_t)loss_nwg(n_rows) * 256;
 }
 
 int ggad_mb_loss(const float *params, int32_t D, int32_t F, const float *h1, const float *nbar, const float *gen,
                  const int32_t *labels, const int32_t *pos_meta, const int32_t *row_pos, const int32_t *ent_ptr,
                  int32_t row0, int32_t n_rows, float *loss_ws, float *losses8, float *d_h1, float *d_gen, float *d_nbar,
                  float *dz, float *coef_a, float *coef_g, int32_t *step_counter, ggad_stream_t stream) {
+  if (is_wide(D))
+    return ggad_int_wide_loss(params, D, F, h1, nbar, gen, labels, pos_meta, row_pos, ent_ptr, row0, n_rows, loss_ws, losses8, d_h1,
+                              d_gen, d_nbar, dz, coef_a, coef_g, step_counter, stream);
   GGAD_REQUIRE(params && h1 && nbar && gen && labels && pos_meta && row_pos && ent_ptr && loss_ws && losses8);
   GGAD_REQUIRE(dz && coef_a && coef_g);
   GGAD_REQUIRE((d_h1 == nullptr) == (d_gen == nullptr) && (d_h1 == nullptr) == (d_nbar == nullptr));
@@ -935,6 +944,9 @@ int ggad_mb_row_coefs(const float *params, int32_t D, int32_t F, const int32_t *
                       int32_t row0, int32_t n_rows, const float *h1, const float *gen, const float *d_h1,
                       const float *d_gen, const float *d_nbar, float *dz, float *coef_a, float *coef_g,
                       ggad_stream_t stream) {
+  if (is_wide(D))
+    return ggad_int_wide_row_coefs(params, D, F, labels, ent_ptr, row0, n_rows, h1, gen, d_h1, d_gen, d_nbar, dz, coef_a, coef_g,
+                                   stream);
   GGAD_REQUIRE(params && labels && ent_ptr && h1 && gen && d_h1 && d_gen && d_nbar && dz && coef_a && coef_g);
   GGAD_REQUIRE(dims_ok(D, F) && n_rows >= 1 && row0 >= 0);
   ParamLayout L{D, F};
@@ -952,6 +964,8 @@ static int bwd_flat_launch(int32_t D, int32_t F, const float *x1, const float *x
 int ggad_mb_bwd_flat(int32_t D, int32_t F, const float *x1, const float *x2, const float *h2, const int32_t *ent_own,
                      const int32_t *ent_row, int32_t row0, int32_t n_rows, int32_t ent0, int32_t n_ents,
                      const float *coef_a, const float *coef_g, float *dw_part, ggad_stream_t stream) {
+  if (is_wide(D))
+    return ggad_int_wide_bwd_flat(D, F, x1, x2, h2, ent_own, ent_row, row0, n_rows, ent0, n_ents, coef_a, coef_g, dw_part, stream);
   return bwd_flat_launch(D, F, x1, x2, h2, ent_own, ent_row, row0, n_rows, ent0, n_ents, coef_a, coef_g, dw_part, 0, stream);
 }
 
@@ -977,6 +991,9 @@ static int bwd_flat_launch(int32_t D, int32_t F, const float *x1, const float *x
 int ggad_mb_grad_reduce(int32_t D, int32_t F, const int32_t *pos_meta, int32_t row0, int32_t n_rows,
                         const float *losses8, const float *nbar, const float *dw_part, const float *dz,
                         const float *loss_ws, float *grads, ggad_stream_t stream) {
+  if (is_wide(D))
+    return ggad_int_wide_grad_reduce(D, F, pos_meta, row0, n_rows, losses8, nbar, dw_part, dz, loss_ws, grads, 0, nullptr, nullptr,
+                                     nullptr, 0.f, 0.f, nullptr, nullptr, 0u, 1.0f, stream);
   GGAD_REQUIRE(pos_meta && losses8 && nbar && dw_part && dz && loss_ws && grads && dims_ok(D, F) && n_rows >= 1);
   ParamLayout L{D, F};
   const int nwg = loss_nwg(n_rows);
@@ -991,7 +1008,7 @@ int ggad_mb_grad_reduce(int32_t D, int32_t F, const int32_t *pos_meta, int32_t r
 int ggad_mb_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *grads, int32_t D, int32_t F,
                  float lr, float weight_decay, float grad_scale, const int32_t *step_counter,
                  ggad_stream_t stream) {
-  GGAD_REQUIRE(params && exp_avg && exp_avg_sq && grads && step_counter && dims_ok(D, F));
+  GGAD_REQUIRE(params && exp_avg && exp_avg_sq && grads && step_counter && dims_any(D, F));
   ParamLayout L{D, F};
   k_adam<<<dim3((L.n_train() + 255) / 256), dim3(256), 0, as_stream(stream)>>>(params, exp_avg, exp_avg_sq, grads, L, lr,
                                                                               weight_decay, grad_scale, step_counter);
@@ -1001,6 +1018,7 @@ int ggad_mb_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *
 
 int ggad_mb_score(const float *params, int32_t D, int32_t F, const float *x1, int32_t n_rows, float *prob,
                   ggad_stream_t stream) {
+  if (is_wide(D)) return ggad_int_wide_rows(params, D, F, x1, n_rows, prob, 1, stream);
   GGAD_REQUIRE(params && x1 && prob && dims_ok(D, F) && n_rows >= 0);
   if (n_rows == 0) return GGAD_OK;
   ParamLayout L{D, F};
@@ -1012,6 +1030,7 @@ int ggad_mb_score(const float *params, int32_t D, int32_t F, const float *x1, in
 
 int ggad_mb_encode(const float *params, int32_t D, int32_t F, const float *x1, int32_t n_rows, float *h,
                    ggad_stream_t stream) {
+  if (is_wide(D)) return ggad_int_wide_rows(params, D, F, x1, n_rows, h, 0, stream);
   GGAD_REQUIRE(params && x1 && h && dims_ok(D, F) && n_rows >= 0);
   if (n_rows == 0) return GGAD_OK;
   ParamLayout L{D, F};
@@ -1023,7 +1042,7 @@ int ggad_mb_encode(const float *params, int32_t D, int32_t F, const float *x1, i
 
 /* One whole training step for one batch.  chain 0 (default): fwd_rows_v (projection fused, F == 17; else project ->
  * fwd_rows) -> loss_pos -> loss_rows -> bwd_flat -> grad_reduce; chain 2: always project -> fwd_rows -> ...
- * (the generic layered chain).
+ * (the generic layered chain); chain 3, and any chain at D > 64: the layered chain of step_wide.hip.
  * Adam is fused into the last launch when fuse_adam != 0; otherwise the caller all-reduces s->grads and calls
  * ggad_mb_adam. */
 int64_t ggad_mb_dw_part_elems(int32_t n_rows, int32_t D, int32_t F) {
@@ -1041,9 +1060,22 @@ int ggad_mb_train_step(const ggad_mb_step *s, int32_t fuse_adam, ggad_stream_t s
 static int train_step_impl(const ggad_mb_step *s, int32_t fuse_adam, const ggad_xchg_view *xv, uint32_t xstep, float grad_scale,
                            ggad_stream_t stream) {
   GGAD_REQUIRE(s && s->params && s->exp_avg && s->exp_avg_sq && s->grads && s->step_counter);
-  GGAD_REQUIRE(s->chain == 0 || s->chain == 2);
+  GGAD_REQUIRE(s->chain == 0 || s->chain == 2 || s->chain == 3);
   const int D = s->D, F = s->F;
   int rc;
+  if (s->chain == 3 || is_wide(D)) {       // the wide chain (step_wide.hip): always the six layered launches
+    if ((rc = ggad_int_wide_project(s->params, D, F, s->x2, s->ent_own, s->ent0, s->n_ents, s->h2, stream))) return rc;
+    if ((rc = ggad_int_wide_fwd_rows(s->params, D, F, s->x1, s->h2, s->ent_ptr, s->ent_own, s->labels, s->row0, s->n_rows, s->ent0,
+                                     s->h1, s->nbar, s->gen, stream))) return rc;
+    if ((rc = ggad_int_wide_loss(s->params, D, F, s->h1, s->nbar, s->gen, s->labels, s->pos_meta, s->row_pos, s->ent_ptr, s->row0,
+                                 s->n_rows, s->loss_ws, s->losses8, nullptr, nullptr, nullptr, s->dz, s->coef_a, s->coef_g,
+                                 s->step_counter, stream))) return rc;
+    if ((rc = ggad_int_wide_bwd_flat(D, F, s->x1, s->x2, s->h2, s->ent_own, s->ent_row, s->row0, s->n_rows, s->ent0, s->n_ents,
+                                     s->coef_a, s->coef_g, s->dw_part, stream))) return rc;
+    return ggad_int_wide_grad_reduce(D, F, s->pos_meta, s->row0, s->n_rows, s->losses8, s->nbar, s->dw_part, s->dz, s->loss_ws,
+                                     s->grads, fuse_adam, s->params, s->exp_avg, s->exp_avg_sq, s->lr, s->weight_decay,
+                                     s->step_counter, xv, xstep, grad_scale, stream);
+  }
   // 5 launches: the projection is done by the forward-rows kernel -- unless the batch holds a hub row (one workgroup would
   // project thousands of entries while the flat k_project spreads them over the chip)
   static const int fuse_max_row = [] { const char *e = getenv("GGAD_FUSE_MAX_ROW"); return e ? atoi(e) : 256; }();
@@ -1168,6 +1200,7 @@ int ggad_mb_train_chunk_xchg(const ggad_mb_step *tmpl, int32_t n_batches, const 
                              const int32_t *batch_max_row, float *loss_log, int32_t log_base, float grad_scale, ggad_xchg *xchg,
                              ggad_stream_t stream) {
   GGAD_REQUIRE(tmpl && batch_ptr && batch_ent_ptr && loss_log && xchg && n_batches >= 0 && log_base >= 0);
+  GGAD_REQUIRE(!is_wide(tmpl->D));          // the one-shot exchange is sized and tested for D <= 64
   ParamLayout L{tmpl->D, tmpl->F};
   GGAD_REQUIRE(xchg->view.n >= L.n_train());
   for (int q = 0; q < xchg->view.world; ++q) GGAD_REQUIRE(xchg->view.peer[q] != nullptr);

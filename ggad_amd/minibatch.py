@@ -416,12 +416,15 @@ class MiniBatchEngine:
                  chain: int = 0, resident: Optional[bool] = None):
         """`resident`: run the dense steps of a chunk as ONE launch resident on one XCD (`ggad_mb_train_chunk_xcd`,
         csrc/step_xcd.hip) instead of 5 launches per step.  None = whenever the kernel supports the shapes (F == 17,
-        D <= 64, chain 0) and GGAD_XCD is not 0."""
+        D <= 64, chain 0) and GGAD_XCD is not 0.
+        `embed_dim` above `ggad_max_embed_dim()` (64), up to `ggad_mb_wide_max_embed_dim()` (256), trains on the wide launch chain
+        (csrc/step_wide.hip) whatever `chain` says; `chain=3` takes that chain at D <= 64 too."""
         self.lib = _lib.load()
-        # 0: fused-forward step (5 launches, F == 17); 2: always the generic 6 launches (project -> fwd_rows -> ...)
+        # 0: fused-forward step (5 launches, F == 17); 2: always the generic 6 launches (project -> fwd_rows -> ...);
+        # 3: the 6 launches of the wide chain (a lane owns channels lane + 64 j), which D > 64 takes under any value
         self.chain = int(chain)
-        if self.chain not in (0, 2):
-            raise ValueError("chain must be 0 or 2")
+        if self.chain not in (0, 2, 3):
+            raise ValueError("chain must be 0, 2 or 3")
         self.F, self.D = int(feat_dim), int(embed_dim)
         import os
         can = int(feat_dim) == 17 and int(embed_dim) <= 64 and self.chain == 0
@@ -434,8 +437,11 @@ class MiniBatchEngine:
         self.xcd_wgs = 0                 # workgroups of the resident launch that stay (0 = 32: a whole XCD)
         self._xcd_rows = 0
         self._xcd_caps = (0, 0)
-        if self.D > self.lib.ggad_max_embed_dim():
-            raise ValueError(f"emb_size {self.D} > {self.lib.ggad_max_embed_dim()} is not supported by the HIP step kernels")
+        self.wide = self.chain == 3 or self.D > int(self.lib.ggad_max_embed_dim())
+        if self.wide and not self.lib.ggad_mb_wide_supported(self.D, self.F):
+            raise ValueError(f"emb_size {self.D} / feature width {self.F} is not supported by the HIP step kernels: the wide chain "
+                             f"takes 1 <= emb_size <= {int(self.lib.ggad_mb_wide_max_embed_dim())} and "
+                             f"1 <= features <= {int(self.lib.ggad_max_feat_dim())}")
         self.dev = torch.device(device)
         self.lr, self.wd = float(lr), float(weight_decay)
         self.n_train = int(self.lib.ggad_mb_param_count(self.D, self.F))
@@ -555,6 +561,8 @@ class MiniBatchEngine:
                        "ggad_mb_train_chunk_xcd")
             return
         if exchange is not None:
+            if self.D > int(self.lib.ggad_max_embed_dim()):
+                raise ValueError(f"the one-shot exchange takes emb_size <= {int(self.lib.ggad_max_embed_dim())}; use the all-reduce path")
             s = self.step_desc(ch, 0, log_base)
             bp, ep, mr = ch._bp_host, ch._bep_host, ch._bmr_host
             _lib.check(self.lib.ggad_mb_train_chunk_xchg(ctypes.byref(s), ch.n_batches, bp.ctypes.data, ep.ctypes.data,

@@ -13,7 +13,7 @@ unpacks four (`:358-362`), and `test_sage` calls `to_prob(nodes, None)` where `G
 
 Extra, optional config keys:  ``device`` (cuda index), ``num_batches`` (default 150, the reference's
 hard override `:317`), ``data`` = (adj_lists | DeviceGraph | (rowptr, col), feat_data, labels) to bypass
-the file loader, ``log_every``.  Under `torch.distributed` (backend nccl = RCCL) batches are dealt
+the file loader, ``log_every``, ``n_pseudo`` (pseudo-anomalies per batch, default 50: the reference's `:342-347`).  Under `torch.distributed` (backend nccl = RCCL) batches are dealt
 round-robin over the ranks and gradients are all-reduced once per step.
 """
 from __future__ import annotations
@@ -122,7 +122,7 @@ class ModelHandler(object):
         if own_stream:
             rng = PyCompatRandom(int(getattr(args, "seed", 0)) * 1000003 + rank + 1)
         sched = BatchSchedule(idx_train, self.dataset["idx_anomaly"], self.dataset["labels"], args.batch_size, rng,
-                              n_pseudo=50, batches_per_epoch=num_batches)
+                              n_pseudo=int(getattr(args, "n_pseudo", 50)), batches_per_epoch=num_batches)      # (50: the reference's, :342-347)
         allreduce = None
         if world > 1:
             def allreduce(t):
@@ -134,7 +134,7 @@ class ModelHandler(object):
                                 device=features.weight.device if dist.get_backend() == "nccl" else "cpu")
             dist.broadcast(flag, src=0)
             want_oneshot = bool(flag.item())
-        if world > 1 and want_oneshot:
+        if world > 1 and want_oneshot and engine.D <= int(engine.lib.ggad_max_embed_dim()):     # (emb_size > 64: the all-reduce path)
             # one-shot peer-write exchange inside the gradient / Adam launch; every rank agrees on whether
             # it is usable, else all of them keep the all-reduce
             from .exchange import OneShotExchange

@@ -152,6 +152,10 @@ class DGraphTrainer:
         # device (tests) must pass False: two resident kernels cannot both hold the same XCD
         self.engine = engine or MiniBatchEngine(feat.shape[1], embed_dim, feat.device, lr, weight_decay, chain=chain,
                                                 resident=(None if resident is None or resident else False))
+        if exchange is not None and self.engine.D > int(self.engine.lib.ggad_max_embed_dim()):
+            # the wide chain (emb_size > 64) is data parallel through the all-reduce callback only
+            raise ValueError(f"the one-shot exchange takes emb_size <= {int(self.engine.lib.ggad_max_embed_dim())}, got "
+                             f"{self.engine.D}: pass `allreduce` instead of `exchange`")
         self.chunk_batches = int(chunk_batches)
         self.ramp = None if ramp is None else [int(k) for k in ramp]
         f = int(feat.shape[1])

@@ -43,6 +43,16 @@ const char *ggad_last_error(void);
 /* Upper limits compiled into the kernels (embedding width, feature width). */
 int ggad_max_embed_dim(void);
 int ggad_max_feat_dim(void);
+/* ggad_max_embed_dim() (64) is the width of the one-lane-per-channel kernels: the fused chain-0 step, the XCD-resident chunk
+ * kernel, the one-shot exchange and every comparison handler.  The mini-batch step chain (the ggad_mb_* entry points below)
+ * also takes 64 < D <= ggad_mb_wide_max_embed_dim() (256) on the wide chain (csrc/step_wide.hip: a lane owns the channels
+ * lane + 64 j).  ggad_mb_wide_supported(D, F) != 0  <=>  1 <= D <= 256 and 1 <= F <= ggad_max_feat_dim() (1024): the wide
+ * kernels keep nothing of size F or D*D in LDS or registers, so F is bounded by the plan's gather kernels only.  Every
+ * ggad_mb_* entry point that takes (D, F) accepts D > 64 when this predicate holds, with the buffer contracts it has at
+ * D <= 64 (at D <= 64 its own limits apply: (4 F D + 512) floats of LDS <= 150 KB); ggad_mb_train_chunk_xchg and
+ * ggad_mb_train_chunk_xcd return GGAD_E_INVALID at D > 64 and launch nothing. */
+int ggad_mb_wide_max_embed_dim(void);
+int ggad_mb_wide_supported(int32_t D, int32_t F);
 
 /* ------------------------------------------------------------------------------------
  * Generic device primitives
@@ -418,7 +428,8 @@ int ggad_mb_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *
 
 /* Whole training step of one batch in one host call.  chain 0 (default): fwd_rows_v (h2 = relu(W x2) computed by the
  * row's workgroup, F == 17) or project -> fwd_rows, then loss_pos -> loss_rows -> bwd_flat -> grad_reduce (5 or 6
- * launches); chain 2: always 6.
+ * launches); chain 2: always 6; chain 3: the six launches of the wide chain (csrc/step_wide.hip) at any D that
+ * ggad_mb_wide_supported takes -- at D > 64 chains 0 and 2 take it too.
  * Adam is fused into the last launch when fuse_adam != 0 (single GPU); with fuse_adam == 0 the caller all-reduces
  * `grads` and then calls ggad_mb_adam.  All members are device pointers. */
 typedef struct ggad_mb_step {
@@ -431,7 +442,7 @@ typedef struct ggad_mb_step {
   int32_t D, F, row0, n_rows, ent0, n_ents;
   float lr, weight_decay;
   int32_t chain;          /* 0 (default): 5 launches when F == 17 and the batch has no hub row (projection fused into the
-                             forward-rows kernel, h2 per ENTRY), else 6; 2: always 6 */
+                             forward-rows kernel, h2 per ENTRY), else 6; 2: always 6; 3: the wide chain (6 launches) */
   int32_t max_row_entries; /* largest closed neighbourhood among the batch rows (host knowledge; 0 = unknown -> 6 launches) */
   /* optional (all four or none): row-piece tables of the PLAN (staging block of ggad_mb_plan_build) and the
    * partial-sum buffer, float[(chunks of the plan) * 64].  With them a chain-0 batch that holds a hub row takes the
