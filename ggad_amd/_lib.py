@@ -229,6 +229,10 @@ SIGNATURES = {
     "ggad_pcgnn_hop_f32": (c_int32, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     "ggad_pcgnn_nb_fwd_f32": (c_int32, [_P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "ggad_pcgnn_nb_bwd_f32": (c_int32, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
+    "ggad_pcgnn_head_supported": (c_int32, [_I, _I]),
+    "ggad_pcgnn_head_parts": (c_int32, []),
+    "ggad_pcgnn_head_workspace_elems": (c_int64, [_I, _I]),
+    "ggad_pcgnn_head_f32": (c_int32, [_P] * 9 + [_I, _I] + [_P] * 13),
     "ggad_sage_supported": (c_int32, [_I, _I, _I]),
     "ggad_sage_bwd_parts": (c_int32, []),
     "ggad_sage_bwd_workspace_elems": (c_int64, [_I, _I]),

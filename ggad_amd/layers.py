@@ -88,7 +88,7 @@ class InterAgg(nn.Module):
     parity), its evaluation is skipped.  Aggregations: HIP ragged gathers inside `IntraAgg`; every product (the per-relation
     projections, mask @ to_feats_neigh, the two (3D -> D) projections) runs on the MFMA GEMM with autograd (`LinearFn`)."""
 
-    def __init__(self, features, feature_dim, embed_dim, train_pos, adj_lists, intraggs, inter="GNN", cuda=True):
+    def __init__(self, features, feature_dim, embed_dim, train_pos, adj_lists, intraggs, inter="GNN", cuda=True, fused=False):
         super().__init__()
         self.features = _features(features)
         self.dropout = 0.6
@@ -113,7 +113,10 @@ class InterAgg(nn.Module):
         self.device_path = None
         if isinstance(adj_lists, (list, tuple)) and len(adj_lists) == 3 and all(isinstance(a, DeviceGraph) for a in adj_lists):
             from .pcgnn_device import PcgnnDevice
-            self.device_path = PcgnnDevice(self.features, self.feat_dim, self.embed_dim, adj_lists)
+            self.device_path = PcgnnDevice(self.features, self.feat_dim, self.embed_dim, adj_lists, fused=fused)
+        elif fused:
+            raise ValueError("InterAgg(fused=True) needs the device path: three DeviceGraph relations (config keys `pcgnn_fused` "
+                             "and `pcgnn_device`)")
 
     def forward(self, nodes, labels, train_flag=True):
         if self.device_path is not None:
@@ -137,7 +140,9 @@ class InterAgg(nn.Module):
 
 class PCALayer(nn.Module):
     """`PCALayer` of the reference's `src/model.py:8-48`: class scores from the inter-relation embedding, cross entropy +
-    5 x the affinity margin (margin 1); `loss` returns (total, margin term), `to_prob` the two sigmoid score sets."""
+    5 x the affinity margin (margin 1); `loss` returns (total, margin term), `to_prob` the two sigmoid score sets.  When `inter1`
+    runs its device path with `fused` on, `loss` and `to_prob` go through the HIP head (`pcgnn_device.PcgnnHeadFn`): no
+    `torch.argwhere`, nothing that waits for the device; only the total is differentiable there."""
 
     def __init__(self, num_classes, inter1, lambda_1):
         super().__init__()
@@ -154,7 +159,16 @@ class PCALayer(nn.Module):
         scores_t = LinearFn.apply(embeds1.t().contiguous(), self.weight, False)        # (weight.mm(embeds1)).t()   :25-26
         return scores_t, affinity
 
+    def _fused(self):
+        """The device path of `inter1` when its fused head is on (csrc/pcgnn_head.hip), else None."""
+        dp = getattr(self.inter1, "device_path", None)
+        return dp if dp is not None and dp.fused else None
+
     def to_prob(self, nodes, labels, train_flag=True):
+        dp = self._fused()
+        if dp is not None:
+            gnn_logits, label_logits = dp.head_forward(self.inter1, self.weight, nodes)
+            return torch.sigmoid(gnn_logits), torch.sigmoid(label_logits)
         gnn_logits, label_logits = self.forward(nodes, labels, train_flag)
         return torch.sigmoid(gnn_logits), torch.sigmoid(label_logits)
 
@@ -165,6 +179,9 @@ class PCALayer(nn.Module):
 
     def loss(self, nodes, labels, train_flag=True):
         labels = torch.as_tensor(labels, device=self.weight.device).long()
+        dp = self._fused()
+        if dp is not None:
+            return dp.head_loss(self.inter1, self.weight, nodes, labels)
         label_scores, affinity = self.forward(nodes, labels, train_flag)
         loss_cls = self.xent(label_scores, labels.squeeze())
         loss_constraint = self.affinity(affinity, labels)

@@ -40,6 +40,9 @@ class ModelHandler(object):
 
     def __init__(self, config):
         args = argparse.Namespace(**config)
+        if bool(getattr(args, "pcgnn_fused", False)) and not bool(getattr(args, "pcgnn_device", False)):
+            raise ValueError("config key `pcgnn_fused` needs `pcgnn_device: true`: the fused head runs behind the relation kernels of "
+                             "the device path")
         data = getattr(args, "data", None)
         if data is not None:
             homo, feat_data, labels = data
@@ -367,7 +370,8 @@ class ModelHandler(object):
         train_flag=False)[0][:, 1]` (the class-1 GNN score).  No vectors of the reference exist for this loop (it never ran): the
         modules are pinned (tests/golden/minibatch_pcgnn.npz), the loop is checked for self-consistency (tests/test_dropin_gpu.py).
         Config key `pcgnn_device` (default False): the relations become `DeviceGraph`s and `InterAgg` runs from the CSR in HBM
-        (pcgnn_device.py); without it nothing here changes."""
+        (pcgnn_device.py); without it nothing here changes.  Config key `pcgnn_fused` (default False, needs `pcgnn_device`): the head
+        behind the relations and `PCALayer.loss` / `to_prob` run in csrc/pcgnn_head.hip (`PcgnnHeadFn`)."""
         from .fullgraph import FlatAdam
         from .layers import InterAgg, IntraAgg, PCALayer
         from . import synth
@@ -400,7 +404,8 @@ class ModelHandler(object):
         train_pos = [i for i in idx_train if self.dataset["labels"][i] == 1]          # pos_neg_split(idx_train, y_train)[0]
         rho, alpha = float(getattr(args, "rho", 0.5)), float(getattr(args, "alpha", 2))
         intras = [IntraAgg(features, f, args.emb_size, train_pos, rho, cuda=True) for _ in range(3)]         # :270-275
-        inter1 = InterAgg(features, f, args.emb_size, train_pos, adjs, intras, inter=args.multi_relation, cuda=True)    # :276-277
+        inter1 = InterAgg(features, f, args.emb_size, train_pos, adjs, intras, inter=args.multi_relation, cuda=True,      # :276-277
+                          fused=bool(getattr(args, "pcgnn_fused", False)))
         gnn_model = PCALayer(2, inter1, alpha).to(dev)                 # :288
         features.to(dev)
         optimizer = FlatAdam([p for p in gnn_model.parameters() if p.requires_grad], lr=args.lr, weight_decay=args.weight_decay)

@@ -6,7 +6,11 @@ kernels (`csrc/pcgnn.hip`): the neighbourhood plan (U in ascending id order, `po
 of the 2-hop embeddings over the batch rows with its transpose for the backward.  `combined` and `affinity` are sums over U, so
 the order of U does not change them.  |U| is never read back: buffers have the capacity min(N, sum of the batch
 rows' degrees), known from `rowptr_host`, and the rows past |U| are zeros.  There is no fallback: shapes the hop kernel does not
-take raise at construction."""
+take raise at construction.
+
+Opt-in on top (`fused`, config key `pcgnn_fused`): what follows the relations -- both 3D -> D projections, the norms, the affinity,
+the class scores, `PCALayer.loss` and all their gradients -- runs in `csrc/pcgnn_head.hip` (`PcgnnHeadFn`, four launches; one for
+`to_prob`) instead of torch ops, without `argwhere` or any other wait for the device."""
 from __future__ import annotations
 
 import numpy as np
@@ -168,10 +172,102 @@ class PcgnnRelationFn(torch.autograd.Function):
         return gemm(a, dz, True, False), None, None, None, None
 
 
-class PcgnnDevice:
-    """What `InterAgg` holds when every relation is a `DeviceGraph`: one `RelationState` per relation, checked once."""
+def _head_args(t1s, nbs, weight, cls_weight, labels):
+    """Shapes and pointers of one head call, checked on the host before any launch: (B, D, the nine input pointers)."""
+    if len(t1s) != 3 or len(nbs) != 3:
+        raise ValueError("the PC-GNN head takes three relations")
+    if not isinstance(t1s[0], torch.Tensor) or t1s[0].dim() != 2:
+        raise ValueError("T1 of relation 0: expected a (B, D) tensor")
+    b, d = int(t1s[0].shape[0]), int(t1s[0].shape[1])
+    lib = _lib.load()
+    if not lib.ggad_pcgnn_head_supported(b, d):
+        raise ValueError(f"the PC-GNN head kernels take B >= 1 and 1 <= embed_dim <= {int(lib.ggad_max_embed_dim())}; got ({b}, {d})")
+    ptrs = []
+    for name, group in (("T1", t1s), ("NB", nbs)):
+        for r, t in enumerate(group):
+            ptrs.append(_dptr(t, torch.float32, f"{name} of relation {r}"))
+            if tuple(t.shape) != (b, d):
+                raise ValueError(f"{name} of relation {r}: expected shape ({b}, {d}), got {tuple(t.shape)}")
+    ptrs.append(_dptr(weight, torch.float32, "InterAgg.weight"))
+    ptrs.append(_dptr(cls_weight, torch.float32, "PCALayer.weight"))
+    if tuple(weight.shape) != (3 * d, d) or tuple(cls_weight.shape) != (2, d):
+        raise ValueError(f"the PC-GNN head takes InterAgg.weight ({3 * d}, {d}) and PCALayer.weight (2, {d}); got "
+                         f"{tuple(weight.shape)} and {tuple(cls_weight.shape)}")
+    if labels is None:
+        ptrs.append(0)
+    else:
+        ptrs.append(_dptr(labels, torch.int64, "labels"))
+        if labels.numel() != b:
+            raise ValueError(f"labels: expected {b} entries, got {labels.numel()}")
+    return b, d, ptrs
 
-    def __init__(self, features, feat_dim: int, embed_dim: int, graphs):
+
+def pcgnn_head_forward(t1s, nbs, weight, cls_weight):
+    """(scores (B, 2), affinity (B)) of the head in ONE launch (`ggad_pcgnn_head_f32` without a loss): nothing else is written and
+    no gradient buffer exists."""
+    b, d, ptrs = _head_args(t1s, nbs, weight, cls_weight, None)
+    dev = weight.device
+    scores = torch.empty(b, 2, dtype=torch.float32, device=dev)
+    affinity = torch.empty(b, dtype=torch.float32, device=dev)
+    call("ggad_pcgnn_head_f32", *ptrs, b, d, scores.data_ptr(), affinity.data_ptr(), *([0] * 10))
+    return scores, affinity
+
+
+class PcgnnHeadFn(torch.autograd.Function):
+    """(total (1), constraint (1), scores (B, 2), affinity (B)) of `InterAgg`'s two projections, the cosine affinity, the class
+    scores and `PCALayer.loss`, from the three relations' (T1, NB), `InterAgg.weight`, `PCALayer.weight` and int64 labels.  All
+    eight gradients of `total` are computed by the forward call (four launches, csrc/pcgnn_head.hip) into one flat buffer and scaled
+    by the incoming gradient in `backward`; only `total` is differentiable.  `buffers`: optional dict that receives the outputs, the
+    flat gradient buffer and the workspace, all flat float32 (or supplies pre-filled ones under the same keys: the determinism test);
+    the workspace starts with `combined` and `neigh`, B x D each."""
+
+    @staticmethod
+    def forward(ctx, t1_0, nb_0, t1_1, nb_1, t1_2, nb_2, weight, cls_weight, labels, buffers=None):
+        t1s, nbs = [t.detach() for t in (t1_0, t1_1, t1_2)], [t.detach() for t in (nb_0, nb_1, nb_2)]
+        w, wc = weight.detach(), cls_weight.detach()
+        b, d, ptrs = _head_args(t1s, nbs, w, wc, labels)
+        dev = w.device
+        lib = _lib.load()
+        buffers = {} if buffers is None else buffers
+        sizes = [b * d] * 6 + [3 * d * d, 2 * d]
+
+        def buf(key, n):
+            t = buffers.get(key)
+            if t is None:
+                t = buffers[key] = torch.empty(n, dtype=torch.float32, device=dev)
+            _dptr(t, torch.float32, key)
+            if t.numel() != n:
+                raise ValueError(f"{key}: expected {n} floats, got {t.numel()}")
+            return t
+        scores, affinity, loss = buf("scores", 2 * b), buf("affinity", b), buf("loss", 2)
+        grads = buf("grads", sum(sizes))
+        ws = buf("ws", int(lib.ggad_pcgnn_head_workspace_elems(b, d)))
+        offs = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+        gp = [grads.data_ptr() + 4 * o for o in offs[:8]]
+        # flat order: dT1_0, dT1_1, dT1_2, dNB_0, dNB_1, dNB_2, dW, dW_cls
+        call("ggad_pcgnn_head_f32", *ptrs, b, d, scores.data_ptr(), affinity.data_ptr(), loss.data_ptr(), *gp, ws.data_ptr())
+        ctx.grads, ctx.offs, ctx.dims = grads, offs, (b, d)
+        scores, affinity = scores.view(b, 2), affinity
+        total, constraint = loss[0:1], loss[1:2]
+        ctx.mark_non_differentiable(constraint, scores, affinity)
+        return total, constraint, scores, affinity
+
+    @staticmethod
+    def backward(ctx, g, _gc, _gs, _ga):
+        b, d = ctx.dims
+        flat = ctx.grads * g                                       # one launch for all eight
+        o = ctx.offs
+        shapes = [(b, d)] * 6 + [(3 * d, d), (2, d)]
+        dt1_0, dt1_1, dt1_2, dnb_0, dnb_1, dnb_2, dw, dwc = (flat[o[i]:o[i + 1]].view(shapes[i]) for i in range(8))
+        return dt1_0, dnb_0, dt1_1, dnb_1, dt1_2, dnb_2, dw, dwc, None, None
+
+
+class PcgnnDevice:
+    """What `InterAgg` holds when every relation is a `DeviceGraph`: one `RelationState` per relation, checked once.  `fused`: the
+    head behind the relations (both 3D -> D projections, the affinity, the class scores, `PCALayer.loss` and their backward) runs in
+    csrc/pcgnn_head.hip instead of torch ops; off, nothing here changes."""
+
+    def __init__(self, features, feat_dim: int, embed_dim: int, graphs, fused: bool = False):
         lib = _lib.load()
         if not lib.ggad_pcgnn_supported(int(feat_dim), int(embed_dim)):
             raise ValueError(f"the PC-GNN hop kernel takes 1 <= feat_dim <= {int(lib.ggad_pcgnn_max_feat_dim())} and "
@@ -183,9 +279,11 @@ class PcgnnDevice:
             if isinstance(g, DeviceGraph) and (g.n > table.shape[0] or g.device != table.device):
                 raise ValueError("a relation graph has more nodes than the feature table has rows, or lives on another device")
         self.states = [RelationState(g) for g in graphs]
+        self.fused = bool(fused)
+        self.last_head = {}
 
-    def forward(self, inter, nodes):
-        """`InterAgg.forward` from the CSR relations: (combined.t(), affinity)."""
+    def relations(self, inter, nodes):
+        """([T1_0, T1_1, T1_2], [NB_0, NB_1, NB_2]) of the batch from the CSR relations."""
         nodes = _node_array(nodes)
         feat = inter.features.weight.data
         batch = self.states[0].upload(nodes)
@@ -196,6 +294,11 @@ class PcgnnDevice:
             t1, nb = PcgnnRelationFn.apply(agg.weight, st, feat, batch, st.capacity(nodes))
             r_feats.append(t1)
             nb_feats.append(nb)
+        return r_feats, nb_feats
+
+    def forward(self, inter, nodes):
+        """`InterAgg.forward` from the CSR relations: (combined.t(), affinity)."""
+        r_feats, nb_feats = self.relations(inter, nodes)
         wt = inter.weight.t().contiguous()
         combined = LinearFn.apply(torch.cat(r_feats, dim=1), wt, True)
         neigh = LinearFn.apply(torch.cat(nb_feats, dim=1), wt, True)
@@ -205,3 +308,18 @@ class PcgnnDevice:
         nn_ = torch.where(torch.isnan(nn_), torch.full_like(nn_, 0), nn_)
         affinity = (nn_ * cn).sum(1)
         return combined.t(), affinity
+
+    def head_loss(self, inter, cls_weight, nodes, labels):
+        """`PCALayer.loss` on the fused route: (total (1), constraint (1)); `labels`: int64 device tensor, one per node."""
+        r_feats, nb_feats = self.relations(inter, nodes)
+        buffers = {}
+        total, constraint, _, _ = PcgnnHeadFn.apply(r_feats[0], nb_feats[0], r_feats[1], nb_feats[1], r_feats[2], nb_feats[2],
+                                                    inter.weight, cls_weight, labels.reshape(-1), buffers)
+        self.last_head = buffers                                   # buffers of the latest training call (tests, profiling)
+        return total, constraint
+
+    def head_forward(self, inter, cls_weight, nodes):
+        """`PCALayer.forward` on the fused route, forward only: (scores (B, 2), affinity (B)), no graph recorded."""
+        with torch.no_grad():
+            r_feats, nb_feats = self.relations(inter, nodes)
+            return pcgnn_head_forward(r_feats, nb_feats, inter.weight.detach(), cls_weight.detach())

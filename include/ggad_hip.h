@@ -931,6 +931,31 @@ int ggad_sage_bwd_f32(const float *combined, const float *emb, const float *dsco
                       int32_t feat_dim, int32_t embed_dim, float *ws, float *d_enc, float *d_cls, ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Head and loss of the PC-GNN comparison model behind its relation kernels (pcgnn_head.hip; reference src/layers.py:125-153,
+ * src/model.py:25-48).  t1_r / nb_r: the batch embedding and the neighbourhood mean of relation r, n_batch x embed_dim each, rows
+ * embed_dim apart; w: 3 embed_dim x embed_dim (InterAgg.weight); w_cls: 2 x embed_dim (PCALayer.weight); labels: n_batch int64 in
+ * {0, 1}.
+ *   combined = relu([t1_0 t1_1 t1_2] w), neigh = relu([nb_0 nb_1 nb_2] w), affinity_i = <combined_i / |combined_i|, neigh_i / |neigh_i|>
+ *   (a row of norm 0 counts as a row of zeros), scores = combined w_cls^T (n_batch x 2),
+ *   loss[1] = max(0, 1 - (a0 - a1)) with a0 / a1 the mean affinity of the label-0 / label-1 rows, loss[0] = mean cross entropy of
+ *   scores + 5 loss[1].  A batch without a row of one label has a 0 / 0 mean: both entries of loss are NaN, the hinge passes no
+ *   gradient and the cross-entropy gradients stay finite, as torch's autograd gives for the reference's expressions.
+ * loss NULL: forward only -- scores and affinity are the only stores; labels, ws and every d_* pointer may be NULL.
+ * loss given: also the gradients of loss[0]: d_t1_r / d_nb_r (n_batch x embed_dim), d_w (as w), d_cls (as w_cls); ws holds
+ * ggad_pcgnn_head_workspace_elems(n_batch, embed_dim) floats and needs no initialisation.  The weight gradients are summed over
+ * ggad_pcgnn_head_parts() row ranges in range order; no floating-point atomics anywhere: equal inputs give equal bits.
+ * ggad_pcgnn_head_supported(n_batch, embed_dim): n_batch >= 1 and 1 <= embed_dim <= ggad_max_embed_dim(); anything else is
+ * GGAD_E_UNSUPPORTED and nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_pcgnn_head_supported(int32_t n_batch, int32_t embed_dim);
+int32_t ggad_pcgnn_head_parts(void);
+int64_t ggad_pcgnn_head_workspace_elems(int32_t n_batch, int32_t embed_dim);
+int ggad_pcgnn_head_f32(const float *t1_0, const float *t1_1, const float *t1_2, const float *nb_0, const float *nb_1, const float *nb_2,
+                        const float *w, const float *w_cls, const int64_t *labels, int32_t n_batch, int32_t embed_dim, float *scores,
+                        float *affinity, float *loss, float *d_t1_0, float *d_t1_1, float *d_t1_2, float *d_nb_0, float *d_nb_1,
+                        float *d_nb_2, float *d_w, float *d_cls, float *ws, ggad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Mini-batch AEGIS comparison model (reference src/graphsage_aegis.py:167-173, 298-323), the discriminator step on the two 1-hop
  * aggregates of a batch (aegis_mb.hip).  x_feat / x_noise: total_rows x feat_dim tables; batch i owns rows
  * [batch_ptr[i], batch_ptr[i + 1]) of both (B_i rows, 2 <= B_i <= ggad_aegis_mb_max_rows(); a batch outside that is left alone).

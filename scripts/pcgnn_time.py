@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Time per optimiser step of PC-GNN (`IntraAgg` x 3 -> `InterAgg` -> `PCALayer`, FlatAdam): the set path (python sets per batch,
-`ggad_amd/layers.py`) against the device path (CSR relations in HBM, `ggad_amd/pcgnn_device.py`, `csrc/pcgnn.hip`).
+"""Time per optimiser step of PC-GNN (`IntraAgg` x 3 -> `InterAgg` -> `PCALayer`, FlatAdam), three legs: the set path (python sets
+per batch, `ggad_amd/layers.py`), the device path (CSR relations in HBM, `ggad_amd/pcgnn_device.py`, `csrc/pcgnn.hip`) and the
+device path with the fused head (`pcgnn_fused`: `csrc/pcgnn_head.hip` behind the relation kernels).
 
     python scripts/pcgnn_time.py [--steps 30] [--nodes 200000] [--big_nodes 3700550] [--out profiles/pcgnn_time_line.json]
 
 1. Comparison size: three synthetic power-law relations on `--nodes` nodes (a size whose dict-of-sets builds in well under a
-   minute); the same batches, the same initial weights, both paths; median wall time of a step that ends in a device synchronise.
-   The time to build each path's graph container is reported beside it.
-2. The device path alone on three relations of DGraph-Fin's node count (`--big_nodes`, `--big_entries` directed entries each).
+   minute); the same relations, batches and initial weights on all three legs; median wall time of a step that ends in a device
+   synchronise.  The time to build each path's graph container is reported beside it.
+2. The two device legs on three relations of DGraph-Fin's node count (`--big_nodes`, `--big_entries` directed entries each).
 
 Prints and writes one JSON line."""
 import argparse
@@ -28,12 +29,12 @@ from ggad_amd.graphsage import FeatureTable  # noqa: E402
 from ggad_amd.layers import InterAgg, IntraAgg, PCALayer  # noqa: E402
 
 
-def build_model(relations, feat, d, seed):
+def build_model(relations, feat, d, seed, fused=False):
     torch.manual_seed(seed)
     feats = FeatureTable(torch.from_numpy(feat))
     f = feat.shape[1]
     intras = [IntraAgg(feats, f, d, [], 0.5, cuda=True) for _ in range(3)]
-    inter = InterAgg(feats, f, d, [], relations, intras, inter="GNN", cuda=True)
+    inter = InterAgg(feats, f, d, [], relations, intras, inter="GNN", cuda=True, fused=fused)
     model = PCALayer(2, inter, 2)
     return model, FlatAdam([p for p in model.parameters() if p.requires_grad], lr=0.005, weight_decay=0.007)
 
@@ -86,8 +87,9 @@ def main():
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     line = dict(what="PC-GNN, median wall ms per optimiser step (loss, backward, FlatAdam; ends in a device synchronise): set = python-set "
-                     "neighbour lists per batch (layers.IntraAgg), device = CSR relations in HBM (pcgnn_device.py, csrc/pcgnn.hip); same "
-                     "batches and initial weights; big = the device path alone at DGraph-Fin's node count",
+                     "neighbour lists per batch (layers.IntraAgg), device = CSR relations in HBM (pcgnn_device.py, csrc/pcgnn.hip), fused = "
+                     "device + the head and loss in csrc/pcgnn_head.hip (pcgnn_fused); same relations, batches and initial weights; "
+                     "fused_over_device = fused median / device median; big = the two device legs at DGraph-Fin's node count",
                 device=torch.cuda.get_device_name(0), batch=a.batch, feat=a.feat, emb=a.emb)
     total = a.steps + a.warmup
     # ---- 1. comparison size
@@ -103,15 +105,18 @@ def main():
     model_d, opt_d = build_model(graphs, feat, a.emb, 1)          # (construction runs check_relation once per relation)
     torch.cuda.synchronize()
     t_graphs = time.perf_counter() - t0
+    model_f, opt_f = build_model(graphs, feat, a.emb, 1, fused=True)
     model_s, opt_s = build_model(sets, feat, a.emb, 1)
     cmp_ = dict(nodes=a.nodes, entries=[int(len(ci)) for _, ci in rels], build_sets_s=t_sets, build_device_graphs_and_check_s=t_graphs)
     cmp_["device"] = time_steps(model_d, opt_d, batches, labels, a.warmup)
+    cmp_["fused"] = time_steps(model_f, opt_f, batches, labels, a.warmup)
     cmp_["set"] = time_steps(model_s, opt_s, batches, labels, a.warmup)
     cmp_["speedup"] = cmp_["set"]["median_ms"] / cmp_["device"]["median_ms"]
+    cmp_["fused_over_device"] = cmp_["fused"]["median_ms"] / cmp_["device"]["median_ms"]
     line["comparison"] = cmp_
     print("comparison", cmp_, flush=True)
-    del sets, model_s, opt_s, model_d, opt_d, graphs
-    # ---- 2. DGraph size, device path alone
+    del sets, model_s, opt_s, model_d, opt_d, model_f, opt_f, graphs
+    # ---- 2. DGraph size, the two device legs
     rels = [synth.make_graph_torch(a.big_nodes, a.big_entries, 21 + k, dev, max_degree=a.max_degree) for k in range(3)]
     feat = synth.make_features(a.big_nodes, a.feat, 4)
     labels = synth.make_labels(a.big_nodes, 15509.0 / 3700550.0, 4)
@@ -122,6 +127,10 @@ def main():
     torch.cuda.synchronize()
     big = dict(nodes=a.big_nodes, entries=[int(len(ci)) for _, ci in rels], build_device_graphs_and_check_s=time.perf_counter() - t0)
     big["device"] = time_steps(model_d, opt_d, batches, labels, a.warmup)
+    del model_d, opt_d
+    model_f, opt_f = build_model(graphs, feat, a.emb, 1, fused=True)
+    big["fused"] = time_steps(model_f, opt_f, batches, labels, a.warmup)
+    big["fused_over_device"] = big["fused"]["median_ms"] / big["device"]["median_ms"]
     line["big"] = big
     print("big", big, flush=True)
     print(json.dumps(line))
