@@ -248,6 +248,12 @@ SIGNATURES = {
     "ggad_recon_mb_supported": (c_int32, [_I, _I, _I]),
     "ggad_recon_mb_steps_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),
     "ggad_recon_mb_scores_f32": (c_int32, [_P, _P, _L, _I, _I, _P, _P, _P, _P]),
+    "ggad_tam_head_max_dim": (c_int32, []),
+    "ggad_tam_head_hub_len": (c_int32, []),
+    "ggad_tam_head_supported": (c_int32, [_I, _I]),
+    "ggad_tam_head_workspace_elems": (c_int64, [_I, _I, _I, _I]),
+    "ggad_tam_head_fwd_f32": (c_int32, [_P] * 6 + [_F, _I, _I, _P, _P, _I, _I] + [_P] * 6),
+    "ggad_tam_head_bwd_f32": (c_int32, [_P] * 6 + [_F, _I, _I, _P, _P, _I, _I] + [_P] * 7),
 }
 
 

@@ -9,6 +9,7 @@ order of numpy's random draws; HIP kernels for everything per epoch):
     graph_nsgt                        `utils_tam.py:222-240`   -> vectorised over rows, same draws from numpy's stream
     normalize_adj_tensor              `utils_tam.py:45-53`
     max_message / inference           `tam.py:113-146`         -> `AffinityFn` (HIP row-normalise, CSR SpMM, row dots)
+                                                               -> opt-in: `TamHeadFn` / `max_message_fused` (csrc/tam.hip)
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ from typing import List, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from ._lib import call, ptr
 from .fullgraph import FullGraphAdj, spmm
 
@@ -170,27 +172,137 @@ def max_message(emb: torch.Tensor, adj: FullGraphAdj, normal_label_idx) -> Tuple
     return -torch.sum(m.index_select(0, idx.reshape(-1).long())), m
 
 
+class TamHead:
+    """What the fused head (csrc/tam.hip) needs besides the embedding, built ONCE per (adj, normal_label_idx), outside any capture:
+    cnt (occurrences of every node in the index list -- `split_nodes` can list a node twice), K = len(list), the hub list of R and
+    the zeroed workspace.  The backward of the kernels gathers with R where the composed path multiplies by R^T, so R must be
+    symmetric in pattern and values: checked here on the host; an asymmetric R raises ValueError."""
+
+    def __init__(self, adj: FullGraphAdj, normal_label_idx):
+        R = adj.Rt
+        host = R.host
+        if host.shape[0] != host.shape[1] or abs(host - host.T).nnz != 0:
+            raise ValueError("the fused TAM head needs a symmetric raw adjacency (pattern and values); use the composed path "
+                             "(`max_message` / `train_cut(..., fused=False)`) for this graph")
+        lib = _lib.load()
+        dev = adj.dev
+        n = int(host.shape[0])
+        idx = normal_label_idx.detach().cpu().numpy() if isinstance(normal_label_idx, torch.Tensor) else np.asarray(normal_label_idx)
+        idx = idx.reshape(-1).astype(np.int64)
+        if len(idx) and (idx.min() < 0 or idx.max() >= n):
+            raise IndexError("normal_label_idx holds a node outside the graph")
+        self.adj, self.n = adj, n
+        self.k_total = float(len(idx))
+        self.cnt = torch.from_numpy(np.bincount(idx, minlength=n).astype(np.float32)).to(dev)
+        hub_len = int(lib.ggad_tam_head_hub_len())
+        deg = np.diff(host.indptr)
+        hubs = np.nonzero(deg > hub_len)[0]
+        pp = np.concatenate(([0], np.cumsum(-(-deg[hubs] // hub_len)))).astype(np.int32)
+        self.n_hub, self.n_pieces = int(len(hubs)), int(pp[-1])
+        self.hub_rows = torch.from_numpy(hubs.astype(np.int32)).to(dev) if self.n_hub else None
+        self.hub_pp = torch.from_numpy(pp).to(dev) if self.n_hub else None
+        self.r_inv = adj.r_inv_dev()
+        self._ws = {}
+
+    def workspace(self, h: int) -> torch.Tensor:
+        """The zeroed workspace for width h (created on first use: in an eager epoch, before any capture)."""
+        w = self._ws.get(h)
+        if w is None:
+            elems = int(_lib.load().ggad_tam_head_workspace_elems(self.n, h, self.n_hub, self.n_pieces))
+            w = self._ws[h] = torch.zeros(max(1, elems), dtype=torch.float32, device=self.adj.dev)
+        return w
+
+    def _args(self, emb):
+        R = self.adj.Rt
+        n, h = emb.shape
+        return (ptr(R.rowptr), ptr(R.col), ptr(R.val), ptr(emb), ptr(self.r_inv), ptr(self.cnt), self.k_total, n, h,
+                ptr(self.hub_rows), ptr(self.hub_pp), self.n_hub, self.n_pieces)
+
+
+class TamHeadFn(torch.autograd.Function):
+    """(loss, m, a) of the fused head: a = the raw affinity (`inference`), m its min-max normalisation, loss = -sum of m over the index
+    list.  Only the loss carries a gradient (to emb).  `want_m=False` skips the launch that writes m (m is then None)."""
+
+    @staticmethod
+    def forward(ctx, emb, head: TamHead, want_m: bool):
+        emb = emb.contiguous()
+        n, h = emb.shape
+        if n != head.n:
+            raise ValueError("embedding rows != nodes of the head's graph")
+        if not _lib.load().ggad_tam_head_supported(n, h):
+            raise ValueError(f"the fused TAM head takes 1 <= h <= {int(_lib.load().ggad_tam_head_max_dim())}, not h = {h}")
+        dev = emb.device
+        a = torch.empty(n, dtype=torch.float32, device=dev)
+        scal = torch.empty(8, dtype=torch.float32, device=dev)
+        m = torch.empty(n, dtype=torch.float32, device=dev) if want_m else None
+        inv = torch.empty(n, dtype=torch.float32, device=dev)
+        call("ggad_tam_head_fwd_f32", *head._args(emb), ptr(a), ptr(scal), ptr(m), ptr(inv), ptr(head.workspace(h)))
+        ctx.save_for_backward(emb, a, scal, inv)
+        ctx.head = head
+        loss = scal[0]
+        if want_m:
+            ctx.mark_non_differentiable(m, a)
+            return loss, m, a
+        ctx.mark_non_differentiable(a)
+        return loss, None, a
+
+    @staticmethod
+    def backward(ctx, g, _gm, _ga):
+        emb, a, scal, inv = ctx.saved_tensors
+        head = ctx.head
+        g = g.contiguous().float()
+        d_emb = torch.empty_like(emb)
+        call("ggad_tam_head_bwd_f32", *head._args(emb), ptr(a), ptr(scal), ptr(inv), ptr(g), ptr(d_emb),
+             ptr(head.workspace(emb.shape[1])))
+        return d_emb, None, None
+
+
+def tam_head(adj: FullGraphAdj, normal_label_idx) -> TamHead:
+    """The `TamHead` of (adj, normal_label_idx), cached on adj (keyed by the list's contents)."""
+    idx = normal_label_idx.detach().cpu().numpy() if isinstance(normal_label_idx, torch.Tensor) else np.asarray(normal_label_idx)
+    key = ("tam", idx.astype(np.int64).tobytes())
+    head = adj._head.get(key)
+    if head is None:
+        head = adj._head[key] = TamHead(adj, idx)
+    return head
+
+
+def max_message_fused(emb: torch.Tensor, adj: FullGraphAdj, normal_label_idx, head: "TamHead" = None, want_m: bool = True):
+    """`max_message` and `inference` in the fused kernels of csrc/tam.hip: (loss, m, a) with a = `inference(emb, adj)` and (loss, m)
+    = `max_message(emb, adj, normal_label_idx)`.  `head`: a `TamHead` built beforehand (`train_cut` does; otherwise it is looked up
+    on `adj`, which copies a device index list to the host).  R must be symmetric: ValueError otherwise."""
+    if head is None:
+        head = tam_head(adj, normal_label_idx)
+    return TamHeadFn.apply(emb.reshape(-1, emb.shape[-1]), head, bool(want_m))
+
+
 def normalize_score(ano_score: np.ndarray) -> np.ndarray:
     return (ano_score - np.min(ano_score)) / (np.max(ano_score) - np.min(ano_score))             # utils_tam.py:56-59
 
 
 def train_cut(model, optimiser, features: torch.Tensor, adj: FullGraphAdj, normal_label_idx, num_epoch: int, use_graph: bool = True,
-              log_every: int = 0):
+              log_every: int = 0, fused: bool = False):
     """The epoch loop of one truncation round (`tam.py:186-201`): forward, `max_message` loss, `inference`, backward, Adam step.
     The reference calls `zero_grad()` ONCE per round (`:182`), so the gradients of a round accumulate from epoch to epoch;
     the caller does the same (this function never clears them).  After two eager epochs the epoch (forward, both affinity
     passes, backward into the accumulating gradients, fused Adam) is captured into one hipGraph and replayed.
+    `fused=True`: the loss comes from `max_message_fused` and the round's message is that call's raw affinity; the second
+    `inference` pass (which recomputes the same numbers from the same embedding) is not run.
     Returns (losses [num_epoch] fp32 tensor on the device, message of the last epoch)."""
     dev = features.device
     idx = torch.as_tensor(np.asarray(normal_label_idx, dtype=np.int64), device=dev)
     losses = torch.zeros(max(1, int(num_epoch)), dtype=torch.float32, device=dev)
     state = {}
+    head = TamHead(adj, normal_label_idx) if fused else None
 
     def epoch():
         node_emb, feat1, feat2 = model.forward(features, adj)
-        loss, _ = max_message(node_emb[0], adj, idx)
-        with torch.no_grad():
-            state["message"] = inference(node_emb[0].detach(), adj)
+        if fused:
+            loss, _, state["message"] = max_message_fused(node_emb[0], adj, idx, head=head, want_m=False)
+        else:
+            loss, _ = max_message(node_emb[0], adj, idx)
+            with torch.no_grad():
+                state["message"] = inference(node_emb[0].detach(), adj)
         loss.backward()
         optimiser.step()
         return loss.detach()

@@ -1018,6 +1018,39 @@ int ggad_recon_mb_steps_f32(const float *x1, const float *target, const int32_t 
 int ggad_recon_mb_scores_f32(const float *x1, const float *target, int64_t n_rows, int32_t feat_dim, int32_t embed_dim, const float *w_enc,
                              const float *w_fc, float *out, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Affinity head and loss of the full-graph TAM comparison model (tam.hip; reference tam.py:113-146).  (rowptr, col, val): the CSR of
+ * the raw adjacency R over n nodes, which must be symmetric in pattern and values (the backward relies on it); emb: n x h, row-major;
+ * r_inv: 1 / column sum of R (inf -> 0); cnt[i]: how often node i occurs in the list of labelled normal nodes (float), k_total = sum cnt.
+ *
+ *   a_i = r_inv_i <e_hat_i, sum_j v_ij e_hat_j>,  e_hat_i = e_i / |e_i| (zero rows -> 0);   lo = min a, hi = max a;
+ *   loss = -(S - k_total lo) / (hi - lo),  S = sum_i cnt_i a_i;   m_i = (a_i - lo) / (hi - lo)   (no guard for hi = lo)
+ *
+ * ggad_tam_head_fwd_f32  writes a (n), inv (n: 1 / |e_i|), scal = (loss, lo, hi, n_lo, n_hi, S, 0, 0) with n_lo / n_hi the numbers of
+ *                        ties at lo / hi, and, if m is not NULL, m (n).  Three launches, four with m.
+ * ggad_tam_head_bwd_f32  d_emb (n x h, every element written) = *g * d loss / d emb from the a, scal and inv of the forward call on
+ *                        the same emb; ties at lo / hi share their gradient evenly like torch.min / torch.max.  Two launches.
+ * Rows with more than ggad_tam_head_hub_len() stored entries are hubs, summed in pieces of that many entries and the pieces added
+ * in piece order: hub_rows (n_hub, ascending) must list exactly those rows and hub_piece_ptr (n_hub + 1, starting at 0) the
+ * prefix sums of their piece counts ceil(len / hub_len), n_pieces its last value (both may be NULL with n_hub = 0).
+ * workspace: ggad_tam_head_workspace_elems(n, h, n_hub, n_pieces) floats, ZERO before the first call (it holds the ticket words,
+ * which the kernels leave zero).  No floating-point atomics: equal inputs give equal bits.
+ * ggad_tam_head_supported(n, h): n >= 1 and 1 <= h <= ggad_tam_head_max_dim() (256); any other h is GGAD_E_UNSUPPORTED and nothing
+ * is launched.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_tam_head_max_dim(void);
+int32_t ggad_tam_head_hub_len(void);
+int32_t ggad_tam_head_supported(int32_t n, int32_t h);
+int64_t ggad_tam_head_workspace_elems(int32_t n, int32_t h, int32_t n_hub, int32_t n_pieces);
+int ggad_tam_head_fwd_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *emb, const float *r_inv,
+                          const float *cnt, float k_total, int32_t n, int32_t h, const int32_t *hub_rows, const int32_t *hub_piece_ptr,
+                          int32_t n_hub, int32_t n_pieces, float *a, float *scal, float *m, float *inv, float *workspace,
+                          ggad_stream_t stream);
+int ggad_tam_head_bwd_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *emb, const float *r_inv,
+                          const float *cnt, float k_total, int32_t n, int32_t h, const int32_t *hub_rows, const int32_t *hub_piece_ptr,
+                          int32_t n_hub, int32_t n_pieces, const float *a, const float *scal, const float *inv, const float *g,
+                          float *d_emb, float *workspace, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,8 @@ Adam with `zero_grad()` once per round, then the AUROC / AP prints of `:204-232`
 PYTHONHASHSEED (its `random` / `numpy` / `torch` seeding is commented out, `:42-47`); here `--seed` seeds them so that a run can
 be repeated.  Adjacency, distances and truncated graphs are CSR; the GCN layers, both affinity passes, the backward and Adam
 run in the kernels of libggad_hip.so; after two eager epochs every epoch of a round is one replayed hipGraph.
-`--synthetic` / `--device` / `--quiet` / `--no_graph` / `--num_epoch` / `--lr` are additions.
+`--synthetic` / `--device` / `--quiet` / `--no_graph` / `--num_epoch` / `--lr` / `--fused_head` (the affinity head and its loss in
+the fused kernels of `csrc/tam.hip`, off by default) are additions.
 """
 import argparse
 import os
@@ -51,6 +52,7 @@ def parse():
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the training epoch")
+    p.add_argument("--fused_head", action="store_true", help="affinity head and loss in the fused kernels of csrc/tam.hip")
     a = p.parse_args()
     if a.lr is None:
         a.lr = 1e-5                                                    # tam.py:35
@@ -140,7 +142,8 @@ def main():
             torch.cuda.synchronize()
             t0 = time.time()
             losses, message_sum = T.train_cut(models[index], optimisers[index], feats, full, normal_label_idx, args.num_epoch,
-                                              use_graph=not args.no_graph, log_every=0 if args.quiet else 50)
+                                              use_graph=not args.no_graph, log_every=0 if args.quiet else 50,
+                                              fused=args.fused_head)
             torch.cuda.synchronize()
             epoch_times.append((time.time() - t0) / max(1, args.num_epoch))
             message_list.append(message_sum.detach().unsqueeze(0))
