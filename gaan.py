@@ -16,88 +16,35 @@ drawn from the CPU generator every epoch in the reference's order and copied int
 `--device_noise` (opt-in): the same stream continues on the device (ggad_amd.rng) and the draw opens the captured epoch; the host does
 nothing between replays.  `--synthetic` / `--device` / `--quiet` / `--no_graph` as in `aegis.py`.
 """
-import argparse
 import os
-import random
 import sys
 import time
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ggad_amd import synth  # noqa: E402
-from ggad_amd.fullgraph import FlatAdam, FullGraphAdj  # noqa: E402
-from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
+from ggad_amd.fullgraph import FlatAdam  # noqa: E402
+from ggad_amd.fullgraph_script import (DEVICE_NOISE_HELP, CapturedEpoch, NoiseFeed, init_process, load_graph, make_parser,  # noqa: E402
+                                       parse_with_defaults, prepare, print_captured, print_eval, print_median)
 from ggad_amd.model_gaan import Model  # noqa: E402
-from ggad_amd.utils import load_mat, normalize_adj, preprocess_features, split_nodes  # noqa: E402
-from run import SIZES  # noqa: E402
 
 LR = {"Amazon": 1e-3, "t_finance": 5e-4, "reddit": 1e-3, "photo": 1e-3, "elliptic": 5e-3}
 EPOCHS = {"reddit": 500, "t_finance": 1500, "Amazon": 800, "photo": 300, "elliptic": 600}
 
 
 def parse(argv=None):
-    p = argparse.ArgumentParser(description="")
-    p.add_argument("--dataset", type=str, default="Amazon")
-    p.add_argument("--lr", type=float)
-    p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--embedding_dim", type=int, default=300)
-    p.add_argument("--num_epoch", type=int)
-    p.add_argument("--drop_prob", type=float, default=0.0)
-    p.add_argument("--batch_size", type=int, default=300)
-    p.add_argument("--subgraph_size", type=int, default=4)
-    p.add_argument("--readout", type=str, default="avg")
-    p.add_argument("--auc_test_rounds", type=int, default=256)
-    p.add_argument("--negsamp_ratio", type=int, default=1)
-    p.add_argument("--synthetic", action="store_true", help="generate a graph of the dataset's size instead of loading ./dataset/*.mat")
-    p.add_argument("--device", type=int, default=0)
-    p.add_argument("--quiet", action="store_true")
-    p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the training epoch")
-    p.add_argument("--device_noise", action="store_true", help="draw the per-epoch noise on the device from torch's own CPU stream "
-                   "(ggad_amd.rng): the draw is the first node of the captured epoch; values agree with the host's to float32 rounding")
-    a = p.parse_args(argv)
-    if a.lr is None:
-        a.lr = LR.get(a.dataset)
-    if a.num_epoch is None:
-        a.num_epoch = EPOCHS.get(a.dataset)
-    if a.lr is None or a.num_epoch is None:
-        p.error("no default lr / num_epoch for dataset {!r}: pass --lr and --num_epoch".format(a.dataset))
-    return a
-
-
-def load(args):
-    """(adj, features, ano_label, all_idx, idx_test) as the reference's load_mat returns them."""
-    if args.synthetic or not os.path.exists("./dataset/{}.mat".format(args.dataset)):
-        if not args.synthetic:
-            print("./dataset/{}.mat not found: using a synthetic graph of the same size".format(args.dataset))
-        n, ne, f, rate = SIZES[args.dataset]
-        rowptr, col = synth.make_graph(n, ne, args.seed, kind="powerlaw", max_degree=max(64, n // 8), exact=True)
-        adj = synth.csr_to_scipy(rowptr, col, n)
-        feat = sp.lil_matrix(synth.make_features(n, f, args.seed))
-        ano = synth.make_labels(n, rate, args.seed)
-        all_idx, _, _, idx_test, _, _ = split_nodes(ano, args.dataset, verbose=not args.quiet)
-        return adj, feat, ano, all_idx, idx_test
-    adj, feat, _, all_idx, _, _, idx_test, ano, _, _, _, _ = load_mat(args.dataset)
-    return adj, feat, ano, all_idx, idx_test
+    return parse_with_defaults(make_parser("Amazon", device_noise_help=DEVICE_NOISE_HELP), argv, LR, EPOCHS)
 
 
 def setup(args, dev):
     """Graph, features, model and the two optimisers as gaan.py:74-105 builds them (CSR adjacency in HBM)."""
-    adj, features, ano_label, all_idx, idx_test = load(args)
-    if args.dataset in ["Amazon", "tf_finace", "reddit", "elliptic"]:                 # gaan.py:77 (typo kept: never T-Finance)
-        features = preprocess_features(features)
-    else:
-        features = np.asarray(features.todense())
-    nb_nodes, ft_size = features.shape
-    full = FullGraphAdj(normalize_adj(adj) + sp.eye(nb_nodes), adj + sp.eye(nb_nodes), dev)     # :89-91
-    feats = torch.FloatTensor(np.asarray(features, dtype=np.float32)[np.newaxis]).to(dev)
+    g = load_graph(args)
+    full, feats, ft_size = prepare(args, g.adj, g.feat, dev)
     model = Model(ft_size, args.embedding_dim, "prelu", args.negsamp_ratio, args.readout).to(dev)
     optimiser = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     optimiser_gen = FlatAdam(model.generator.parameters(), lr=args.lr)
-    return full, feats, model, optimiser, optimiser_gen, np.asarray(ano_label), list(all_idx), np.asarray(idx_test, dtype=np.int64)
+    return full, feats, model, optimiser, optimiser_gen, np.asarray(g.ano_label), list(g.all_idx), np.asarray(g.idx_test, dtype=np.int64)
 
 
 def make_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test):
@@ -115,81 +62,43 @@ def make_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test):
 def main():
     args = parse()
     print("Dataset: ", args.dataset)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    random.seed(args.seed)
-    if not torch.cuda.is_available():
-        sys.exit("gaan.py needs an MI355X: there is no CPU fallback")
-    torch.set_num_threads(min(8, os.cpu_count() or 1))
-    dev = torch.device("cuda", args.device)
-    torch.cuda.set_device(dev)      # the C-ABI launches on the CURRENT device's stream: it must be the one the tensors live on
+    dev = init_process(args, "gaan.py")
     full, feats, model, optimiser, optimiser_gen, ano_label, all_idx, idx_test = setup(args, dev)
     y_test_dev = torch.as_tensor(ano_label[idx_test].astype(np.int64), device=dev)
     n = full.n
-    epoch_fn = make_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test)
-    total_time, epoch_times = 0.0, []
-    graph, static, noise_buf = None, None, None
-    # --device_noise: the CPU generator continues on the device from here on; the draw opens every epoch (and the captured one), and
-    # the host generator gets the advanced state back when the loop ends
-    mt = None
-    if args.device_noise:
-        from ggad_amd.rng import DeviceMT
-        mt = DeviceMT.from_host(dev)
-        noise_buf = torch.zeros(n, model.noise_dim, device=dev)
-        model.noise_override = noise_buf
-        host_epoch = epoch_fn
+    # the forward's noise (model_gaan.py:311): one (n, noise_dim) draw per epoch, in the reference's order
+    noise = NoiseFeed(model, make_epoch(model, optimiser, optimiser_gen, feats, full, all_idx, idx_test), (n, model.noise_dim), dev,
+                      args.device_noise)
 
-        def epoch_fn():
-            mt.randn_(noise_buf)                                # this epoch's draw (model_gaan.py:311), in the reference's order
-            return host_epoch()
+    def before_capture():
+        noise.before_capture()
+        model.emb = None
+        optimiser.zero_grad()
+        optimiser_gen.zero_grad()
+
+    def after_capture():
+        noise.after_capture()
+        print_captured()
+
+    cap = CapturedEpoch(noise.epoch_fn, enabled=not args.no_graph, before_capture=before_capture, after_capture=after_capture)
+    total_time, epoch_times = 0.0, []
     try:
         for epoch in range(args.num_epoch):
             start_time = time.time()
             model.train()
-            if not args.no_graph and graph is None and epoch == 2:
-                if mt is None:
-                    noise_buf = torch.zeros(n, model.noise_dim, device=dev)
-                    model.noise_override = noise_buf
-                # nothing of the eager epochs' autograd graphs may survive into the capture
-                loss = score = None
-                model.emb = None
-                optimiser.zero_grad()
-                optimiser_gen.zero_grad()
-                import gc
-                gc.collect()
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    static = epoch_fn()
-                if mt is None:
-                    model.noise_override = None
-                print("training epoch captured as a hipGraph", flush=True)
-            if graph is not None:
-                if mt is None:
-                    noise_buf.copy_(torch.randn(n, model.noise_dim))       # this epoch's draw (model_gaan.py:311), in the reference's order
-                graph.replay()
-                loss, score = static
-            else:
-                loss, score = epoch_fn()
+            loss, score = cap.step(epoch, noise.before_replay)
             if epoch % 5 == 0:
                 print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss.item()))
                 model.eval()
-                sc = score.view(-1)
-                print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(sc, y_test_dev)))
-                print("Testing AP:", average_precision(sc, y_test_dev))
+                print_eval(args.dataset, score.view(-1), y_test_dev)
                 if not args.quiet:
                     print("Total time is", total_time)
             torch.cuda.synchronize()
             epoch_times.append(time.time() - start_time)
             total_time += epoch_times[-1]
     finally:
-        if mt is not None:
-            model.noise_override = None
-            mt.to_host()
-    if epoch_times:
-        med = float(np.median(epoch_times))
-        print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. one-off structure building / module load)".format(
-            med * 1e3, n / med, epoch_times[0] * 1e3))
+        noise.close()
+    print_median(epoch_times, n, "one-off structure building / module load")
 
 
 if __name__ == "__main__":

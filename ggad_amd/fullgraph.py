@@ -23,6 +23,10 @@ from . import _lib
 from ._lib import call, ptr, ptr_rows
 
 
+def _capturing(dev) -> bool:
+    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+
 def _dev_i32(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
 

@@ -1,0 +1,240 @@
+"""What the full-graph entry scripts (`run.py`, `ocgnn.py`, `anomalyDAE.py`, `aegis.py`, `gaan.py`, `dominant.py`, `tam.py`) share:
+the command line the reference's scripts have in common, the loader (a `.mat` file or a synthetic graph of the published size),
+feature / adjacency preparation, process setup, the capture of the training epoch as a hipGraph, the per-epoch noise feed of
+`gaan.py` / `aegis.py`, and the closing prints.  What differs between the scripts -- their defaults, print cadence and timed window
+-- stays in the scripts.
+"""
+from __future__ import annotations
+
+import argparse
+import gc
+import os
+import random
+import sys
+from typing import NamedTuple
+
+import numpy as np
+import scipy.sparse as sp
+import torch
+
+from . import synth
+from .fullgraph import FullGraphAdj
+from .metrics import average_precision, roc_auc
+from .utils import load_mat, normalize_adj, preprocess_features, split_nodes
+
+# published sizes (reference README.md:53-58): nodes, directed entries, features, anomaly rate
+SIZES = {"reddit": (10984, 168016, 64, 0.033), "Amazon": (11944, 4398392, 25, 0.069), "photo": (7535, 119043, 745, 0.092),
+         "t_finance": (39357, 21222543, 10, 0.046), "elliptic": (46564, 73248, 93, 0.098)}
+NO_GRAPH_HELP = "do not replay a captured hipGraph of the training epoch"
+DEVICE_NOISE_HELP = ("draw the per-epoch noise on the device from torch's own CPU stream (ggad_amd.rng): the draw is the first node "
+                     "of the captured epoch; values agree with the host's to float32 rounding")
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def make_parser(dataset, no_graph_help=NO_GRAPH_HELP, device_noise_help=None, sampling=True):
+    """The options the reference's full-graph scripts share, plus `--synthetic` / `--device` / `--quiet` / `--no_graph` and -- where
+    `device_noise_help` is given -- `--device_noise`.  `sampling`: `--batch_size` / `--subgraph_size`, which the reference's baselines
+    carry and its `run.py` does not.  A script adds its own options to the returned parser."""
+    p = argparse.ArgumentParser(description="")
+    p.add_argument("--dataset", type=str, default=dataset)
+    p.add_argument("--lr", type=float)
+    p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--embedding_dim", type=int, default=300)
+    p.add_argument("--num_epoch", type=int)
+    p.add_argument("--drop_prob", type=float, default=0.0)
+    if sampling:
+        p.add_argument("--batch_size", type=int, default=300)
+        p.add_argument("--subgraph_size", type=int, default=4)
+    p.add_argument("--readout", type=str, default="avg")
+    p.add_argument("--auc_test_rounds", type=int, default=256)
+    p.add_argument("--negsamp_ratio", type=int, default=1)
+    p.add_argument("--synthetic", action="store_true", help="generate a graph of the dataset's size instead of loading ./dataset/*.mat")
+    p.add_argument("--device", type=int, default=0)
+    p.add_argument("--quiet", action="store_true")
+    p.add_argument("--no_graph", action="store_true", help=no_graph_help)
+    if device_noise_help is not None:
+        p.add_argument("--device_noise", action="store_true", help=device_noise_help)
+    return p
+
+
+def parse_with_defaults(p, argv, lr, epochs, fallback=None):
+    """Parse, then let the script's per-dataset `lr` / `epochs` dictionaries fill what the command line left open.  A dataset outside
+    them is an error (the reference's scripts leave the value None there), unless `fallback` = (lr, num_epoch) says what it gets."""
+    a = p.parse_args(argv)
+    fb_lr, fb_epochs = fallback or (None, None)
+    if a.lr is None:
+        a.lr = lr.get(a.dataset, fb_lr)
+    if a.num_epoch is None:
+        a.num_epoch = epochs.get(a.dataset, fb_epochs)
+    if a.lr is None or a.num_epoch is None:
+        p.error("no default lr / num_epoch for dataset {!r}: pass --lr and --num_epoch".format(a.dataset))
+    return a
+
+
+# ------------------------------------------------------------------------------------------------ data
+class Graph(NamedTuple):
+    """What the reference's `load_mat` returns, less what no script reads."""
+    adj: object
+    feat: object
+    ano_label: object
+    all_idx: list
+    idx_train: list
+    idx_val: list
+    idx_test: list
+    normal_idx: list
+    abn_idx: list
+
+
+def synthetic_graph(dataset, seed):
+    """(adj, feat, ano_label) of a power-law graph with the dataset's published size, from the seed alone."""
+    n, ne, f, rate = SIZES[dataset]
+    rowptr, col = synth.make_graph(n, ne, seed, kind="powerlaw", max_degree=max(64, n // 8), exact=True)
+    adj = synth.csr_to_scipy(rowptr, col, n)
+    feat = sp.lil_matrix(synth.make_features(n, f, seed))
+    return adj, feat, synth.make_labels(n, rate, seed)
+
+
+def load_graph(args) -> Graph:
+    """`./dataset/<dataset>.mat`, or (`--synthetic`, or no such file) a synthetic graph of the same size; the split draws from
+    python's `random` stream as the reference's `load_mat` does."""
+    if args.synthetic or not os.path.exists("./dataset/{}.mat".format(args.dataset)):
+        if not args.synthetic:
+            print("./dataset/{}.mat not found: using a synthetic graph of the same size".format(args.dataset))
+        adj, feat, ano = synthetic_graph(args.dataset, args.seed)
+        return Graph(adj, feat, ano, *split_nodes(ano, args.dataset, verbose=not args.quiet))
+    adj, feat, _, all_idx, idx_train, idx_val, idx_test, ano, _, _, normal_idx, abn_idx = load_mat(args.dataset)
+    return Graph(adj, feat, ano, all_idx, idx_train, idx_val, idx_test, normal_idx, abn_idx)
+
+
+def prepare(args, adj, feat, dev):
+    """(full, feats, ft_size): the CSR adjacency pair in HBM (normalize_adj(A) + I and A + I, run.py:98-101) and the (1, N, F)
+    feature tensor, row-normalised for the datasets the reference's scripts list."""
+    # run.py:87, and the same list in ocgnn.py:124, anomalyDAE.py:80, aegis.py:77, gaan.py:77, dominant.py:84 (typo kept: never T-Finance)
+    if args.dataset in ["Amazon", "tf_finace", "reddit", "elliptic"]:
+        features = preprocess_features(feat)
+    else:
+        features = np.asarray(feat.todense())
+    nb_nodes, ft_size = features.shape
+    full = FullGraphAdj(normalize_adj(adj) + sp.eye(nb_nodes), adj + sp.eye(nb_nodes), dev)
+    feats = torch.FloatTensor(np.asarray(features, dtype=np.float32)[np.newaxis]).to(dev)
+    return full, feats, ft_size
+
+
+def init_process(args, script_name, why="there is no CPU fallback", host_threads=8):
+    """Seed numpy, torch (`torch.manual_seed` seeds every CUDA generator too) and `random`, insist on a GPU, make `--device` current;
+    returns the device."""
+    np.random.seed(args.seed)
+    torch.manual_seed(args.seed)
+    random.seed(args.seed)
+    if not torch.cuda.is_available():
+        sys.exit("{} needs an MI355X: {}".format(script_name, why))
+    if host_threads:
+        # the host-side tensor work left is tiny (a noise draw per epoch at most): torch's default of one intra-op thread per core
+        # (128 on the MI355X box) turns it into a 1-90 ms lottery on a loaded host
+        torch.set_num_threads(min(host_threads, os.cpu_count() or 1))
+    dev = torch.device("cuda", args.device)
+    torch.cuda.set_device(dev)      # the C-ABI launches on the CURRENT device's stream: it must be the one the tensors live on
+    return dev
+
+
+# ------------------------------------------------------------------------------------------------ the captured epoch
+def capture(epoch_fn, before=None):
+    """Capture one call of `epoch_fn` into a hipGraph: (graph, what `epoch_fn` returned -- the static outputs every replay refills).
+    The capture itself executes nothing.  Nothing of earlier eager epochs' autograd graphs may survive into it (their AccumulateGrad
+    nodes are bound to the default stream): `epoch_fn` returns detached tensors, `before` is where the caller zeroes its optimisers'
+    gradients and drops whatever else holds a `grad_fn`, and the collection here frees what only a reference cycle kept alive."""
+    if before is not None:
+        before()
+    gc.collect()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static = epoch_fn()
+    return graph, static
+
+
+class CapturedEpoch:
+    """A training loop's epoch: eager (allocations, plan caches, Adam state) until epoch `at`, captured there -- if `enabled` and
+    `gate()` holds -- and replayed from that epoch on."""
+
+    def __init__(self, epoch_fn, *, enabled=True, at=2, before_capture=None, after_capture=None, gate=None):
+        self.epoch_fn, self.enabled, self.at = epoch_fn, enabled, at
+        self.before_capture, self.after_capture, self.gate = before_capture, after_capture, gate
+        self.graph = self.static = None
+
+    @property
+    def captured(self) -> bool:
+        return self.graph is not None
+
+    def step(self, epoch, before_replay=None):
+        """Run epoch `epoch`; returns what `epoch_fn` returns (once captured: the static outputs).  `before_replay` runs ahead of every
+        replay, the capturing epoch's included: the place to refill a buffer the captured epoch reads."""
+        if self.enabled and self.graph is None and epoch == self.at and (self.gate is None or self.gate()):
+            self.graph, self.static = capture(self.epoch_fn, self.before_capture)
+            if self.after_capture is not None:
+                self.after_capture()
+        if self.graph is None:
+            return self.epoch_fn()
+        if before_replay is not None:
+            before_replay()
+        self.graph.replay()
+        return self.static
+
+
+class NoiseFeed:
+    """The `shape` standard-normal draw that the forward of `gaan.py` / `aegis.py` makes every epoch, for a captured epoch.  On the
+    host (the default): eager epochs draw inside the model; the captured epoch reads `model.noise_override`, a buffer installed for
+    the capture, which `before_replay` refills from the CPU generator in the reference's order.  `device_noise`: the CPU generator
+    continues on the device (ggad_amd.rng) from here on, `epoch_fn` opens with the draw, and `close` hands the advanced state back."""
+
+    def __init__(self, model, epoch_fn, shape, dev, device_noise):
+        self.model, self.epoch_fn, self.shape, self.dev = model, epoch_fn, shape, dev
+        self.mt = self.buf = None
+        if device_noise:
+            from .rng import DeviceMT
+            self.mt = mt = DeviceMT.from_host(dev)
+            self.buf = buf = model.noise_override = torch.zeros(*shape, device=dev)
+
+            def with_draw():
+                mt.randn_(buf)
+                return epoch_fn()
+            self.epoch_fn = with_draw
+
+    def before_capture(self):
+        if self.mt is None:
+            self.buf = self.model.noise_override = torch.zeros(*self.shape, device=self.dev)
+
+    def after_capture(self):
+        if self.mt is None:
+            self.model.noise_override = None
+
+    def before_replay(self):
+        if self.mt is None:
+            self.buf.copy_(torch.randn(*self.shape))
+
+    def close(self):
+        if self.mt is not None:
+            self.model.noise_override = None
+            self.mt.to_host()
+
+
+# ------------------------------------------------------------------------------------------------ prints
+def print_captured():
+    print("training epoch captured as a hipGraph", flush=True)
+
+
+def print_eval(dataset, scores, y):
+    """The reference's two evaluation lines (= sklearn's roc_auc_score / average_precision_score); returns (auc, ap)."""
+    auc = roc_auc(scores, y)
+    print("Testing {} AUC:{:.4f}".format(dataset, auc))
+    ap = average_precision(scores, y)
+    print("Testing AP:", ap)
+    return auc, ap
+
+
+def print_median(epoch_times, n, note):
+    if epoch_times:
+        med = float(np.median(epoch_times))
+        print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. {})".format(
+            med * 1e3, n / med, epoch_times[0] * 1e3, note))

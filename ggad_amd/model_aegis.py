@@ -37,17 +37,13 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import FullGraphAdj, GcnLayerFn, _ticket_word, gemm, spmm
+from .fullgraph import FullGraphAdj, GcnLayerFn, _capturing, _ticket_word, gemm, spmm
 from .graphsage_aegis import MLP
 from .model import GCN, AvgReadout, MaxReadout, MinReadout, WSReadout, as_full_adj
 from .model import Discriminator
 from .model_anomalydae import LinearBiasFn
 
 ACT_RELU, ACT_SIGMOID = 0, 1
-
-
-def _capturing(dev) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
 def _bn_parts(bn: nn.BatchNorm1d):

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import FullGraphAdj, _dev_f32, _dev_i32, gemm
+from .fullgraph import FullGraphAdj, _capturing, _dev_f32, _dev_i32, gemm
 from .gat import GATConv, colsum
 from .model import AvgReadout, Discriminator, MaxReadout, MinReadout, WSReadout, as_full_adj
 
@@ -45,10 +45,6 @@ class LinearBiasFn(torch.autograd.Function):
             dz = g
         dx = gemm(dz, weight, False, False) if ctx.needs_input_grad[0] else None
         return dx, gemm(dz, x, True, False), colsum(dz), None
-
-
-def _capturing(dev) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
 def row_structs(adj: FullGraphAdj, idx) -> dict:

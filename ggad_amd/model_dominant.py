@@ -32,13 +32,9 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import Csr, FullGraphAdj, _ticket_word, gemm, spmm
+from .fullgraph import Csr, FullGraphAdj, _capturing, _ticket_word, gemm, spmm
 from .model import AvgReadout, Discriminator, MaxReadout, MinReadout, WSReadout, as_full_adj
 from .model_anomalydae import LinearBiasFn
-
-
-def _capturing(dev) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
 # ------------------------------------------------------------------------------------------------ the GCN (PyG 2.1 restated)

@@ -31,15 +31,11 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import FullGraphAdj, _dev_i32, _ticket_word, gemm
+from .fullgraph import FullGraphAdj, _capturing, _dev_i32, _ticket_word, gemm
 from .graphsage_aegis import MLP
 from .model import AvgReadout, Discriminator, MaxReadout, MinReadout, WSReadout, as_full_adj
 from .model_aegis import ACT_RELU, BnActFn, _LossAeFn, bn_forward, loss_rows
 from .model_anomalydae import LinearBiasFn
-
-
-def _capturing(dev) -> bool:
-    return dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
 
 
 def edge_list(a_hat, idx) -> tuple:

@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr
 from .fullgraph import FullGraphAdj, spmm
+from .fullgraph_script import capture
 
 
 def split_nodes(ano_labels: np.ndarray, rng=_pyrandom) -> Tuple[List[int], np.ndarray]:
@@ -315,14 +316,13 @@ def train_cut(model, optimiser, features: torch.Tensor, adj: FullGraphAdj, norma
             print("mean_loss is {}".format(losses[e].item()))
     left = int(num_epoch) - n_eager
     if left > 0:
-        import gc
-        gc.collect()
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
         static_loss = torch.zeros((), dtype=torch.float32, device=dev)
-        with torch.cuda.graph(graph):
+
+        def captured_epoch():
             static_loss.copy_(epoch())
-            static_msg = state["message"]
+            return state["message"]
+
+        graph, static_msg = capture(captured_epoch)
         # the capture does not execute: every remaining epoch is one replay
         for e in range(n_eager, int(num_epoch)):
             graph.replay()

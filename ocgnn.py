@@ -6,80 +6,40 @@ elliptic 500 / photo 600), seeding, prints and evaluation cadence (AUROC / AP on
 `ocgnn.py`; the two GCN layers, the one-class loss, the backward and Adam run in the kernels of libggad_hip.so on the CSR
 adjacency.  `--synthetic` / `--device` / `--quiet` / `--no_graph` as in `run.py`.
 """
-import argparse
 import os
-import random
 import sys
 import time
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ggad_amd.fullgraph import FlatAdam, FullGraphAdj  # noqa: E402
-from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
+from ggad_amd.fullgraph import FlatAdam  # noqa: E402
+from ggad_amd.fullgraph_script import (CapturedEpoch, init_process, load_graph, make_parser, parse_with_defaults, prepare,  # noqa: E402
+                                       print_eval, print_median)
 from ggad_amd.model_ocgnn import Model, ocgnn_loss  # noqa: E402
-from ggad_amd.utils import normalize_adj, preprocess_features  # noqa: E402
-from run import load  # noqa: E402
 
 LR = {"t_finance": 5e-4}
 EPOCHS = {"reddit": 500, "t_finance": 1500, "Amazon": 800, "elliptic": 500, "photo": 600}
 
 
-def parse():
-    p = argparse.ArgumentParser(description="")
-    p.add_argument("--dataset", type=str, default="t_finance")
-    p.add_argument("--lr", type=float)
-    p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--embedding_dim", type=int, default=300)
-    p.add_argument("--num_epoch", type=int)
-    p.add_argument("--drop_prob", type=float, default=0.0)
-    p.add_argument("--batch_size", type=int, default=300)
-    p.add_argument("--subgraph_size", type=int, default=4)
-    p.add_argument("--readout", type=str, default="avg")
-    p.add_argument("--auc_test_rounds", type=int, default=256)
-    p.add_argument("--negsamp_ratio", type=int, default=1)
-    p.add_argument("--synthetic", action="store_true", help="generate a graph of the dataset's size instead of loading ./dataset/*.mat")
-    p.add_argument("--device", type=int, default=0)
-    p.add_argument("--quiet", action="store_true")
-    p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the training epoch")
-    a = p.parse_args()
-    if a.lr is None:
-        a.lr = LR.get(a.dataset, 1e-3)
-    if a.num_epoch is None:
-        a.num_epoch = EPOCHS.get(a.dataset, 500)
-    return a
+def parse(argv=None):
+    return parse_with_defaults(make_parser("t_finance"), argv, LR, EPOCHS, fallback=(1e-3, 500))
 
 
 def main():
     args = parse()
     print("Dataset: ", args.dataset)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    torch.cuda.manual_seed_all(args.seed)
-    random.seed(args.seed)
-    if not torch.cuda.is_available():
-        sys.exit("ocgnn.py needs an MI355X: there is no CPU fallback")
-    torch.set_num_threads(min(8, os.cpu_count() or 1))
-    dev = torch.device("cuda", args.device)
-    torch.cuda.set_device(dev)      # the C-ABI launches on the CURRENT device's stream: it must be the one the tensors live on
-    adj, features, ano_label, idx_test, normal_label_idx, abnormal_label_idx = load(args)
-    if args.dataset in ["Amazon", "tf_finace", "reddit", "elliptic"]:                 # ocgnn.py:124 (same typo as run.py)
-        features = preprocess_features(features)
-    else:
-        features = np.asarray(features.todense())
-    nb_nodes, ft_size = features.shape
-    full = FullGraphAdj(normalize_adj(adj) + sp.eye(nb_nodes), adj + sp.eye(nb_nodes), dev)     # ocgnn.py:135-137, CSR in HBM
-    feats = torch.FloatTensor(np.asarray(features, dtype=np.float32)[np.newaxis]).to(dev)
+    dev = init_process(args, "ocgnn.py")
+    g = load_graph(args)
+    full, feats, ft_size = prepare(args, g.adj, g.feat, dev)
     model = Model(ft_size, args.embedding_dim, "prelu", args.negsamp_ratio, args.readout).to(dev)
     optimiser = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
-    normal_dev = torch.as_tensor(np.asarray(normal_label_idx, dtype=np.int64), device=dev)
-    idx_test_dev = torch.as_tensor(np.asarray(idx_test, dtype=np.int64), device=dev)
-    y_test_dev = torch.as_tensor(np.asarray(ano_label)[np.asarray(idx_test, dtype=np.int64)].astype(np.int64), device=dev)
+    idx_test = np.asarray(g.idx_test, dtype=np.int64)
+    normal_dev = torch.as_tensor(np.asarray(g.normal_idx, dtype=np.int64), device=dev)
+    idx_test_dev = torch.as_tensor(idx_test, device=dev)
+    y_test_dev = torch.as_tensor(np.asarray(g.ano_label)[idx_test].astype(np.int64), device=dev)
     total_time, epoch_times = 0.0, []
-    graph, static = None, None
 
     def train_epoch():
         optimiser.zero_grad()
@@ -87,40 +47,26 @@ def main():
         loss, _ = ocgnn_loss(emb[0], normal_dev)                # torch.squeeze(emb)[normal_label_idx]   ocgnn.py:180-184
         loss.backward()
         optimiser.step()
-        return loss
+        return loss.detach()
 
+    # a host-bound epoch is captured (see run.py)
+    cap = CapturedEpoch(train_epoch, enabled=not args.no_graph, before_capture=optimiser.zero_grad,
+                        gate=lambda: epoch_times[1] < float(os.environ.get("GGAD_CAPTURE_BELOW_S", "20e-3")))
     for epoch in range(args.num_epoch):
         start_time = time.time()
         model.train()
-        if not args.no_graph and graph is None and epoch == 2 and epoch_times[1] < float(os.environ.get("GGAD_CAPTURE_BELOW_S", "20e-3")):     # host-bound epoch: capture it (see run.py)
-            loss = None
-            optimiser.zero_grad()
-            import gc
-            gc.collect()
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static = train_epoch()
-        if graph is not None:
-            graph.replay()
-            loss = static
-        else:
-            loss = train_epoch()
+        loss = cap.step(epoch)
         torch.cuda.synchronize()
         if epoch % 5 == 0:
             print("Epoch:", "%04d" % epoch, "train_loss=", "{:.5f}".format(loss.item()))
             model.eval()
             with torch.no_grad():
                 _, score = ocgnn_loss(model(feats, full)[0])
-            scores = score[idx_test_dev]
-            print("Testing {} AUC:{:.4f}".format(args.dataset, roc_auc(scores, y_test_dev)))
-            print("Testing AP:", average_precision(scores, y_test_dev))
+            print_eval(args.dataset, score[idx_test_dev], y_test_dev)
             print("Total time is", total_time)
         epoch_times.append(time.time() - start_time)         # like the reference, the window includes the evaluation (ocgnn.py:210-211)
         total_time += epoch_times[-1]
-    med = float(np.median(epoch_times))
-    print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. one-off plan building / module load)".format(
-        med * 1e3, nb_nodes / med, epoch_times[0] * 1e3))
+    print_median(epoch_times, full.n, "one-off plan building / module load")
 
 
 if __name__ == "__main__":

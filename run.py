@@ -10,98 +10,48 @@ instead of the reference's dense N x N tensors).  Extra flags: `--synthetic` (no
 builds a graph of the dataset's published size from the seed), `--device`, `--device_noise` (opt-in: the N(mean, var)
 noise is drawn on the device from torch's own CPU stream, `ggad_amd/rng.py`; the draw opens the captured epoch).
 """
-import argparse
 import os
-import random
 import sys
 import time
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ggad_amd import synth  # noqa: E402
-from ggad_amd.fullgraph import FlatAdam, FullGraphAdj, ggad_loss  # noqa: E402
+from ggad_amd.fullgraph import FlatAdam, ggad_loss  # noqa: E402
+from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, init_process, load_graph, make_parser, parse_with_defaults,  # noqa: E402,F401
+                                       prepare, print_captured, print_eval, print_median)
 from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
 from ggad_amd.model import Model  # noqa: E402
-from ggad_amd.utils import load_mat, normalize_adj, preprocess_features, split_nodes  # noqa: E402
 
-# published sizes (reference README.md:53-58): nodes, directed entries, features, anomaly rate
-SIZES = {"reddit": (10984, 168016, 64, 0.033), "Amazon": (11944, 4398392, 25, 0.069), "photo": (7535, 119043, 745, 0.092),
-         "t_finance": (39357, 21222543, 10, 0.046), "elliptic": (46564, 73248, 93, 0.098)}
 EPOCHS = {"photo": 100, "elliptic": 150, "reddit": 300, "t_finance": 500, "Amazon": 800}
 
 
-def parse():
-    p = argparse.ArgumentParser(description="")
-    p.add_argument("--dataset", type=str, default="reddit")
-    p.add_argument("--lr", type=float)
-    p.add_argument("--weight_decay", type=float, default=0.0)
-    p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--embedding_dim", type=int, default=300)
-    p.add_argument("--num_epoch", type=int)
-    p.add_argument("--drop_prob", type=float, default=0.0)
-    p.add_argument("--readout", type=str, default="avg")
-    p.add_argument("--auc_test_rounds", type=int, default=256)
-    p.add_argument("--negsamp_ratio", type=int, default=1)
+def parse(argv=None):
+    p = make_parser("reddit", sampling=False,
+                    no_graph_help="launch every kernel of every epoch from Python instead of replaying a captured hipGraph of the "
+                                  "training epoch (same kernels, same order, same results)",
+                    device_noise_help="draw the N(mean, var) noise on the device from torch's own CPU stream (ggad_amd.rng): the draw "
+                                      "becomes the first node of the captured epoch; values agree with the host's to float32 rounding")
     p.add_argument("--mean", type=float, default=0.0)
     p.add_argument("--var", type=float, default=0.0)
-    p.add_argument("--synthetic", action="store_true", help="generate a graph of the dataset's size instead of loading ./dataset/*.mat")
-    p.add_argument("--device", type=int, default=0)
-    p.add_argument("--quiet", action="store_true")
-    p.add_argument("--no_graph", action="store_true", help="launch every kernel of every epoch from Python instead of replaying a "
-                   "captured hipGraph of the training epoch (same kernels, same order, same results)")
-    p.add_argument("--device_noise", action="store_true", help="draw the N(mean, var) noise on the device from torch's own CPU stream "
-                   "(ggad_amd.rng): the draw becomes the first node of the captured epoch; values agree with the host's to float32 "
-                   "rounding")
-    a = p.parse_args()
-    if a.lr is None:
-        a.lr = 1e-3
-    if a.num_epoch is None:
-        a.num_epoch = EPOCHS.get(a.dataset, 100)
+    a = parse_with_defaults(p, argv, {}, EPOCHS, fallback=(1e-3, 100))
     a.mean, a.var = (0.02, 0.01) if a.dataset in ["reddit", "photo"] else (0.0, 0.0)      # run.py:61-66 (CLI values overwritten)
     return a
 
 
 def load(args):
-    if args.synthetic or not os.path.exists("./dataset/{}.mat".format(args.dataset)):
-        if not args.synthetic:
-            print("./dataset/{}.mat not found: using a synthetic graph of the same size".format(args.dataset))
-        n, ne, f, rate = SIZES[args.dataset]
-        rowptr, col = synth.make_graph(n, ne, args.seed, kind="powerlaw", max_degree=max(64, n // 8), exact=True)
-        adj = synth.csr_to_scipy(rowptr, col, n)
-        feat = sp.lil_matrix(synth.make_features(n, f, args.seed))
-        ano = synth.make_labels(n, rate, args.seed)
-        all_idx, idx_train, idx_val, idx_test, normal_idx, abn_idx = split_nodes(ano, args.dataset, verbose=not args.quiet)
-        return adj, feat, ano, idx_test, normal_idx, abn_idx
-    adj, feat, labels, all_idx, idx_train, idx_val, idx_test, ano, _, _, normal_idx, abn_idx = load_mat(args.dataset)
-    return adj, feat, ano, idx_test, normal_idx, abn_idx
+    g = load_graph(args)
+    return g.adj, g.feat, g.ano_label, g.idx_test, g.normal_idx, g.abn_idx
 
 
 def main():
     args = parse()
     print("Dataset: ", args.dataset)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    torch.cuda.manual_seed_all(args.seed)
-    random.seed(args.seed)
-    if not torch.cuda.is_available():
-        sys.exit("run.py needs an MI355X: the GGAD hot path has no CPU fallback")
-    # the only host-side tensor work left is the N(mean, var) noise (<= 844 x 300 floats per epoch): torch's default of one
-    # intra-op thread per core (128 on the MI355X box) turns it into a 1-90 ms lottery on a loaded host
-    torch.set_num_threads(min(8, os.cpu_count() or 1))
-    dev = torch.device("cuda", args.device)
-    torch.cuda.set_device(dev)      # the C-ABI launches on the CURRENT device's stream: it must be the one the tensors live on
+    dev = init_process(args, "run.py", why="the GGAD hot path has no CPU fallback")
     adj, features, ano_label, idx_test, normal_label_idx, abnormal_label_idx = load(args)
-    if args.dataset in ["Amazon", "tf_finace", "reddit", "elliptic"]:                 # run.py:87 (typo kept: never T-Finance)
-        features = preprocess_features(features)
-    else:
-        features = np.asarray(features.todense())
-    nb_nodes, ft_size = features.shape
     print(adj.sum())
-    full = FullGraphAdj(normalize_adj(adj) + sp.eye(nb_nodes), adj + sp.eye(nb_nodes), dev)     # run.py:98-101, CSR in HBM
-    feats = torch.FloatTensor(np.asarray(features, dtype=np.float32)[np.newaxis]).to(dev)
+    full, feats, ft_size = prepare(args, adj, features, dev)
     model = Model(ft_size, args.embedding_dim, "prelu", args.negsamp_ratio, args.readout).to(dev)
     fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label)
 
@@ -143,7 +93,7 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
     # (Reddit: 1.3 ms of kernels per 2.3 ms epoch).  After two eager epochs (allocations, plan caches, Adam state) the epoch
     # is captured once and replayed; the N(mean, var) noise is still drawn from the CPU generator every epoch, exactly as
     # the reference does (model.py:143), and copied into the static buffer the captured epoch reads.
-    graph, static, noise_buf, pending_noise = None, None, None, None
+    noise_buf, pending_noise = None, None
     n_abn = len(abnormal_label_idx)
 
     one = torch.ones((), dtype=torch.float32, device=dev)
@@ -159,46 +109,38 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
         out = ggad_loss(emb, logits, emb_con, emb_abnormal, full, ls, 0.7)
         out[0].backward(gradient=one)            # (d loss / d loss = 1 from a kept tensor: autograd would fill a new one every epoch)
         optimiser.step()
-        return out
+        return tuple(t.detach() for t in out)
 
+    def before_capture():
+        nonlocal noise_buf
+        if device_mt is None:
+            noise_buf = model.noise_override = torch.zeros(1, n_abn, args.embedding_dim, device=dev)
+        optimiser.zero_grad()
+
+    def after_capture():
+        model.noise_override = None
+        if device_mt is not None:
+            print_captured()
+
+    def host_draw():
+        nonlocal pending_noise
+        noise = pending_noise
+        if noise is None:
+            noise = torch.randn(1, n_abn, args.embedding_dim) * args.var + args.mean  # same draw as Model.forward
+        pending_noise = None
+        noise_buf.copy_(noise)
+
+    # (where launch gaps matter: an eager epoch under 20 ms -- T-Finance size, 5.3 ms of kernels, still gains 2.5 %)
+    cap = CapturedEpoch(train_epoch, enabled=not args.no_graph, before_capture=before_capture, after_capture=after_capture,
+                        gate=lambda: epoch_times[1] < float(os.environ.get("GGAD_CAPTURE_BELOW_S", "20e-3")))
     for epoch in range(args.num_epoch):
         start_time = time.time()
         model.train()
-        # (where launch gaps matter: an eager epoch under 20 ms -- T-Finance size, 5.3 ms of kernels, still gains 2.5 %)
-        if not args.no_graph and graph is None and epoch == 2 and epoch_times[1] < float(os.environ.get("GGAD_CAPTURE_BELOW_S", "20e-3")):
-            if device_mt is None:
-                noise_buf = torch.zeros(1, n_abn, args.embedding_dim, device=dev)
-                model.noise_override = noise_buf
-            # nothing of the eager epochs' autograd graphs may survive into the capture (their AccumulateGrad nodes are
-            # bound to the default stream)
-            loss = loss_margin = loss_bce = loss_rec = None
-            optimiser.zero_grad()
-            import gc
-            gc.collect()
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static = train_epoch()
-            model.noise_override = None
-            if device_mt is not None:
-                print("training epoch captured as a hipGraph", flush=True)
-            # the capture itself does not execute: fall through and replay it for this epoch
-        if graph is not None and device_mt is not None:
-            graph.replay()              # the draw is the first node of the captured epoch: nothing to do on the host
-            loss, loss_margin, loss_bce, loss_rec = static
-        elif graph is not None:
-            noise = pending_noise
-            if noise is None:
-                noise = torch.randn(1, n_abn, args.embedding_dim) * args.var + args.mean  # same draw as Model.forward
-            pending_noise = None
-            noise_buf.copy_(noise)
-            graph.replay()
-            loss, loss_margin, loss_bce, loss_rec = static
-            # the next epoch's draw while the GPU runs this one -- unless an evaluation (which draws too) comes in between
-            if epoch % 10 != 0 and epoch + 1 < args.num_epoch:
-                pending_noise = torch.randn(1, n_abn, args.embedding_dim) * args.var + args.mean
-        else:
-            loss, loss_margin, loss_bce, loss_rec = train_epoch()
+        # (under device noise the draw is the first node of the captured epoch: nothing to do on the host)
+        loss, loss_margin, loss_bce, loss_rec = cap.step(epoch, host_draw if device_mt is None else None)
+        # the next epoch's draw while the GPU runs this one -- unless an evaluation (which draws too) comes in between
+        if cap.captured and device_mt is None and epoch % 10 != 0 and epoch + 1 < args.num_epoch:
+            pending_noise = torch.randn(1, n_abn, args.embedding_dim) * args.var + args.mean
         torch.cuda.synchronize()
         epoch_times.append(time.time() - start_time)
         total_time += epoch_times[-1]
@@ -217,10 +159,7 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
             with torch.no_grad():
                 _, _, logits_eval, _, _ = model(feats, full, abnormal_label_idx, normal_label_idx, False, args)
             scores = logits_eval[0, idx_test_dev, 0]                          # stays in HBM: device sort + fp64 prefix sums
-            auc = roc_auc(scores, y_test_dev)                                 # = sklearn roc_auc_score      run.py:236
-            print("Testing {} AUC:{:.4f}".format(args.dataset, auc))
-            ap = average_precision(scores, y_test_dev)                        # = average_precision_score    run.py:238
-            print("Testing AP:", ap)
+            auc, ap = print_eval(args.dataset, scores, y_test_dev)            # run.py:236-238
             if history is not None:
                 history.setdefault("eval", []).append([epoch, auc, ap])
     if history is not None:
@@ -230,11 +169,9 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
         scores = logits_eval[0, idx_test_dev, 0]
         history["final_logits"] = logits_eval[0, :, 0].cpu().numpy()
         history["final_auc"], history["final_ap"] = roc_auc(scores, y_test_dev), average_precision(scores, y_test_dev)
-        history["captured"] = graph is not None
+        history["captured"] = cap.captured
     print("nodes/s (training window, run.py:146->214): {:.1f}".format(nb_nodes * args.num_epoch / total_time))
-    med = float(np.median(epoch_times))
-    print("median epoch {:.3f} ms -> {:.1f} nodes/s (first epoch {:.1f} ms incl. one-off plan building / module load)".format(
-        med * 1e3, nb_nodes / med, epoch_times[0] * 1e3))
+    print_median(epoch_times, nb_nodes, "one-off plan building / module load")
 
 
 if __name__ == "__main__":

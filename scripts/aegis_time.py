@@ -17,6 +17,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import aegis  # noqa: E402
+from ggad_amd.fullgraph_script import capture  # noqa: E402
 
 
 def time_size(dataset, epochs):
@@ -37,10 +38,7 @@ def time_size(dataset, epochs):
     opt_ae.zero_grad()
     opt.zero_grad()
     opt_gen.zero_grad()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        main_epoch()
+    graph, _ = capture(main_epoch)
     model.noise_override = None
     times = []
     for _ in range(epochs):

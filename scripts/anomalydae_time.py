@@ -62,15 +62,13 @@ def floor_s(flops, sig):
 
 def time_gpu(dataset, steps, warmup, dev):
     import anomalyDAE
+    from ggad_amd.fullgraph_script import capture
     from ggad_amd.model_anomalydae import recon_score
     full, feats, model, opt, ano, idx_test, normal_idx = _setup(dataset, dev)
     ep = anomalyDAE.make_epoch(model, opt, feats, full, normal_idx)
     for _ in range(2):
         ep()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        static = ep()
+    g, static = capture(ep)
     for _ in range(warmup):
         g.replay()
     torch.cuda.synchronize()

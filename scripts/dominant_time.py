@@ -18,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import dominant  # noqa: E402
+from ggad_amd.fullgraph_script import capture  # noqa: E402
 from ggad_amd.model_dominant import fused_supported  # noqa: E402
 
 
@@ -34,11 +35,7 @@ def time_path(dataset, epochs, wide):
     torch.cuda.synchronize()
     first = (time.perf_counter() - t0) * 1e3
     epoch_fn()
-    opt.zero_grad()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        epoch_fn()
+    graph, _ = capture(epoch_fn, before=opt.zero_grad)
     times = []
     for _ in range(epochs):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

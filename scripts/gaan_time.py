@@ -18,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import gaan  # noqa: E402
+from ggad_amd.fullgraph_script import capture  # noqa: E402
 from ggad_amd.model_gaan import edge_structs  # noqa: E402
 
 
@@ -35,10 +36,7 @@ def time_size(dataset, epochs):
     model.emb = None
     opt.zero_grad()
     opt_gen.zero_grad()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        epoch_fn()
+    graph, _ = capture(epoch_fn)
     model.noise_override = None
     times, draws = [], []
     for _ in range(epochs):

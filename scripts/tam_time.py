@@ -24,10 +24,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from ggad_amd import synth  # noqa: E402
 from ggad_amd import tam_utils as T  # noqa: E402
 from ggad_amd.fullgraph import FlatAdam, FullGraphAdj  # noqa: E402
-from ggad_amd.fullgraph_bench import SIZES  # noqa: E402
+from ggad_amd.fullgraph_script import capture, synthetic_graph  # noqa: E402
 from ggad_amd.model_tam import Model  # noqa: E402
 from ggad_amd.utils import preprocess_features  # noqa: E402
 
@@ -37,11 +36,8 @@ def setup(dataset, dev, h, seed=0):
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)
-    n, ne, f, rate = SIZES[dataset]
-    rowptr, col = synth.make_graph(n, ne, seed, kind="powerlaw", max_degree=max(64, n // 8), exact=True)
-    adj = synth.csr_to_scipy(rowptr, col, n)
-    feat = sp.lil_matrix(synth.make_features(n, f, seed))
-    ano = synth.make_labels(n, rate, seed)
+    adj, feat, ano = synthetic_graph(dataset, seed)
+    n = adj.shape[0]
     normal, _ = T.split_nodes(ano)
     features = np.asarray(preprocess_features(feat)) if dataset == "Amazon" else np.asarray(feat.todense())
     raw = (adj + sp.eye(n)).tocsr()
@@ -54,14 +50,10 @@ def setup(dataset, dev, h, seed=0):
     return full, feats, copy.deepcopy(model.state_dict()), normal, features.shape[1], raw
 
 
-def capture(fn, warm=2):
+def warm_capture(fn, warm=2):
     for _ in range(warm):
         fn()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        fn()
-    return graph
+    return capture(fn)[0]
 
 
 def replay_ms(graph, reps):
@@ -133,8 +125,8 @@ def time_size(dataset, epochs, h):
             return msg
 
         tag = "fused" if fused else "composed"
-        graphs[("epoch", tag)] = capture(epoch)
-        graphs[("head", tag)] = capture(head_only)
+        graphs[("epoch", tag)] = warm_capture(epoch)
+        graphs[("head", tag)] = warm_capture(head_only)
         keep.append((model, opt, emb))
     times = {k: [] for k in graphs}
     blocks = 2

@@ -13,7 +13,6 @@ the fused kernels of `csrc/tam.hip`, off by default) are additions.
 """
 import argparse
 import os
-import random
 import sys
 import time
 
@@ -22,10 +21,9 @@ import scipy.sparse as sp
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ggad_amd import synth  # noqa: E402
 from ggad_amd import tam_utils as T  # noqa: E402
 from ggad_amd.fullgraph import FlatAdam, FullGraphAdj  # noqa: E402
-from ggad_amd.fullgraph_bench import SIZES  # noqa: E402
+from ggad_amd.fullgraph_script import init_process, synthetic_graph  # noqa: E402
 from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
 from ggad_amd.model_tam import Model  # noqa: E402
 from ggad_amd.utils import preprocess_features  # noqa: E402
@@ -65,11 +63,7 @@ def load(args):
     if args.synthetic or not os.path.exists("./data/{}.mat".format(args.dataset)):
         if not args.synthetic:
             print("./data/{}.mat not found: using a synthetic graph of the same size".format(args.dataset))
-        n, ne, f, rate = SIZES[args.dataset]
-        rowptr, col = synth.make_graph(n, ne, args.seed, kind="powerlaw", max_degree=max(64, n // 8), exact=True)
-        adj = synth.csr_to_scipy(rowptr, col, n)
-        feat = sp.lil_matrix(synth.make_features(n, f, args.seed))
-        ano = synth.make_labels(n, rate, args.seed)
+        adj, feat, ano = synthetic_graph(args.dataset, args.seed)
         normal, idx_test = T.split_nodes(ano)
         return adj, feat, ano, normal, idx_test
     adj, feat, ano, _, _, normal, idx_test = T.load_mat(args.dataset)
@@ -80,13 +74,7 @@ def main():
     args = parse()
     print("Dataset: ", args.dataset)
     os.environ["PYTHONHASHSEED"] = str(args.seed)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    if not torch.cuda.is_available():
-        sys.exit("tam.py needs an MI355X: there is no CPU fallback")
-    dev = torch.device("cuda", args.device)
-    torch.cuda.set_device(dev)
+    dev = init_process(args, "tam.py", host_threads=None)             # (the reference leaves torch's thread count alone)
     adj, features, ano_label, normal_label_idx, idx_test = load(args)
     if args.dataset in ["Amazon", "YelpChi", "Amazon-all", "YelpChi-all", "elliptic_no_isolate"]:       # tam.py:55-57
         features = np.asarray(preprocess_features(features))
