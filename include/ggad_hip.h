@@ -628,7 +628,7 @@ int ggad_spmm_sliced_f32(const int32_t *col, const float *val, const int32_t *se
  * its entries are then part of the stream): out[i] = act(row_scale[i] * sum_j col_scale[j] X[j] + diag[i] X[i] + bias).
  * A workgroup of ggad_spmm_panel_waves() waves owns (32-float column slice, row block) and walks the operand in panels of
  * ggad_spmm_panel_rows() source rows staged in LDS; the entries are a host-built stream of 16-bit panel row indices (layout at
- * k_spmm_panel in fullgraph.hip; built by ggad_amd/fullgraph.py::Csr.panel_plan): wg_tab[n_wg][2] = (slice, block) or (-1, -1),
+ * k_spmm_panel in fullgraph.hip; built by ggad_amd/csr.py::Csr.panel_plan): wg_tab[n_wg][2] = (slice, block) or (-1, -1),
  * dir[(block * waves + wave) * n_chunks + chunk][8] = {first oct of the wave's tiles of that panel, 8 x 16-bit counts of the QUADS
  * (4 steps) walked per round: whole octs, then half of the last one}, stream = [oct][8 lane groups][8 steps] uint16, two
  * per uint32, + 8 spare octs, row_tab[(block * waves + wave) * rounds + round][8] = output row (| GGAD_SPMM_PANEL_WIDE) or -1.  xs_workspace as for ggad_spmm_sliced_f32.
@@ -666,7 +666,7 @@ int ggad_spmm_panel_f32(const int32_t *wg_tab, int32_t n_wg, const uint32_t *dir
  * passing through a RING of ggad_spmm_ring_slots() LDS slots of ggad_spmm_ring_slot_rows() source rows: during phase j the
  * ggad_spmm_ring_walkers() walker waves of a workgroup read the slots j .. j + ggad_spmm_ring_window() - 1 while one more wave
  * stages slot j + slots - 1 by LDS-DMA; one barrier per phase.  The entries are a host-built per-walker list of QUADS (4 steps x 8
- * lane groups x 16-bit LDS row index; layout at k_spmm_ring in fullgraph.hip, built by ggad_amd/fullgraph.py::Csr.ring_plan):
+ * lane groups x 16-bit LDS row index; layout at k_spmm_ring in fullgraph.hip, built by ggad_amd/csr.py::Csr.ring_plan):
  * wg_tab[n_wg][2] = (slice, block) or (-1, -1); wave_sb[block * walkers + wave][2] = {first super-block (4 quads), count};
  * idx = [super-block][2 halves][8 lane groups][2 quads][4 steps] uint16 (+ one spare super-block); ctl = one byte per quad:
  * bits 0..5 = 4 * accumulator slot (< ggad_spmm_ring_rounds()), bit 6 = last quad of its phase (every walker flags every phase);
