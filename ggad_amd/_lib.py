@@ -40,6 +40,7 @@ SIGNATURES = {
     "ggad_max_feat_dim": (c_int32, []),
     "ggad_mb_wide_max_embed_dim": (c_int32, []),
     "ggad_mb_wide_supported": (c_int32, [c_int32, c_int32]),
+    "ggad_mb_supported": (c_int32, [c_int32, c_int32]),
     "ggad_scan_workspace_elems": (c_int64, [_L]),
     "ggad_exclusive_scan_i32": (c_int32, [_P, _P, _L, _P, _P]),
     "ggad_mb_chunk_len": (c_int32, []),

@@ -174,7 +174,8 @@ __global__ void __launch_bounds__(256) k_expand(const int32_t *__restrict__ rowp
 // 1-hop aggregate.  Scalar phase (lane = entry): c_j, owner, weight 1 / (sqrt r_i sqrt c_j) (graphsage.py:314-318); for
 // train plans with the LDS-counting 2-hop stage also the owner's CSR row start / degree, the storage of its pair counts in
 // pc[] (one atomic per WAVE on the cursor: the layout of pc[] is free, only sequential per owner) and the per-node list of
-// owner entries (atomicExch on node_head: order of the list is irrelevant).  Vector phase: the wave gathers the feature
+// owner entries (atomicExch on node_head: order of the list is irrelevant; only when k_build_groups follows, ldsw == 1: it reads the
+// lists and puts node_head back to zero).  Vector phase: the wave gathers the feature
 // rows of each of its four pieces, rpi = 64 / F rows per load instruction, and leaves the piece's partial sum in
 // part1[piece] -- or directly in x1 when the row is that single piece.
 __global__ void __launch_bounds__(256) k_gather1c(const float *__restrict__ feat, int F, int stride,
@@ -218,7 +219,7 @@ __global__ void __launch_bounds__(256) k_gather1c(const float *__restrict__ feat
       if (own == e) {
         rp = rowptr[j];
         deg = rowptr[j + 1] - rp;
-        own_next[e] = atomicExch(&node_head[j], e + 1);
+        if (ldsw == 1) own_next[e] = atomicExch(&node_head[j], e + 1);      // (ldsw == 2: k_gather2_w takes no node lists)
       }
       own_rp[e] = rp;
       own_deg[e] = deg;
@@ -446,6 +447,8 @@ int ggad_int_hop1(const ggad_mb_plan *P, const ggad_plan_view &V, int ldsw, int 
   if (V.n_chunks == 0) return GGAD_OK;
   const unsigned eb = (unsigned)((V.n_chunks + 15) / 16);       // 16 pieces (4 waves x 4) per workgroup
   const int skip = P->xcd_skip >= 0 && P->xcd_skip < 8 ? P->xcd_skip : -1;
+  // the per-node owner lists are read, and node_head cleared, by k_build_groups alone: the condition of ggad_int_ldsw_hop2
+  if (ldsw && !(P->node_major && P->feat_dim <= 64)) ldsw = 2;
   k_expand<<<dim3(ggad_skip_grid(eb, skip)), dim3(256), 0, st>>>(P->rowptr, P->col, V.nodes, V.row_slot, V.ent_ptr, V.ck_rc, V.ck_e0, V.n_chunks,
                                             P->n_nodes, P->ent_col, P->ent_slot, P->ent_row, P->cnt1, P->own1, P->counters, skip);
   k_gather1c<<<dim3(ggad_skip_grid(eb, skip)), dim3(256), 0, st>>>(P->feat, P->feat_dim, P->feat_stride, V.row_slot, V.ent_ptr, V.row_ck_ptr, V.ck_rc,

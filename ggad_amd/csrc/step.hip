@@ -857,7 +857,8 @@ __global__ void __launch_bounds__(256) k_loss_pos_ck(const float *__restrict__ p
 bool dims_ok(int D, int F) { return D >= 1 && D <= GGAD_MAX_D && F >= 1 && (size_t)(4 * F * D + 512) * 4 <= 150 * 1024; }
 // D > GGAD_MAX_D: the entry points forward to the wide chain (step_wide.hip)
 bool is_wide(int D) { return D > GGAD_MAX_D; }
-bool dims_any(int D, int F) { return is_wide(D) ? ggad_int_wide_ok(D, F) : dims_ok(D, F); }
+// what any chain takes (parameter block, Adam): chain 3 runs the wide kernels at D <= GGAD_MAX_D too, on shapes dims_ok refuses
+bool dims_any(int D, int F) { return ggad_int_wide_ok(D, F) || dims_ok(D, F); }
 
 }  // namespace
 
@@ -866,6 +867,7 @@ extern "C" {
 int ggad_max_embed_dim(void) { return GGAD_MAX_D; }
 int ggad_max_feat_dim(void) { return GGAD_MAX_F; }
 int ggad_mb_bwd_parts(void) { return BWD_PARTS; }
+int ggad_mb_supported(int32_t D, int32_t F) { return dims_ok(D, F) && F <= GGAD_MAX_F ? 1 : 0; }
 
 int64_t ggad_mb_param_count(int32_t D, int32_t F) { return (int64_t)D + (int64_t)D * F + (int64_t)D * D; }
 int64_t ggad_mb_param_block_elems(int32_t D, int32_t F) { return ggad_mb_param_count(D, F) + (int64_t)F * D + (int64_t)D * D; }

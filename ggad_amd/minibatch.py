@@ -442,6 +442,15 @@ class MiniBatchEngine:
             raise ValueError(f"emb_size {self.D} / feature width {self.F} is not supported by the HIP step kernels: the wide chain "
                              f"takes 1 <= emb_size <= {int(self.lib.ggad_mb_wide_max_embed_dim())} and "
                              f"1 <= features <= {int(self.lib.ggad_max_feat_dim())}")
+        if not self.wide and not self.lib.ggad_mb_supported(self.D, self.F):
+            # refused here, before any allocation or launch, and not as an error code in the middle of the first chunk
+            f_max = max((f for f in range(1, int(self.lib.ggad_max_feat_dim()) + 1) if self.lib.ggad_mb_supported(self.D, f)), default=0)
+            other = "chain=3 (the wide chain) takes this shape" if self.lib.ggad_mb_wide_supported(self.D, self.F) \
+                else "the wide chain (chain=3) does not take it either"
+            raise ValueError(f"feature width {self.F} at emb_size {self.D} is not supported by chain {self.chain} of the HIP step kernels: "
+                             f"at emb_size {self.D} it takes 1 <= features <= {f_max} (four features x emb_size fp32 partial sums in "
+                             f"LDS: (4 * features * emb_size + 512) floats <= 150 KB, and features <= "
+                             f"{int(self.lib.ggad_max_feat_dim())}); {other}")
         self.dev = torch.device(device)
         self.lr, self.wd = float(lr), float(weight_decay)
         self.n_train = int(self.lib.ggad_mb_param_count(self.D, self.F))

@@ -53,6 +53,10 @@ int ggad_max_feat_dim(void);
  * ggad_mb_train_chunk_xcd return GGAD_E_INVALID at D > 64 and launch nothing. */
 int ggad_mb_wide_max_embed_dim(void);
 int ggad_mb_wide_supported(int32_t D, int32_t F);
+/* ggad_mb_supported(D, F) != 0  <=>  the one-lane-per-channel chain (chains 0 and 2) takes the shape: 1 <= D <= 64,
+ * 1 <= F <= ggad_max_feat_dim() and (4 F D + 512) floats of LDS <= 150 KB, that is F D <= 9472.  A shape it refuses at D <= 64
+ * and F <= 1024 trains on the wide chain (chain 3). */
+int ggad_mb_supported(int32_t D, int32_t F);
 
 /* ------------------------------------------------------------------------------------
  * Generic device primitives

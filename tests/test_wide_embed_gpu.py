@@ -25,6 +25,7 @@ from conftest import load_golden
 from ggad_amd import synth
 from oracle import ggad_oracle as O
 import step_reference as R
+import width_reference as WR
 
 pytestmark = pytest.mark.gpu
 
@@ -307,32 +308,6 @@ def _branch_device(f):
     return DeviceGraph(rowptr, col, DEV), torch.from_numpy(_branch_feat(f)).to(DEV)
 
 
-def _split(x, d, f):
-    return x[:d], x[d:d + d * f], x[d + d * f:d + d * f + d * d]
-
-
-def _check_step(eng, before, ref_g, what):
-    """tests/step_reference.py::check_step with the engine's own feature width (the helper's is fixed at 17)."""
-    p0, m0, v0, t0 = before
-    d, f, nt = eng.D, eng.F, eng.n_train
-    params = eng.params.cpu().numpy()
-    R.check_moments(eng.exp_avg.cpu().numpy(), eng.exp_avg_sq.cpu().numpy(), *R.moment_bounds(ref_g, p0, m0, v0), what)
-    p_ref, _, _ = O.adam_f64(p0, m0, v0, ref_g, t0 + 1, R.LR, R.WD)
-    gp = ref_g + R.WD * p0
-    for name, a, r, q, s in zip(("w", "W", "fc"), _split(params[:nt].astype(np.float64), d, f), _split(p_ref, d, f),
-                                _split(p0, d, f), _split(gp, d, f)):
-        diff = np.abs(a - r)
-        sure = np.abs(s) > max(1e-6 * np.abs(s).max(), 1e-6)
-        if sure.any():
-            assert diff[sure].max() < 3e-6, f"{what}: {name} off by {diff[sure].max():.3e} after the Adam step"
-        assert diff.max() <= 2.1 * np.abs(r - q).max() + 1e-12, f"{what}: {name} off by {diff.max():.3e} (more than one opposite step)"
-    W = params[d:d + d * f].reshape(d, f)
-    fc = params[d + d * f:nt].reshape(d, d)
-    assert np.array_equal(params[nt:nt + f * d].reshape(f, d), W.T), f"{what}: Wt is not W^T"
-    assert np.array_equal(params[nt + f * d:nt + f * d + d * d].reshape(d, d), fc.T), f"{what}: fcT is not fc^T"
-    assert int(eng.step_counter.item()) == t0 + 1, what
-
-
 BRANCH_CASES = [(d, 17) for d in (65, 128, 129, 192, 255, 256)] + [(96, 1), (200, 9), (256, 70), (130, 128)]
 
 
@@ -379,7 +354,7 @@ def test_wide_step_against_float64(d, f):
                 R.check_losses(got_l, ref_loss, what)
                 R.check_grads(got_g, g, what)
                 eng.adam_step()
-                _check_step(eng, (p0, m0, v0, t0), g, what)
+                WR.check_step(eng, (p0, m0, v0, t0), g, what)
             except AssertionError as exc:
                 failures.append(str(exc))
     assert not failures, "\n".join(failures)
