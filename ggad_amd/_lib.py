@@ -234,11 +234,14 @@ SIGNATURES = {
     "ggad_pcgnn_head_parts": (c_int32, []),
     "ggad_pcgnn_head_workspace_elems": (c_int64, [_I, _I]),
     "ggad_pcgnn_head_f32": (c_int32, [_P] * 9 + [_I, _I] + [_P] * 13),
+    "ggad_sage_sched_epoch": (c_int32, [_P, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _I, _I, _I, _P, _L, _P]),
     "ggad_sage_supported": (c_int32, [_I, _I, _I]),
     "ggad_sage_bwd_parts": (c_int32, []),
     "ggad_sage_bwd_workspace_elems": (c_int64, [_I, _I]),
     "ggad_sage_fwd_f32": (c_int32, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ggad_sage_bwd_f32": (c_int32, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "ggad_sage_sum_adam_f32": (c_int32, [_P, _P, _I, _I, _I] + [_P] * 8 + [_F, _F, _P, _P]),
+    "ggad_sage_epoch_f32": (c_int32, [_P, _I, _P, _L, _P, _I, _I, _I, _I] + [_P] * 8 + [_F, _F] + [_P] * 8),
     "ggad_aegis_mb_max_rows": (c_int32, []),
     "ggad_aegis_mb_supported": (c_int32, [_I, _I, _I]),
     "ggad_aegis_mb_scratch_elems": (c_int64, [_L]),

@@ -41,6 +41,17 @@ __device__ __forceinline__ int wave_sum_i(int v) {
   return v;
 }
 
+// k_adam_multi's update of one element (fullgraph.hip), expression for expression: torch's Adam with L2 weight decay, betas .9 / .999,
+// eps 1e-8; sc0 = lr / (1 - .9^t) and sc1 = sqrt(1 - .999^t) are formed in double by the caller.  Shared by the kernels that apply
+// Adam inside a fused step (recon_mb.hip, sage.hip).
+__device__ __forceinline__ void ggad_adam_elem(float &pi, float &mi, float &vi, float g, float wd, float sc0, float sc1) {
+  float gi = fmaf(wd, pi, g);
+  mi = fmaf(gi - mi, 0.1f, mi);
+  vi = fmaf(0.001f * gi, gi, vi * 0.999f);
+  const float denom = sqrtf(vi) / sc1 + 1e-8f;
+  pi = pi - sc0 * (mi / denom);
+}
+
 // first index in sorted a[lo,hi) with a[idx] >= key
 __device__ __forceinline__ int lower_bound_i32(const int32_t *__restrict__ a, int lo, int hi, int key) {
   while (lo < hi) {

@@ -83,15 +83,6 @@ __device__ __forceinline__ void rm_fwd_block(const float *__restrict__ x1, const
   for (int j = 0; j < RM_RB; ++j) r[j] = (col && j < nv) ? (rr[j] < 0.f ? 0.f : rr[j]) : 0.f;
 }
 
-// k_adam_multi's update of one element (fullgraph.hip), expression for expression
-__device__ __forceinline__ void rm_adam(float &pi, float &mi, float &vi, float g, float wd, float sc0, float sc1) {
-  float gi = fmaf(wd, pi, g);
-  mi = fmaf(gi - mi, 0.1f, mi);
-  vi = fmaf(0.001f * gi, gi, vi * 0.999f);
-  const float denom = sqrtf(vi) / sc1 + 1e-8f;
-  pi = pi - sc0 * (mi / denom);
-}
-
 __global__ __launch_bounds__(RM_THREADS) void k_rm_steps(const float *__restrict__ x1, const float *__restrict__ tg,
                                                           const int32_t *__restrict__ batch_ptr, int n_steps, int total_rows,
                                                           int max_rows, int F, float *__restrict__ W, float *__restrict__ Wfc,
@@ -211,7 +202,7 @@ __global__ __launch_bounds__(RM_THREADS) void k_rm_steps(const float *__restrict
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (last && gF) gF[own * RM_D + q4 + j] = acc[j];
-        rm_adam(pf[j], mf[j], vf[j], acc[j], wd, sc0, sc1);
+        ggad_adam_elem(pf[j], mf[j], vf[j], acc[j], wd, sc0, sc1);
       }
     }
     __syncthreads();
@@ -257,7 +248,7 @@ __global__ __launch_bounds__(RM_THREADS) void k_rm_steps(const float *__restrict
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (last && gW) gW[(q4 + j) * F + own] = acc[j];
-        rm_adam(pw[j], mw[j], vw[j], acc[j], wd, sc0, sc1);
+        ggad_adam_elem(pw[j], mw[j], vw[j], acc[j], wd, sc0, sc1);
         s_wt[own * RM_D + q4 + j] = pw[j];
         s_wfc[own * RM_FC_LD + q4 + j] = pf[j];
       }

@@ -7,6 +7,10 @@
 // columns of `combined` in four interleaved chains; the 64 lanes of a wave in butterfly order; a thread over the rows of its row
 // range, then the SG_BWD_PARTS ranges in range order), so equal inputs give equal bits.  Entries of `nbr` at or past cnt_i are never
 // read.  At B ~ 200 both entry points are bound by launch and gather latency, not by bandwidth or arithmetic.
+// The epoch path (ggad_sage_epoch_f32, sage_epoch.py) enqueues the steps of an epoch on one stream from a table sampled in one
+// host call (sampler.cpp, ggad_sage_sched_epoch): per step k_sage_fwd, k_sage_bwd_part and k_sage_sum_adam, which adds the partial
+// gradients in range order, applies Adam in place (weights, moments, step counters) and stores the step's mean loss -- one
+// workgroup, the same orders of summation as k_sage_bwd_sum and k_sage_loss, so the bits equal the step path's.
 #include "common.h"
 
 #define SG_THREADS 256
@@ -17,6 +21,8 @@
 #define SG_BWD_PARTS 8          // row ranges of the backward; their partial sums are added in range order
 #define SG_BWD_ROWS 32          // rows of a range staged in LDS at a time
 #define SG_BWD_TILE (4 * SG_THREADS)      // entries of dW_enc per workgroup, four per thread
+#define SG_SA_THREADS 1024      // the one workgroup of k_sage_sum_adam
+#define SG_SA_PER ((SG_MAX_D * 2 * SG_MAX_F + 2 * SG_MAX_D + SG_SA_THREADS - 1) / SG_SA_THREADS)      // parameters per thread at most (9)
 
 namespace {
 
@@ -178,6 +184,63 @@ __global__ __launch_bounds__(SG_THREADS) void k_sage_bwd_sum(const float *__rest
   if (o < n_out) d_enc[o] = t; else d_cls[o - n_out] = t;
 }
 
+// The tail of a step in ONE workgroup (at most 64 * 128 + 128 = 8,320 parameters: up to nine per thread): thread t owns the entries
+// t, t + 1024, ... of [d_enc | d_cls].  Each is the sum of its SG_BWD_PARTS partials in range order (k_sage_bwd_sum), then
+// k_adam_multi's update in place (ggad_adam_elem; the bias corrections of the two tensors are formed in double by four threads of
+// four waves side by side).  Wave 0 adds the row losses as k_sage_loss does.  Both step counters are read before the first barrier
+// and advanced by thread 0 behind the second: no other workgroup exists that could still want the old values.
+__global__ __launch_bounds__(SG_SA_THREADS) void k_sage_sum_adam(const float *__restrict__ ws, const float *__restrict__ rowloss, int B,
+                                                                 int n_out, int n_cls, float *__restrict__ Wenc,
+                                                                 float *__restrict__ mEnc, float *__restrict__ vEnc,
+                                                                 int32_t *__restrict__ ctrEnc, float *__restrict__ Wcls,
+                                                                 float *__restrict__ mCls, float *__restrict__ vCls,
+                                                                 int32_t *__restrict__ ctrCls, float lr, float wd,
+                                                                 float *__restrict__ loss) {
+  __shared__ float sc[4];                                      // enc: lr / (1 - .9^t), sqrt(1 - .999^t); then cls
+  const int tid = threadIdx.x, stride = n_out + n_cls;
+  if ((tid & (GGAD_WAVE - 1)) == 0 && tid < 4 * GGAD_WAVE) {
+    const int which = tid / GGAD_WAVE;
+    const double t = (double)((which < 2 ? *ctrEnc : *ctrCls) + 1);
+    sc[which] = (which & 1) ? (float)sqrt(1.0 - pow(0.999, t)) : (float)((double)lr / (1.0 - pow(0.9, t)));
+  }
+  float g[SG_SA_PER];
+#pragma unroll
+  for (int u = 0; u < SG_SA_PER; ++u) {                        // the gradients do not need the corrections: summed while they form
+    const int o = tid + u * SG_SA_THREADS;
+    float t = 0.f;
+    if (o < stride) {
+      t = ws[o];
+#pragma unroll
+      for (int p = 1; p < SG_BWD_PARTS; ++p) t += ws[(size_t)p * stride + o];
+    }
+    g[u] = t;
+  }
+  if (tid < GGAD_WAVE) {                                       // k_sage_loss: lane l adds rows l, l + 64, ...; the butterfly
+    float t = 0.f;
+    for (int i = tid; i < B; i += GGAD_WAVE) t += rowloss[i];
+    t = wave_sum(t);
+    if (tid == 0) loss[0] = t / (float)B;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < SG_SA_PER; ++u) {
+    const int o = tid + u * SG_SA_THREADS;
+    if (o < stride) {
+      const bool enc = o < n_out;
+      const int i = enc ? o : o - n_out;
+      float *__restrict__ p = enc ? Wenc : Wcls, *__restrict__ m = enc ? mEnc : mCls, *__restrict__ v = enc ? vEnc : vCls;
+      float pi = p[i], mi = m[i], vi = v[i];
+      ggad_adam_elem(pi, mi, vi, g[u], wd, enc ? sc[0] : sc[2], enc ? sc[1] : sc[3]);
+      p[i] = pi; m[i] = mi; v[i] = vi;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    *ctrEnc += 1;
+    *ctrCls += 1;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -218,6 +281,45 @@ int ggad_sage_bwd_f32(const float *combined, const float *emb, const float *dsco
   k_sage_bwd_sum<<<dim3((unsigned)((n_out + n_cls + SG_THREADS - 1) / SG_THREADS)), dim3(SG_THREADS), 0, st>>>(ws, n_out, n_cls, d_enc,
                                                                                                            d_cls);
   GGAD_CHECK_LAUNCH("sage_bwd");
+  return GGAD_OK;
+}
+
+int ggad_sage_sum_adam_f32(const float *ws, const float *rowloss, int32_t n_batch, int32_t feat_dim, int32_t embed_dim, float *w_enc,
+                           float *m_enc, float *v_enc, int32_t *ctr_enc, float *w_cls, float *m_cls, float *v_cls, int32_t *ctr_cls,
+                           float lr, float weight_decay, float *loss_out, ggad_stream_t stream) {
+  GGAD_REQUIRE(ws && rowloss && w_enc && m_enc && v_enc && ctr_enc && w_cls && m_cls && v_cls && ctr_cls && loss_out && n_batch >= 1);
+  if (!ggad_sage_supported(feat_dim, embed_dim, 2)) return GGAD_E_UNSUPPORTED;
+  k_sage_sum_adam<<<dim3(1), dim3(SG_SA_THREADS), 0, as_stream(stream)>>>(ws, rowloss, n_batch, embed_dim * 2 * feat_dim, 2 * embed_dim,
+                                                                          w_enc, m_enc, v_enc, ctr_enc, w_cls, m_cls, v_cls, ctr_cls, lr,
+                                                                          weight_decay, loss_out);
+  GGAD_CHECK_LAUNCH("sage_sum_adam");
+  return GGAD_OK;
+}
+
+int ggad_sage_epoch_f32(const float *feat, int32_t feat_dim, const int32_t *table, int64_t stride, const int32_t *len_host,
+                        int32_t n_steps, int32_t b_max, int32_t k, int32_t embed_dim, float *w_enc, float *m_enc, float *v_enc,
+                        int32_t *ctr_enc, float *w_cls, float *m_cls, float *v_cls, int32_t *ctr_cls, float lr, float weight_decay,
+                        float *combined, float *emb, float *scores, float *rowloss, float *dscores, float *ws, float *loss_log,
+                        ggad_stream_t stream) {
+  GGAD_REQUIRE(feat && table && len_host && w_enc && m_enc && v_enc && ctr_enc && w_cls && m_cls && v_cls && ctr_cls);
+  GGAD_REQUIRE(combined && emb && scores && rowloss && dscores && ws && loss_log);
+  GGAD_REQUIRE(n_steps >= 0 && b_max >= 1 && k >= 1 && stride >= (int64_t)b_max * (3 + (int64_t)k));
+  if (!ggad_sage_supported(feat_dim, embed_dim, 2)) return GGAD_E_UNSUPPORTED;
+  for (int32_t s = 0; s < n_steps; ++s) GGAD_REQUIRE(len_host[s] >= 1 && len_host[s] <= b_max);      // before the first launch
+  hipStream_t st = as_stream(stream);
+  const int n_out = embed_dim * 2 * feat_dim, n_cls = 2 * embed_dim;
+  const dim3 bwd_grid(SG_BWD_PARTS, (unsigned)((n_out + SG_BWD_TILE - 1) / SG_BWD_TILE));
+  for (int32_t s = 0; s < n_steps; ++s) {
+    const int B = len_host[s];
+    const int32_t *nodes = table + (int64_t)s * stride, *cnt = nodes + b_max, *labels = cnt + b_max, *nbr = labels + b_max;
+    const int groups = (B + SG_WAVES - 1) / SG_WAVES;
+    k_sage_fwd<<<dim3((unsigned)(groups > SG_MAX_GRID ? SG_MAX_GRID : groups)), dim3(SG_THREADS), 0, st>>>(
+        feat, feat_dim, nodes, nbr, cnt, B, k, w_enc, embed_dim, w_cls, labels, combined, emb, scores, rowloss, dscores);
+    k_sage_bwd_part<<<bwd_grid, dim3(SG_THREADS), 0, st>>>(combined, emb, dscores, w_cls, B, feat_dim, embed_dim, ws);
+    k_sage_sum_adam<<<dim3(1), dim3(SG_SA_THREADS), 0, st>>>(ws, rowloss, B, n_out, n_cls, w_enc, m_enc, v_enc, ctr_enc, w_cls, m_cls,
+                                                             v_cls, ctr_cls, lr, weight_decay, loss_log + s);
+    GGAD_CHECK_LAUNCH("sage_epoch");
+  }
   return GGAD_OK;
 }
 

@@ -677,32 +677,30 @@ inline bool strictly_ascending_nonneg(const int32_t *k, int64_t n) {
     if (k[t] <= k[t - 1]) return false;
   return true;
 }
-}  // namespace
 
-extern "C" {
-
-int ggad_pyset_order_i32(const int32_t *keys, int64_t n, int32_t *out) {
-  if (n < 0 || n > 0x3fffffffLL || (n > 0 && (!keys || !out))) return GGAD_E_INVALID;
-  if (!strictly_ascending_nonneg(keys, n)) return GGAD_E_INVALID;
-  std::vector<int32_t> tab, old;
-  pyset_order(keys, n, out, tab, old);
-  return GGAD_OK;
-}
-
-int ggad_mt_sample_rows(ggad_mt19937 *g, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
-                        const int64_t *nodes, int64_t n_rows, int32_t k, int32_t setsize, int32_t *nbr_out, int32_t *cnt_out) {
-  if (!g || !rowptr_host || !nodes || !nbr_out || !cnt_out) return GGAD_E_INVALID;
-  if (n_nodes < 1 || n_nodes > 0x7fffffffLL || n_rows < 0 || k < 1 || k > 4096 || setsize < 21) return GGAD_E_INVALID;
-  // everything is checked before the first draw: a refused call leaves the generator where it was
+// every id a row of the CSR, every row strictly ascending and non-negative: what a call checks before its first draw
+bool sample_rows_ok(const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes, const int64_t *nodes, int64_t n_rows) {
   for (int64_t r = 0; r < n_rows; ++r) {
     const int64_t v = nodes[r];
-    if (v < 0 || v >= n_nodes) return GGAD_E_INVALID;
+    if (v < 0 || v >= n_nodes) return false;
     const int64_t e0 = rowptr_host[v], e1 = rowptr_host[v + 1];
-    if (e0 < 0 || e1 < e0) return GGAD_E_INVALID;
-    if (e1 > e0 && (!col_host || !strictly_ascending_nonneg(col_host + e0, e1 - e0))) return GGAD_E_INVALID;
+    if (e0 < 0 || e1 < e0) return false;
+    if (e1 > e0 && (!col_host || !strictly_ascending_nonneg(col_host + e0, e1 - e0))) return false;
   }
+  return true;
+}
+
+struct SampleScratch {
   std::vector<int32_t> tab, old, order, pool;
-  std::vector<uint32_t> picked((size_t)k);
+  std::vector<uint32_t> picked;
+};
+
+// the draws of ggad_mt_sample_rows for rows that passed sample_rows_ok
+void sample_rows_checked(ggad_mt19937 *g, const int32_t *rowptr_host, const int32_t *col_host, const int64_t *nodes, int64_t n_rows,
+                         int32_t k, int32_t setsize, int32_t *nbr_out, int32_t *cnt_out, SampleScratch &sc) {
+  std::vector<int32_t> &tab = sc.tab, &old = sc.old, &order = sc.order, &pool = sc.pool;
+  std::vector<uint32_t> &picked = sc.picked;
+  if (picked.size() < (size_t)k) picked.resize((size_t)k);
   for (int64_t r = 0; r < n_rows; ++r) {
     const int64_t v = nodes[r];
     const int64_t e0 = rowptr_host[v];
@@ -738,6 +736,86 @@ int ggad_mt_sample_rows(ggad_mt19937 *g, const int32_t *rowptr_host, const int32
     }
     std::sort(dst, dst + k);                                       // the set path hands `sorted(s)` to the segment mean
     cnt_out[r] = k;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int ggad_pyset_order_i32(const int32_t *keys, int64_t n, int32_t *out) {
+  if (n < 0 || n > 0x3fffffffLL || (n > 0 && (!keys || !out))) return GGAD_E_INVALID;
+  if (!strictly_ascending_nonneg(keys, n)) return GGAD_E_INVALID;
+  std::vector<int32_t> tab, old;
+  pyset_order(keys, n, out, tab, old);
+  return GGAD_OK;
+}
+
+int ggad_mt_sample_rows(ggad_mt19937 *g, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
+                        const int64_t *nodes, int64_t n_rows, int32_t k, int32_t setsize, int32_t *nbr_out, int32_t *cnt_out) {
+  if (!g || !rowptr_host || !nodes || !nbr_out || !cnt_out) return GGAD_E_INVALID;
+  if (n_nodes < 1 || n_nodes > 0x7fffffffLL || n_rows < 0 || k < 1 || k > 4096 || setsize < 21) return GGAD_E_INVALID;
+  // everything is checked before the first draw: a refused call leaves the generator where it was
+  if (!sample_rows_ok(rowptr_host, col_host, n_nodes, nodes, n_rows)) return GGAD_E_INVALID;
+  SampleScratch sc;
+  sample_rows_checked(g, rowptr_host, col_host, nodes, n_rows, k, setsize, nbr_out, cnt_out, sc);
+  return GGAD_OK;
+}
+
+/* One epoch of the GraphSAGE device path's schedule (ggad_amd/model_handler.py, _train_sage_device) on ONE generator:
+ * random.shuffle(train); per batch random.shuffle(pool), nodes = train[i0:i1] ++ pool[:n_pseudo], then the sample table of those rows
+ * (sample_rows_checked: the draws of ggad_mt_sample_rows).  Batch b lands at table_out + b * stride in the layout of a SageBatch of
+ * b_max = batch_size + n_pseudo rows: nodes[b_max], cnt[b_max], labels[b_max], nbr[b_max * k]; rows past len_out[b] hold node 0,
+ * length 0, label 0 and -1.  Every refusal happens before the first draw. */
+int ggad_sage_sched_epoch(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t *pool, int64_t n_pool, int32_t batch_size,
+                          int32_t n_pseudo, int32_t num_batches, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
+                          const int64_t *labels_host, int32_t k, int32_t setsize, int32_t checked, int32_t *table_out, int64_t stride,
+                          int32_t *len_out) {
+  if (!g || !rowptr_host || !labels_host || !table_out || !len_out || (!train && n_train > 0) || (!pool && n_pool > 0))
+    return GGAD_E_INVALID;
+  if (n_nodes < 1 || n_nodes > 0x7fffffffLL || k < 1 || k > 4096 || setsize < 21) return GGAD_E_INVALID;
+  if (n_train < 0 || n_train > 0x7fffffffLL || n_pool < 0 || n_pool > 0x7fffffffLL) return GGAD_E_INVALID;
+  if (batch_size < 1 || n_pseudo < 0 || num_batches < 1) return GGAD_E_INVALID;
+  const int64_t b_max = (int64_t)batch_size + n_pseudo;
+  if (b_max > 0x7fffffffLL / (3 + (int64_t)k) || stride < b_max * (3 + (int64_t)k)) return GGAD_E_INVALID;
+  const int64_t n_p = n_pool < n_pseudo ? n_pool : (int64_t)n_pseudo;          // pool[:n_pseudo] of a shorter pool is the whole pool
+  auto train_rows = [&](int64_t b) {                                             // len(train[i0:i1]), i1 = min(.., n_train)
+    const int64_t i0 = b * batch_size;
+    int64_t i1 = i0 + batch_size;
+    if (i1 > n_train) i1 = n_train;
+    return i1 > i0 ? i1 - i0 : (int64_t)0;
+  };
+  if (n_p == 0 && train_rows((int64_t)num_batches - 1) == 0) return GGAD_E_INVALID;      // a batch of zero rows (the last is the shortest)
+  if (!checked) {      // a shuffle moves ids, it does not change them: a caller whose earlier call on these arrays passed may skip this
+    if (!sample_rows_ok(rowptr_host, col_host, n_nodes, train, n_train)) return GGAD_E_INVALID;
+    if (!sample_rows_ok(rowptr_host, col_host, n_nodes, pool, n_pool)) return GGAD_E_INVALID;
+  }
+  static thread_local std::vector<int32_t> tgt;
+  static thread_local std::vector<int64_t> nodes;
+  static thread_local SampleScratch sc;
+  const int64_t n_big = n_train > n_pool ? n_train : n_pool;
+  if ((int64_t)tgt.size() < n_big + 16) tgt.resize((size_t)n_big + 16);
+  if ((int64_t)nodes.size() < b_max) nodes.resize((size_t)b_max);
+  if (n_train >= 2) {
+    shuffle_targets(g, n_train, tgt.data());
+    apply_swaps(train, n_train, tgt.data());
+  }
+  for (int64_t b = 0; b < num_batches; ++b) {
+    if (n_pool >= 2) {
+      shuffle_targets(g, n_pool, tgt.data());
+      apply_swaps(pool, n_pool, tgt.data());
+    }
+    const int64_t nt = train_rows(b), rows = nt + n_p;
+    if (nt > 0) std::memcpy(nodes.data(), train + b * batch_size, (size_t)nt * sizeof(int64_t));
+    if (n_p > 0) std::memcpy(nodes.data() + nt, pool, (size_t)n_p * sizeof(int64_t));
+    int32_t *t_nodes = table_out + b * stride, *t_cnt = t_nodes + b_max, *t_lab = t_cnt + b_max, *t_nbr = t_lab + b_max;
+    sample_rows_checked(g, rowptr_host, col_host, nodes.data(), rows, k, setsize, t_nbr, t_cnt, sc);
+    for (int64_t r = 0; r < rows; ++r) {
+      t_nodes[r] = (int32_t)nodes[(size_t)r];
+      t_lab[r] = (int32_t)labels_host[nodes[(size_t)r]];
+    }
+    for (int64_t r = rows; r < b_max; ++r) t_nodes[r] = t_cnt[r] = t_lab[r] = 0;
+    for (int64_t e = rows * k; e < b_max * k; ++e) t_nbr[e] = -1;
+    len_out[b] = (int32_t)rows;
   }
   return GGAD_OK;
 }

@@ -43,6 +43,8 @@ class ModelHandler(object):
         if bool(getattr(args, "pcgnn_fused", False)) and not bool(getattr(args, "pcgnn_device", False)):
             raise ValueError("config key `pcgnn_fused` needs `pcgnn_device: true`: the fused head runs behind the relation kernels of "
                              "the device path")
+        if bool(getattr(args, "sage_epoch", False)) and not bool(getattr(args, "sage_device", False)):
+            raise ValueError("config key `sage_epoch` needs `sage_device: true`: the epoch path replays the kernels of the device path")
         data = getattr(args, "data", None)
         if data is not None:
             homo, feat_data, labels = data
@@ -298,7 +300,11 @@ class ModelHandler(object):
         stream for the epoch shuffle, the pool shuffle and the neighbour samples, and a step is one sampler call, one upload and the
         fused kernels of csrc/sage.hip; a validation sweep is one sampler call and one forward launch.  Same loop, same prints,
         same checkpoints.  The draws equal the set path's bit for bit for CSR input and for dicts whose sets were filled in
-        ascending id order; the stream is handed back to `random` before this returns."""
+        ascending id order; the stream is handed back to `random` before this returns.
+
+        Config key `sage_epoch: true` (needs `sage_device`; sage_epoch.py): an epoch is one native sampler call, one upload and one
+        replayed graph of three launches per step, Adam inside the last; `self.sage_epoch` is the runner.  Same draws, losses,
+        weights, optimiser state, prints and checkpoints as the step path, bit for bit."""
         from .fullgraph import FlatAdam
         from .sage_device import SageDevice
         args = self.args
@@ -326,21 +332,42 @@ class ModelHandler(object):
             path_saver = os.path.join(dir_saver, "{}_{}.pkl".format(args.data_name, args.model))
             f1_mac_best, auc_best, ep_best = 0, 0, -1
             self.sage_losses = []
+            self.sage_epoch = None
+            if bool(getattr(args, "sage_epoch", False)):
+                from .sage_epoch import SageEpoch
+                self.sage_epoch = SageEpoch(sage, enc_sage.weight, gnn_model.weight, optimizer, idx_train, idx_anomaly, labels,
+                                            args.batch_size, n_pseudo, num_batches)
             for epoch in range(args.num_epochs):
-                rng.shuffle(idx_train)                                     # :314
                 loss_sum, epoch_time = 0.0, 0.0
-                for batch in range(num_batches):
+                if self.sage_epoch is not None:
+                    # what the stream is asked for after this epoch is drawn while the device trains it: the validation sweep, the
+                    # next epoch, or -- after the last epoch -- the test sweep (a restored checkpoint changes no draw)
+                    if epoch % args.valid_epochs == 0:
+                        ahead = lambda: sage.presample(list(idx_valid))
+                    elif epoch + 1 < args.num_epochs:
+                        ahead = "epoch"
+                    else:
+                        ahead = lambda: sage.presample(list(idx_test))
                     t0 = time.time()
-                    i0, i1 = batch * args.batch_size, min((batch + 1) * args.batch_size, len(idx_train))
-                    rng.shuffle(idx_anomaly)                               # :341
-                    batch_nodes = np.concatenate([idx_train[i0:i1], idx_anomaly[:n_pseudo]])     # :342,347
-                    optimizer.zero_grad()
-                    loss = gnn_model.loss(batch_nodes, labels[batch_nodes])
-                    loss.backward()
-                    optimizer.step()
-                    epoch_time += time.time() - t0
-                    self.sage_losses.append(float(loss.item()))
-                    loss_sum += self.sage_losses[-1]
+                    epoch_losses = self.sage_epoch.run_epoch(ahead)
+                    epoch_time = time.time() - t0
+                    for l in epoch_losses:
+                        self.sage_losses.append(float(l))
+                        loss_sum += self.sage_losses[-1]
+                else:
+                    rng.shuffle(idx_train)                                 # :314
+                    for batch in range(num_batches):
+                        t0 = time.time()
+                        i0, i1 = batch * args.batch_size, min((batch + 1) * args.batch_size, len(idx_train))
+                        rng.shuffle(idx_anomaly)                           # :341
+                        batch_nodes = np.concatenate([idx_train[i0:i1], idx_anomaly[:n_pseudo]])     # :342,347
+                        optimizer.zero_grad()
+                        loss = gnn_model.loss(batch_nodes, labels[batch_nodes])
+                        loss.backward()
+                        optimizer.step()
+                        epoch_time += time.time() - t0
+                        self.sage_losses.append(float(loss.item()))
+                        loss_sum += self.sage_losses[-1]
                 print(f"Epoch: {epoch}, loss: {loss_sum / num_batches}, time: {epoch_time}s")
                 if epoch % args.valid_epochs == 0:
                     print("Valid at epoch {}".format(epoch))

@@ -15,6 +15,9 @@ The arithmetic differs from the set path's in summation order only.
 A row without neighbours gives what `ggad_seg_mean` gives for an empty list: 0 * (1 / 0) = NaN in the neighbour half of
 `combined`, hence NaN scores for that row, as in the reference (its dense mask row is 0 / 0).
 
+The epoch path (`sage_epoch.py`, config key `sage_epoch`) builds on this object: it samples and trains whole epochs without returning
+to the host between steps, and uses `presample` to draw a validation sweep's table while the device still trains.
+
 There is no fallback: shapes outside `ggad_sage_supported` (1 <= feat_dim <= 64, 1 <= embed_dim <= 64, two classes), `gcn=True` and
 `num_sample=None` raise at construction."""
 from __future__ import annotations
@@ -85,12 +88,19 @@ class SageDevice:
         self.rng = rng
         self.ws = torch.empty(int(lib.ggad_sage_bwd_workspace_elems(self.F, self.D)), dtype=torch.float32, device=table.device)
         self.last = {}                                             # buffers of the latest forward / backward (tests, profiling)
+        self._ahead = None                                         # a table drawn by `presample` for the next `sample` call
 
     # ---- host side
     def sample(self, nodes):
         """(nodes, nbr, cnt) as numpy: the sample table of `nodes`, in list order, on the configured stream."""
         nodes = np.asarray(nodes.detach().cpu().numpy() if isinstance(nodes, torch.Tensor) else nodes, dtype=np.int64).reshape(-1)
         g = self.graph
+        ahead, self._ahead = self._ahead, None
+        if ahead is not None:
+            if not np.array_equal(ahead[0], nodes):
+                raise RuntimeError("a table sampled ahead was drawn for other nodes than the next call asks for: the `random` "
+                                   "stream would be out of order")
+            return ahead
         if len(nodes) == 0 or nodes.min() < 0 or nodes.max() >= g.n:
             raise ValueError(f"batch nodes must be a non-empty list of ids in [0, {g.n})")
         if self.rng is not None:
@@ -100,6 +110,12 @@ class SageDevice:
             nbr, cnt = rng.sample_rows(g.rowptr_host, g.col_host, nodes, self.k)
             random.setstate(rng.to_python_state())
         return nodes, nbr, cnt
+
+    def presample(self, nodes) -> None:
+        """Draws the table of `nodes` NOW and keeps it for the next `sample` call, which must ask for the same ids: the epoch path
+        (sage_epoch.py) samples a validation sweep while the device still trains.  The draws are the ones that call would make."""
+        self._ahead = None
+        self._ahead = self.sample(nodes)
 
     def upload(self, nodes, nbr, cnt, labels=None) -> SageBatch:
         """Checks a sample table on the host -- every id a row of the feature table, every length in [0, k], labels in {0, 1} --

@@ -91,6 +91,39 @@ class PyCompatRandom:
                              "samples from are filled in ascending order)")
         return nbr, cnt
 
+    def sage_epoch(self, rowptr: np.ndarray, col: np.ndarray, labels: np.ndarray, train: np.ndarray, pool: np.ndarray, batch_size: int,
+                   n_pseudo: int, num_batches: int, num_sample: int, out: np.ndarray = None, checked: bool = False):
+        """One epoch of the GraphSAGE device path's schedule in one native call (`ggad_sage_sched_epoch`): ``shuffle(train)``, then
+        per batch ``shuffle(pool)``, nodes = ``train[i0:i1] ++ pool[:n_pseudo]`` and their `sample_rows` table.  ``train`` / ``pool``
+        (contiguous int64) are shuffled in place.  Returns ``(table, lens)``: table is (num_batches, b_max * (3 + k)) int32 with
+        b_max = batch_size + n_pseudo, a row holding nodes[b_max], cnt[b_max], labels[b_max] and nbr[b_max * k]; lens the row
+        counts.  ``out``: a contiguous int32 array of that size to write into.  ``checked``: an earlier call on the same graph and
+        arrays succeeded, the id and row scans are skipped.  A refusal raises ValueError and draws nothing."""
+        for a in (train, pool):
+            if not isinstance(a, np.ndarray) or a.dtype != np.int64 or a.ndim != 1 or not a.flags.c_contiguous:
+                raise ValueError("train / pool: contiguous one-dimensional int64 arrays (they are shuffled in place)")
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        k, n_nodes = int(num_sample), len(rowptr) - 1
+        if n_nodes < 1 or int(rowptr[-1]) != len(col) or len(labels) < n_nodes:
+            raise ValueError("rowptr is not a CSR row pointer of col, or labels is shorter than the graph")
+        b_max = int(batch_size) + int(n_pseudo)
+        stride = b_max * (3 + max(k, 0))
+        if out is None:
+            out = np.empty(max(int(num_batches), 0) * stride, dtype=np.int32)
+        if out.dtype != np.int32 or not out.flags.c_contiguous or out.size != max(int(num_batches), 0) * stride:
+            raise ValueError("out: a contiguous int32 array of num_batches * b_max * (3 + k) elements")
+        lens = np.empty(max(int(num_batches), 0), dtype=np.int32)
+        rc = self._lib.ggad_sage_sched_epoch(self._h, train.ctypes.data, len(train), pool.ctypes.data, len(pool), int(batch_size),
+                                             int(n_pseudo), int(num_batches), rowptr.ctypes.data, col.ctypes.data, n_nodes,
+                                             labels.ctypes.data, k, sample_setsize(k) if k >= 1 else 21, int(bool(checked)),
+                                             out.ctypes.data, stride, lens.ctypes.data)
+        if rc != 0:
+            raise ValueError("ggad_sage_sched_epoch refused the epoch before any draw: an id outside the graph in train or pool, "
+                             "num_sample < 1, a CSR row that is not strictly ascending, or a batch without rows")
+        return out.reshape(int(num_batches), stride), lens
+
 
 def sample_setsize(k: int) -> int:
     """The population size up to which `random.sample` copies the population into a pool (CPython Lib/random.py), evaluated with

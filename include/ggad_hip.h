@@ -858,6 +858,19 @@ int ggad_pyset_order_i32(const int32_t *keys_host, int64_t n, int32_t *out_host)
  * the rows, not on how they are cut into calls.  Ids outside [0, n_nodes), an unsorted row, k < 1: GGAD_E_INVALID before any draw. */
 int ggad_mt_sample_rows(ggad_mt19937 *, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
                         const int64_t *nodes_host, int64_t n_rows, int32_t k, int32_t setsize, int32_t *nbr_out, int32_t *cnt_out);
+/* One epoch of the GraphSAGE device path's schedule in one call, on one generator: random.shuffle(train), then for each of
+ * num_batches batches random.shuffle(pool), nodes = train[i0:i1] ++ pool[:n_pseudo] (i0 = b * batch_size, i1 = min(i0 + batch_size,
+ * n_train); a pool shorter than n_pseudo is taken whole) and the sample table of those rows drawn as ggad_mt_sample_rows draws it.
+ * Batch b is written at table_out + b * stride (stride >= b_max * (3 + k) ints, b_max = batch_size + n_pseudo): nodes[b_max],
+ * cnt[b_max], labels[b_max] (labels_host[node], n_nodes int64), nbr[b_max * k]; rows past len_out[b] hold 0 / 0 / 0 / -1.  train and
+ * pool end up shuffled in place and the generator where the per-call path leaves them.  Refused with GGAD_E_INVALID before the
+ * first draw, generator and arrays untouched: an id outside [0, n_nodes) in train or pool, k < 1, an unsorted CSR row of such an id,
+ * a batch of zero rows.  checked != 0: the caller states that an earlier call on the same graph and the same two arrays returned
+ * GGAD_OK -- a shuffle moves ids without changing them -- and the two O(n_train + n_pool) scans are skipped. */
+int ggad_sage_sched_epoch(ggad_mt19937 *, int64_t *train, int64_t n_train, int64_t *pool, int64_t n_pool, int32_t batch_size,
+                          int32_t n_pseudo, int32_t num_batches, const int32_t *rowptr_host, const int32_t *col_host, int64_t n_nodes,
+                          const int64_t *labels_host, int32_t k, int32_t setsize, int32_t checked, int32_t *table_out, int64_t stride,
+                          int32_t *len_out);
 
 /* ------------------------------------------------------------------------------------
  * torch.randn's CPU stream continued on the DEVICE (rng.hip).  `state`: ggad_mt_state_words() uint32 in device memory -- the 624
@@ -933,6 +946,24 @@ int ggad_sage_fwd_f32(const float *feat, int32_t feat_dim, const int32_t *nodes,
                       float *combined, float *emb, float *scores, float *loss, float *dscores, ggad_stream_t stream);
 int ggad_sage_bwd_f32(const float *combined, const float *emb, const float *dscores, const float *w_cls, int32_t n_batch,
                       int32_t feat_dim, int32_t embed_dim, float *ws, float *d_enc, float *d_cls, ggad_stream_t stream);
+/* The tail of a step in one launch of one workgroup: d_enc / d_cls = the ggad_sage_bwd_parts() partial sums of `ws` added in range
+ * order (what ggad_sage_bwd_f32 leaves in its outputs), torch's Adam on both tensors with the arithmetic of ggad_adam_multi_f32 -- in
+ * place on the weights, the moments and the two int32 step counters, which are read first and both advanced by one -- and
+ * loss_out[0] = the mean of the n_batch row losses in the order of ggad_sage_fwd_f32's loss[0].  No floating-point atomics, no
+ * tickets.  ws must hold what k_sage_bwd_part wrote for the same widths. */
+int ggad_sage_sum_adam_f32(const float *ws, const float *rowloss, int32_t n_batch, int32_t feat_dim, int32_t embed_dim, float *w_enc,
+                           float *m_enc, float *v_enc, int32_t *ctr_enc, float *w_cls, float *m_cls, float *v_cls, int32_t *ctr_cls,
+                           float lr, float weight_decay, float *loss_out, ggad_stream_t stream);
+/* n_steps optimiser steps enqueued on one stream with no host work between them: per step the forward and the partial backward of
+ * ggad_sage_fwd_f32 / ggad_sage_bwd_f32 on the step's slice of an epoch table (the layout of ggad_sage_sched_epoch: step s at
+ * table + s * stride, len_host[s] rows, 1 <= len_host[s] <= b_max), then ggad_sage_sum_adam_f32 with loss_log + s.  combined
+ * (b_max x 2 feat_dim), emb (b_max x embed_dim), scores and dscores (b_max x 2), rowloss (b_max) and ws are shared by the steps.
+ * len_host is read on the HOST while enqueueing: under a stream capture the row counts become constants of the graph. */
+int ggad_sage_epoch_f32(const float *feat, int32_t feat_dim, const int32_t *table, int64_t stride, const int32_t *len_host,
+                        int32_t n_steps, int32_t b_max, int32_t k, int32_t embed_dim, float *w_enc, float *m_enc, float *v_enc,
+                        int32_t *ctr_enc, float *w_cls, float *m_cls, float *v_cls, int32_t *ctr_cls, float lr, float weight_decay,
+                        float *combined, float *emb, float *scores, float *rowloss, float *dscores, float *ws, float *loss_log,
+                        ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Head and loss of the PC-GNN comparison model behind its relation kernels (pcgnn_head.hip; reference src/layers.py:125-153,
