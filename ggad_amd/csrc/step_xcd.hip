@@ -113,6 +113,19 @@ __device__ __forceinline__ float rl(float v, int lane) {
 }
 
 __device__ __forceinline__ int ri(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }      // the same in every lane: a scalar register
+
+// Addresses.  Everything the chunk kernel touches is addressed as a WAVE-UNIFORM base (pointer + uniform element index: scalar
+// registers, scalar arithmetic) plus an unsigned 32-bit BYTE offset per lane: the scalar-base form of global_load / global_store,
+// ONE vector register per address and usually the same one (4 * lane) for every array.  As 64-bit per-lane pointers the thirteen
+// loop-invariant ones (optimiser state at pidx, the dw_part slots, the rows of gw_row / pos_o) were hoisted to the kernel's entry,
+// spilled to scratch and reloaded -- each reload with a full s_waitcnt -- inside phases C and E.  A lane offset never leaves one
+// piece / one batch row block / the parameter block, so 32 bits hold it (host: max_rows <= 2^24).
+template <class T>
+__device__ __forceinline__ T *lane_at(T *base, unsigned byte_off) {
+  asm volatile("" : "+v"(byte_off));      // pins the addition to its use: a loop-invariant base + offset is otherwise hoisted out of the step
+  return (T *)((char *)base + byte_off);  // loop as a 64-bit per-lane pointer, exactly what this form is there to avoid
+}
 
 // All workgroups of the launch sit on one XCD: plain stores are in the shared L2 once the wave's vmcnt has drained; the round
 // number in the own slot publishes them; one wave polls all slots with one L1-bypassing load.
@@ -159,23 +172,36 @@ struct PieceX {
   float a[XKS];      // forward operand: X[entry a][4 j + g]
   float b[4];        // gradient operand: X[entry 4 g + v][feature a]
 };
-// n consecutive rows of x (stride XFT floats) from row `base` on; rows beyond n read as zero.  Every load is unconditional
-// (clamped address, select afterwards): 9 loads in flight per piece.
-__device__ __forceinline__ void load_piece_x(const float *__restrict__ x, int base, int n, int lane, PieceX &P) {
+// n consecutive rows of x (stride XFT floats) from the wave-uniform row pointer `xp` on; rows beyond n read as zero.  Every load
+// is unconditional (clamped address, select afterwards): 9 loads in flight per piece.  The loads and the selects are two calls:
+// a select directly behind its load makes the compiler wait for that load before it issues the next (the prefetch of a step's
+// two pieces was 18 dependent round trips), so a caller issues the raw loads of ALL its pieces and masks them where it first
+// needs them (the prefetch: at the hand-over at the bottom of the step, with n of the NEXT step's record).
+__device__ __forceinline__ void load_piece_raw(const float *__restrict__ xp, int n, int lane, PieceX &P) {
   const int a = lane & 15, g = lane >> 4;
-  const unsigned ra = base + min(a, n - 1);
+  const unsigned ra = (unsigned)min(a, n - 1) * XFT;
 #pragma unroll
   for (int j = 0; j < XKS; ++j) {
     const int f = 4 * j + g;
-    const float xv = x[ra * XFT + (f < XFT ? f : 0)];
-    P.a[j] = (a < n && f < XFT) ? xv : 0.0f;
+    P.a[j] = *lane_at(xp, 4u * (ra + (unsigned)(f < XFT ? f : 0)));
   }
 #pragma unroll
   for (int v = 0; v < 4; ++v) {
     const int e = 4 * g + v;
-    const float xv = x[(unsigned)(base + min(e, n - 1)) * XFT + a];
-    P.b[v] = e < n ? xv : 0.0f;
+    P.b[v] = *lane_at(xp, 4u * ((unsigned)min(e, n - 1) * XFT + (unsigned)a));
   }
+}
+__device__ __forceinline__ void mask_piece_x(int n, int lane, PieceX &P) {
+  const int a = lane & 15, g = lane >> 4;
+#pragma unroll
+  for (int j = 0; j < XKS; ++j) P.a[j] = (a < n && 4 * j + g < XFT) ? P.a[j] : 0.0f;
+#pragma unroll
+  for (int v = 0; v < 4; ++v) P.b[v] = 4 * g + v < n ? P.b[v] : 0.0f;
+}
+__device__ __forceinline__ void load_piece_x(const float *__restrict__ xp, int n, int lane, PieceX &P) {
+  load_piece_raw(xp, n, lane, P);
+  __builtin_amdgcn_sched_barrier(0);                        // the nine loads first, then the selects (as in lds_matvec)
+  mask_piece_x(n, lane, P);
 }
 __device__ __forceinline__ void piece_fwd(const PieceX &P, const float (&WB)[XKS][XNT], f4 (&h)[XNT]) {
 #pragma unroll
@@ -221,15 +247,18 @@ __device__ __forceinline__ void adam_apply(float *__restrict__ params, float *__
   vi = fmaf(0.001f * g, g, vi * 0.999f);                    // mul_(beta2).addcmul_(g, g, 1 - beta2)
   const float denom = sqrtf(vi) / bc2s + 1e-8f;
   p = p - step_size * (mi / denom);                         // addcdiv_(exp_avg, denom, -step_size)
-  params[i] = p; m[i] = mi; v[i] = vi;
   const int D = L.D, F = L.F;
+  int it = -1;                                              // where the transposed copy of this parameter lives
   if (i >= L.o_W() && i < L.o_fc()) {
     const int u = i - L.o_W(); const int d = u / F, f = u - d * F;
-    params[L.o_Wt() + f * D + d] = p;
+    it = L.o_Wt() + f * D + d;
   } else if (i >= L.o_fc()) {
     const int u = i - L.o_fc(); const int d = u / D, d2 = u - d * D;
-    params[L.o_fcT() + d2 * D + d] = p;
+    it = L.o_fcT() + d2 * D + d;
   }
+  // the four stores back to back: uniform bases, one lane offset each, no wait between them
+  *lane_at(params, 4u * (unsigned)i) = p; *lane_at(m, 4u * (unsigned)i) = mi; *lane_at(v, 4u * (unsigned)i) = vi;
+  if (it >= 0) *lane_at(params, 4u * (unsigned)it) = p;
 }
 
 template <int MODE, int DT>      // MODE 1: Adam; 2: one-shot data-parallel exchange + Adam.  DT: embedding width at compile time (0 = run time)
@@ -268,19 +297,20 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
     s_rank = r;
   }
   __syncthreads();
-  const int rank = s_rank;
+  const int rank = uni(s_rank);
   if (rank < 0) return;
   const int nv = A.nv, NVW = nv * XW, G = nv;
 
   const ggad_mb_step &S = A.s;
   const int D = DT ? DT : S.D;
   const ParamLayout L{D, XFT};
-  const int lane = lane_id(), wid = threadIdx.x / GGAD_WAVE;
+  const int lane = lane_id(), wid = uni((int)(threadIdx.x / GGAD_WAVE));      // rank, wid: scalar registers, and everything derived from them
   const int la = lane & 15, lg = lane >> 4;             // (a, g) of the matrix-core layouts
   const int l8 = lane & 7;
   const bool on = lane < D;
   const int d = on ? lane : D - 1;
   const int fl = lane < XFT ? lane : XFT - 1;
+  const unsigned lane4 = 4u * (unsigned)lane, d4 = 4u * (unsigned)d;      // THE lane offsets (bytes) of nearly every address below
   // the records and operands of step b + 1 are fetched into registers during step b
   constexpr bool piped = true;
   float *params = S.params;
@@ -300,12 +330,21 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
     } else {
       row0 = A.batch_ptr[bb]; B = A.batch_ptr[bb + 1] - row0; ck0 = S.row_ck_ptr[row0]; nck = S.row_ck_ptr[row0 + B] - ck0;
     }
+    row0 = uni(row0); B = uni(B); ck0 = uni(ck0); nck = uni(nck);      // uniform by construction: bases of the step's addresses
+  };
+  // label-0 positions of batch bb: LDS or global memory by a uniform branch (as one expression the two became ONE flat load
+  // through a selected pointer, waited for with vmcnt(0) lgkmcnt(0) in front of the step's weight loads)
+  auto batch_n0s = [&](int bb) {
+    int n0s;
+    if (bb < XBT) n0s = uni(bt_n0[bb]);
+    else n0s = uni(A.batch_n0[bb]);
+    return n0s;
   };
   // virtual wave of this wave in its first virtual workgroup: pieces / positions v0, v0 + NVW, ...  Consecutive pieces (and
   // positions) go to consecutive WORKGROUPS, so a batch of 358 pieces puts 11-12 on every compute unit
   const int v0 = rank + nv * wid;
-  auto piece_rec = [&](int c) { return A.ck_rec[(unsigned)c * REC + l8]; };
-  auto pos_rec = [&](int row) { return A.pos_rec[(unsigned)row * REC + l8]; };
+  auto piece_rec = [&](int c) { return *lane_at(A.ck_rec + (int64_t)c * REC, 4u * (unsigned)l8); };
+  auto pos_rec = [&](int row) { return *lane_at(A.pos_rec + (int64_t)row * REC, 4u * (unsigned)l8); };
   auto issue_recs = [&](int bb, int (&rv)[XPC], int &pv) {          // records of this wave's pieces / position in step bb
     int r0, Bn, c0, nc;
     batch_info(bb, r0, Bn, c0, nc);
@@ -313,7 +352,9 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
     for (int j = 0; j < XPC; ++j) rv[j] = piece_rec(c0 + min(v0 + j * NVW, max(nc - 1, 0)));
     pv = pos_rec(r0 + min(v0, max(Bn - 1, 0)));
   };
-  auto issue_ops = [&](int rv, PieceX &P) { load_piece_x(S.x2, ri(rv, 1), max(ri(rv, 0) & 63, 1), lane, P); };
+  auto piece_n = [&](int rv) { return max(ri(rv, 0) & 63, 1); };
+  auto issue_raw = [&](int rv, PieceX &P) { load_piece_raw(S.x2 + (int64_t)ri(rv, 1) * XFT, piece_n(rv), lane, P); };      // loads only
+  auto issue_ops = [&](int rv, PieceX &P) { load_piece_x(S.x2 + (int64_t)ri(rv, 1) * XFT, piece_n(rv), lane, P); };
   int recv[XPC], posv = 0, recn[XPC], posn = 0;
   PieceX xc[XPC], xn[XPC];
 #pragma unroll
@@ -321,7 +362,9 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
   if (piped) {
     issue_recs(0, recv, posv);
 #pragma unroll
-    for (int j = 0; j < XPC; ++j) issue_ops(recv[j], xc[j]);
+    for (int j = 0; j < XPC; ++j) issue_raw(recv[j], xc[j]);                    // all 18 loads, then the selects
+#pragma unroll
+    for (int j = 0; j < XPC; ++j) mask_piece_x(piece_n(recv[j]), lane, xc[j]);
   }
   unsigned round = 0;
   unsigned long long t_prev = wall_clock64();
@@ -345,25 +388,29 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
     float *log8 = A.loss_log + (int64_t)8 * (A.log_base + b);
     // ---------------------------------------------------------------- weights of this step: L2 -> LDS (written by phase E of the previous step)
     // ALL the loads of this block first, then the LDS stores: as loops of (load, store) the compiler put an s_waitcnt vmcnt(0)
-    // behind every load -- nine dependent L2 round trips (W^T 2, fc^T 4, w, the batch's n0, its label-1 sources): 1.3 us per step
-    const int n0s = b < XBT ? bt_n0[b] : A.batch_n0[b];
-    const int n_ra = (A.dbg & 2) ? 0 : min(B - n0s, XRA);
-    const int ra_v = S.pos_meta[row0 + min(n0s + (int)threadIdx.x, B - 1)];      // sources of the generated columns (label-1 rows), for phase E
-                                                                                   // (unconditional, clamped: in flight with the weights)
-    const float w_v = (threadIdx.x >= XT - GGAD_WAVE && on) ? cld(params + lane) : 0.0f;
-    if ((D & 1) == 0) {                                   // all three blocks start on even offsets: 8-byte loads
-      constexpr int NWT = (XFT * GGAD_MAX_D / 2 + XT - 1) / XT, NFC = (GGAD_MAX_D * GGAD_MAX_D / 2 + XT - 1) / XT;
-      f2 vwt[NWT], vfc[NFC];
+    // behind every load -- nine dependent L2 round trips (W^T 2, fc^T 4, w, the batch's n0, its label-1 sources): 1.3 us per step.
+    // The batch's n0 (LDS for the first XBT batches) and the pos_meta load that depends on it come BEHIND the weight loads.
+    constexpr int NWT = (XFT * GGAD_MAX_D / 2 + XT - 1) / XT, NFC = (GGAD_MAX_D * GGAD_MAX_D / 2 + XT - 1) / XT;
+    f2 vwt[NWT], vfc[NFC];
+    const bool even_d = (D & 1) == 0;                     // all three blocks start on even offsets: 8-byte loads
+    const float w_v = (threadIdx.x >= XT - GGAD_WAVE && on) ? cld(lane_at(params, lane4)) : 0.0f;
+    if (even_d) {
 #pragma unroll
       for (int k = 0; k < NWT; ++k) {
         const int i = 2 * ((int)threadIdx.x + k * XT);
-        vwt[k] = cld2(params + L.o_Wt() + min(i, XFT * D - 2));
+        vwt[k] = cld2(lane_at(params + L.o_Wt(), 4u * (unsigned)min(i, XFT * D - 2)));
       }
 #pragma unroll
       for (int k = 0; k < NFC; ++k) {
         const int i = 2 * ((int)threadIdx.x + k * XT);
-        vfc[k] = cld2(params + L.o_fcT() + min(i, D * D - 2));
+        vfc[k] = cld2(lane_at(params + L.o_fcT(), 4u * (unsigned)min(i, D * D - 2)));
       }
+    }
+    const int n0s = batch_n0s(b);
+    const int n_ra = (A.dbg & 2) ? 0 : min(B - n0s, XRA);
+    const int ra_v = *lane_at(S.pos_meta + row0, 4u * (unsigned)min(n0s + (int)threadIdx.x, B - 1));      // sources of the generated columns (label-1
+                                                                                   // rows), for phase E (unconditional, clamped: in flight with the weights)
+    if (even_d) {
 #pragma unroll
       for (int k = 0; k < NWT; ++k) {
         const int i = 2 * ((int)threadIdx.x + k * XT);
@@ -378,23 +425,28 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         }
       }
     } else {
-      for (int i = threadIdx.x; i < XFT * D; i += XT) wt_lds[i] = cld(params + L.o_Wt() + i);
+      for (int i = threadIdx.x; i < XFT * D; i += XT) wt_lds[i] = cld(lane_at(params + L.o_Wt(), 4u * (unsigned)i));
       for (int i = threadIdx.x; i < D * D; i += XT) {
         const int r2 = i / D, c2 = i - r2 * D;
-        fct[r2 * FCS + c2] = cld(params + L.o_fcT() + i);
+        fct[r2 * FCS + c2] = cld(lane_at(params + L.o_fcT(), 4u * (unsigned)i));
       }
     }
     if (threadIdx.x >= XT - GGAD_WAVE) w_lds[lane] = w_v;
     if ((int)threadIdx.x < n_ra) ra_lds[threadIdx.x] = ra_v >> 2;
     __syncthreads();
-    float WB[XKS][XNT];                                   // W^T in the B-operand layout: W[16 t + a][4 j + g]
+    // W^T in the B-operand layout: W[16 t + a][4 j + g].  20 registers that live through phase A only: the rare pieces beyond XPC
+    // per wave rebuild them from wt_lds in phase C (unchanged until the next step's top: the same bits)
+    auto load_wb = [&](float (&Wb)[XKS][XNT]) {
 #pragma unroll
-    for (int j = 0; j < XKS; ++j)
+      for (int j = 0; j < XKS; ++j)
 #pragma unroll
-      for (int t = 0; t < XNT; ++t) {
-        const int f = 4 * j + lg, ch = 16 * t + la;
-        WB[j][t] = (f < XFT && ch < D) ? wt_lds[f * D + ch] : 0.0f;
-      }
+        for (int t = 0; t < XNT; ++t) {
+          const int f = 4 * j + lg, ch = 16 * t + la;
+          Wb[j][t] = (f < XFT && ch < D) ? wt_lds[f * D + ch] : 0.0f;
+        }
+    };
+    float WB[XKS][XNT];
+    load_wb(WB);
     const float wd_r = w_lds[d];
     XCD_TICK(8)
 
@@ -413,7 +465,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         st += __shfl_xor(st, 32, GGAD_WAVE);
         out = lg == t ? st : out;                           // lane l = channel 16 (l / 16) + l % 16
       }
-      S.chunk_part[(unsigned)c * 64 + lane] = out;
+      *lane_at(S.chunk_part + (int64_t)c * 64, lane4) = out;
       return pos;
     };
     unsigned hpos[XPC];
@@ -437,15 +489,16 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       XCD_TICK(9)
       for (int p = NVW - 1 - v; 16 * p < B; p += NVW) {     // h1 = relu(W x1[row]), 16 rows per wave     graphsage.py:412
         PieceX P;
-        load_piece_x(S.x1, row0 + 16 * p, min(16, B - 16 * p), lane, P);
+        load_piece_x(S.x1 + (int64_t)(row0 + 16 * p) * XFT, min(16, B - 16 * p), lane, P);
         f4 h[XNT];
         piece_fwd(P, WB, h);
+        float *h1p = S.h1 + (int64_t)(row0 + 16 * p) * D;
 #pragma unroll
         for (int t = 0; t < XNT; ++t)
 #pragma unroll
           for (int vv = 0; vv < 4; ++vv) {
             const int i = 16 * p + 4 * lg + vv, ch = 16 * t + la;
-            if (i < B && ch < D) S.h1[(unsigned)(row0 + i) * D + ch] = fmaxf(h[t][vv], 0.0f);
+            if (i < B && ch < D) *lane_at(h1p, 4u * (unsigned)((4 * lg + vv) * D + ch)) = fmaxf(h[t][vv], 0.0f);
           }
       }
     }
@@ -460,7 +513,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       if (n <= 4) {                                                 // the usual row: no loop, no guards
         float pv[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) pv[k] = cld(S.chunk_part + (unsigned)(first + min(k, n - 1)) * 64 + lane);
+        for (int k = 0; k < 4; ++k) pv[k] = cld(lane_at(S.chunk_part + (int64_t)(first + min(k, n - 1)) * 64, lane4));
 #pragma unroll
         for (int k = 0; k < 4; ++k) tot += (k < n) ? pv[k] : 0.0f;
         return;
@@ -472,7 +525,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         for (int g4 = 0; g4 < PF / 4; ++g4) {
           if (c0 + 4 * g4 < n) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) pv[4 * g4 + k] = cld(S.chunk_part + (unsigned)(first + min(c0 + 4 * g4 + k, n - 1)) * 64 + lane);
+            for (int k = 0; k < 4; ++k) pv[4 * g4 + k] = cld(lane_at(S.chunk_part + (int64_t)(first + min(c0 + 4 * g4 + k, n - 1)) * 64, lane4));
           }
         }
 #pragma unroll
@@ -496,7 +549,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         const bool from_gen = (meta & 2) != 0;
         const int row = row0 + q;
         const int qa = ri(pr, 1), nq = act ? ri(pr, 2) : 0, rq = ri(pr, 3), sa = ri(pr, 4), ns = (act && from_gen) ? ri(pr, 5) : 0, rs = ri(pr, 6);
-        const float hs_r = cld(S.h1 + (unsigned)src * D + d);
+        const float hs_r = cld(lane_at(S.h1 + (int64_t)src * D, d4));
         // a hub row (thousands of entries = hundreds of pieces) is summed by ALL waves of the workgroup, an eighth each, the eight
         // partial sums added in order; every other row by its own wave
         const bool my_hub = nq > xhub || ns > xhub;
@@ -511,9 +564,9 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         __syncthreads();
         const int any_hub = hub_any;                                 // (most batches: no hub row in this workgroup, nothing to walk)
         for (int sidx = 0; any_hub && sidx < 2 * XW; ++sidx) {
-          const int n = hub_n[sidx];
+          const int n = uni(hub_n[sidx]);
           if (n == 0) continue;
-          const int first = hub_first[sidx];
+          const int first = uni(hub_first[sidx]);
           const int seg = ((n + XW - 1) / XW + 3) & ~3;
           const int lo = min(wid * seg, n), hi = min(lo + seg, n);
           float part = 0.0f;
@@ -535,14 +588,14 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         XCD_TICK(15)
         if (!act) continue;
         const float nb_r = (1.0f / (float)rq) * totq;                                            // mask_row = mask / rowsum  graphsage.py:317
-        if (on) S.nbar[(unsigned)row * D + lane] = nb_r;                                          // to_feats_neigh[q, :]
+        if (on) *lane_at(S.nbar + (int64_t)row * D, lane4) = nb_r;                                          // to_feats_neigh[q, :]
         float c_r = hs_r;                                                                        // combined_all[:, q] = h1[src] ...
         if (from_gen) {                                                                          // ... or gen[src] = relu(fc nbar[src])  :428-430
           const float nbm = on ? (1.0f / (float)rs) * tots : 0.0f;
           float a = 0.0f;
           a = lds_matvec(fct + d, FCS, nbm);
           c_r = fmaxf(a, 0.0f);
-          if (on) S.gen[(unsigned)src * D + lane] = c_r;
+          if (on) *lane_at(S.gen + (int64_t)src * D, lane4) = c_r;
         }
         XCD_TICK(13)
         const float wd = on ? wd_r : 0.0f, c = on ? c_r : 0.0f, nb = on ? nb_r : 0.0f;
@@ -553,10 +606,10 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         XCD_TICK(14)
         const float o0 = (1.0f - (float)y) * pv.s - log_sigmoid(pv.s);                           // BCEWithLogits, pos_weight 1 :246
         const float sv = lane == 0 ? pv.s : lane == 1 ? pv.aff : lane == 2 ? pv.na : lane == 3 ? pv.nbn : recn_;
-        if (lane < 5) A.pos_scal[(unsigned)q * 8 + lane] = sv;
+        if (lane < 5) *lane_at(A.pos_scal + (int64_t)q * 8, lane4) = sv;
         const float ov = lane == 0 ? o0 : lane == 1 ? (y == 0 ? pv.aff : 0.0f) : lane == 2 ? (y == 1 ? pv.aff : 0.0f)
                        : lane == 3 ? recn_ : lane == 4 ? (y == 0 ? 1.0f : 0.0f) : (y == 1 ? 1.0f : 0.0f);
-        if (lane < 6) A.pos_o[(unsigned)lane * A.ld_o + q] = ov;
+        if (lane < 6) *lane_at(A.pos_o + q, 4u * (unsigned)lane * (unsigned)A.ld_o) = ov;
       }
     }
     XCD_TICK(2)
@@ -568,14 +621,14 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       RowIn in;
       const int row = ri(rv, 0) >> 6, fl2 = ri(rv, 2), q1 = ri(rv, 4), m2 = ri(rv, 5);
       const int i = row - row0;
-      const unsigned off = (unsigned)row * D + d;
-      in.H1 = cld(S.h1 + off);
-      in.NB = cld(S.nbar + off);
-      in.Gl = (fl2 & 1) ? cld(S.gen + off) : 0.0f;
-      in.pp = cld(A.pos_scal + (unsigned)(lane < 8 ? q1 : i) * 8 + l8);
-      in.nbq = cld(S.nbar + (unsigned)(row0 + q1) * D + d);
-      in.c2 = cld(((m2 & 2) ? S.gen : S.h1) + (unsigned)(m2 >> 2) * D + d);
-      in.xr = (fl2 & 2) ? S.x1[(unsigned)row * XFT + fl] : 0.0f;      // first piece of its row: the row's own item
+      const int64_t off = (int64_t)row * D;                // (uniform: a scalar base per array, d4 the lane offset of all)
+      in.H1 = cld(lane_at(S.h1 + off, d4));
+      in.NB = cld(lane_at(S.nbar + off, d4));
+      in.Gl = (fl2 & 1) ? cld(lane_at(S.gen + off, d4)) : 0.0f;
+      in.pp = cld(lane_at(A.pos_scal, 4u * ((unsigned)(lane < 8 ? q1 : i) * 8 + (unsigned)l8)));
+      in.nbq = cld(lane_at(S.nbar + (int64_t)(row0 + q1) * D, d4));
+      in.c2 = cld(lane_at(((m2 & 2) ? S.gen : S.h1) + (int64_t)(m2 >> 2) * D, d4));
+      in.xr = (fl2 & 2) ? *lane_at(S.x1 + (int64_t)row * XFT, 4u * (unsigned)fl) : 0.0f;      // first piece of its row: the row's own item
       return in;
     };
     RowIn inc[XPC];
@@ -588,7 +641,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       const int k = wid;
       float v = 0.0f;
       for (int g = lane; g < nwg; g += GGAD_WAVE) {
-        const float *po = A.pos_o + (unsigned)k * A.ld_o + 4 * g;
+        const float *po = lane_at(A.pos_o + (int64_t)k * A.ld_o, 16u * (unsigned)g);
         const f2 oa = cld2(po), ob = cld2(po + 2);
         const float o1 = 4 * g + 1 < B ? oa.y : 0.0f, o2 = 4 * g + 2 < B ? ob.x : 0.0f, o3 = 4 * g + 3 < B ? ob.y : 0.0f;
         v += (oa.x + o1) + (o2 + o3);
@@ -632,7 +685,6 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       const int y = fl2 & 1, y1 = (fl2 >> 2) & 1;
       const bool first = (fl2 & 2) != 0;
       const int i = row - row0;
-      const unsigned off = (unsigned)row * D + d;
       const float H1 = in.H1, NB = in.NB, Gl = in.Gl, pp = in.pp, nbq = in.nbq, c2 = in.c2;
       const float s1 = rl(pp, 0), aff1 = rl(pp, 1), na1 = rl(pp, 2), nbn1 = rl(pp, 3), recn_ = rl(pp, 4);
       const float aff2 = rl(pp, 9), na2 = rl(pp, 10), nbn2 = rl(pp, 11);
@@ -657,7 +709,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       float dNb = gq2 * ((c2 * __frcp_rn(nac2)) * inbc2 - (aff2 * inbc2) * cb);
       if (y == 1) {
         const float dZ = (Gv > 0.0f) ? gG : 0.0f;                          // relu(fc(.))
-        if (first && on) S.dz[off] = dZ;
+        if (first && on) *lane_at(S.dz + (int64_t)row * D, d4) = dZ;
         const float dZm = on ? dZ : 0.0f;
         float a = 0.0f;
         a = lds_matvec(fct + d * FCS, 1, dZm);                                                  // fc^T dZ: fc[dd][d] = fct[d][dd]
@@ -665,7 +717,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       }
       ca = (on && H1 > 0.0f) ? gH : 0.0f;
       cg = on ? dNb * __frcp_rn((float)r) : 0.0f;
-      if (first) A.gw_row[(unsigned)i * GGAD_WAVE + lane] = on ? ds * Cc : 0.0f;       // d w = sum_q ds_q * combined_all[:, q]
+      if (first) *lane_at(A.gw_row + (int64_t)i * GGAD_WAVE, lane4) = on ? ds * Cc : 0.0f;       // d w = sum_q ds_q * combined_all[:, q]
     };
     {
       const int vw = rank, v = v0;
@@ -720,8 +772,10 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         PieceX P;
         issue_ops(rv, P);
         const RowIn in = row_load(rv);
+        float WB2[XKS][XNT];
+        load_wb(WB2);
         f4 h[XNT];
-        piece_fwd(P, WB, h);                                // beyond the XPC masks kept from phase A: h2 again, exactly as there
+        piece_fwd(P, WB2, h);                               // beyond the XPC masks kept from phase A: h2 again, exactly as there
         unsigned pos = 0;
 #pragma unroll
         for (int t4 = 0; t4 < XNT; ++t4)
@@ -731,8 +785,8 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       }
       if (more) {                                           // next step's operands: behind every load of this phase, they land
 #pragma unroll
-        for (int jj = 0; jj < XPC; ++jj) issue_ops(recn[jj], xn[jj]);     // during the combine, the barrier and phase E
-      }
+        for (int jj = 0; jj < XPC; ++jj) issue_raw(recn[jj], xn[jj]);     // during the combine; 18 loads in flight, nothing waits for
+      }                                                                   // one of them before the barrier; masked at the hand-over
       // dW partial of the virtual workgroup: its 8 waves in a fixed tree
       XCD_TICK(11)
       __syncthreads();
@@ -748,7 +802,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         if (lg == 0) mine[dw_pos(16, 16 * t4 + la)] = s16;
       }
       __syncthreads();
-      float *out = A.dw_part + (unsigned)vw * XFT * GGAD_WAVE;
+      float *out = A.dw_part + (int64_t)vw * XFT * GGAD_WAVE;
       for (int i = 4 * threadIdx.x; i < XFT * GGAD_WAVE; i += 4 * XT) {     // [f][ch], four channels per thread
         f4 o;
 #pragma unroll
@@ -756,7 +810,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
           const int p = dw_pos(i >> 6, (i & 63) + k);
           o[k] = ((accw[0][p] + accw[1][p]) + (accw[2][p] + accw[3][p])) + ((accw[4][p] + accw[5][p]) + (accw[6][p] + accw[7][p]));
         }
-        *reinterpret_cast<f4 *>(out + i) = o;
+        *reinterpret_cast<f4 *>(lane_at(out, 4u * (unsigned)i)) = o;
       }
     }
     XCD_TICK(4)
@@ -784,22 +838,32 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
       float pw[PWN];
       if (vw < XFT) {
 #pragma unroll
-        for (int k = 0; k < PWN; ++k) pw[k] = cld(A.dw_part + (unsigned)min(wid * PWN + k, nv - 1) * XFT * GGAD_WAVE + vw * GGAD_WAVE + lane);
+        for (int k = 0; k < PWN; ++k) pw[k] = cld(lane_at(A.dw_part + ((int64_t)min(wid * PWN + k, nv - 1) * XFT + vw) * GGAD_WAVE, lane4));
       }
       float ap = 0.0f, am = 0.0f, av = 0.0f;
       if (wid < 5) {
-        const int pl = pidx >= 0 ? pidx : 0;
-        ap = cld(params + pl); am = cld(S.exp_avg + pl); av = cld(S.exp_avg_sq + pl);
+        const unsigned pl4 = 4u * (unsigned)(pidx >= 0 ? pidx : 0);      // one lane offset, three uniform bases
+        ap = cld(lane_at(params, pl4)); am = cld(lane_at(S.exp_avg, pl4)); av = cld(lane_at(S.exp_avg_sq, pl4));
       }
       {
         for (int j0 = wid; j0 < n1; j0 += XW * EU) {         // label-1 rows = sources of the last n1 columns, in order
           float dzr[EU], nbr[EU];
+          int rav[EU];                                              // the block's row ids: EU LDS reads in flight (a block beyond the XRA
+          if (min(j0 + (EU - 1) * XW, n1 - 1) < XRA && !(A.dbg & 2)) {   // listed rows: global memory; a uniform branch, never a flat load)
+#pragma unroll
+            for (int u = 0; u < EU; ++u) rav[u] = ra_lds[min(j0 + u * XW, n1 - 1)];
+          } else {
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+              const int j = min(j0 + u * XW, n1 - 1);
+              rav[u] = j < XRA && !(A.dbg & 2) ? ra_lds[j] : (S.pos_meta[row0 + n0 + j] >> 2);
+            }
+          }
 #pragma unroll
           for (int u = 0; u < EU; ++u) {
-            const int j = min(j0 + u * XW, n1 - 1);
-            const int ra = (j < XRA && !(A.dbg & 2)) ? ra_lds[j] : (S.pos_meta[row0 + n0 + j] >> 2);
-            dzr[u] = cld(S.dz + (unsigned)ra * D + d);
-            nbr[u] = cld(S.nbar + (unsigned)ra * D + d);
+            const int ra = uni(rav[u]);
+            dzr[u] = cld(lane_at(S.dz + (int64_t)ra * D, d4));
+            nbr[u] = cld(lane_at(S.nbar + (int64_t)ra * D, d4));
           }
 #pragma unroll
           for (int u = 0; u < EU; ++u) {
@@ -818,12 +882,13 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         for (int i0 = wid; i0 < B; i0 += XW * EU) {
           float gr[EU];
 #pragma unroll
-          for (int u = 0; u < EU; ++u) gr[u] = cld(A.gw_row + (unsigned)min(i0 + u * XW, B - 1) * GGAD_WAVE + lane);
+          for (int u = 0; u < EU; ++u) gr[u] = cld(lane_at(A.gw_row + (int64_t)min(i0 + u * XW, B - 1) * GGAD_WAVE, lane4));
 #pragma unroll
           for (int u = 0; u < EU; ++u) gw += (i0 + u * XW < B) ? gr[u] : 0.0f;
         }
       }
-      __syncthreads();
+      asm volatile("" : "+v"(ap), "+v"(am), "+v"(av));      // first use of the optimiser state HERE: as plain values the first Adam product was
+      __syncthreads();                                      // moved up behind their loads, a full wait in front of the label-1 row loads
       accw[wid][lane] = gW; accw[wid][64 + lane] = gw;
 #pragma unroll
       for (int k = 0; k < 3; ++k) accw[wid][128 + 64 * k + lane] = gf[k];
@@ -832,7 +897,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
         float g = 0.0f;
 #pragma unroll
         for (int k = 0; k < XW; ++k) g += accw[k][sel + lane];              // fixed order
-        S.grads[pidx] = g;
+        *lane_at(S.grads, 4u * (unsigned)pidx) = g;
         if (MODE == 2) g = xchg_sum(A.X, A.xstep0 + (uint32_t)b + 1u, pidx, g) * A.grad_scale;
         adam_apply(params, S.exp_avg, S.exp_avg_sq, L, pidx, ap, am, av, g, S.weight_decay, sc[0], sc[1]);
       }
@@ -842,7 +907,7 @@ __global__ void __launch_bounds__(XT) k_train_chunk_xcd(XcdArgs A) {
     XCD_TICK(7)
     if (more) {                                             // step b + 1's records and operands become the current ones
 #pragma unroll
-      for (int j = 0; j < XPC; ++j) { recv[j] = recn[j]; xc[j] = xn[j]; }
+      for (int j = 0; j < XPC; ++j) { recv[j] = recn[j]; xc[j] = xn[j]; mask_piece_x(piece_n(recv[j]), lane, xc[j]); }
       posv = posn;
     }
   }
@@ -1101,6 +1166,7 @@ int ggad_mb_train_chunk_xcd(const ggad_mb_step *tmpl, int32_t n_batches, const i
                s.labels && s.pos_meta && s.row_pos && s.h1 && s.nbar && s.gen && s.dz && s.row_ck_ptr && s.ck_rc && s.ck_e0 &&
                s.chunk_part);
   GGAD_REQUIRE(s.F == XFT && s.D >= 1 && s.D <= GGAD_MAX_D && ((uintptr_t)workspace & 15) == 0);
+  GGAD_REQUIRE(max_rows <= (1 << 24));                      // 32-bit byte offsets inside one batch's block of pos_o / pos_scal (lane_at)
   if (n_batches == 0) return GGAD_OK;
   XcdArgs A;
   A.s = s;
