@@ -258,6 +258,10 @@ SIGNATURES = {
     "ggad_tam_head_workspace_elems": (c_int64, [_I, _I, _I, _I]),
     "ggad_tam_head_fwd_f32": (c_int32, [_P] * 6 + [_F, _I, _I, _P, _P, _I, _I] + [_P] * 6),
     "ggad_tam_head_bwd_f32": (c_int32, [_P] * 6 + [_F, _I, _I, _P, _P, _I, _I] + [_P] * 7),
+    "ggad_tam_nsgt_transpose_map": (c_int32, [_P, _P, _I, _P, _P, _P]),
+    "ggad_tam_nsgt_rowstat": (c_int32, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "ggad_tam_nsgt_compact": (c_int32, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ggad_tam_nsgt_cut": (c_int32, [_P, _P, _P, _P, _I, _L, _P, _P, _P]),
 }
 
 

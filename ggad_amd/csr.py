@@ -175,6 +175,28 @@ class Csr:
         self.dev = dev
         self._plans = {}
 
+    @classmethod
+    def from_device(cls, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, shape):
+        """A Csr over arrays that are ALREADY on the device and canonical (int32 rowptr [rows + 1] / col, fp32 val, columns sorted and
+        distinct inside a row): they are kept as they are, and downloaded once into the host matrix the plan builders read -- no
+        `sum_duplicates`, no `sort_indices`, no upload."""
+        import scipy.sparse as sp
+        if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or val.dtype != torch.float32:
+            raise TypeError("Csr.from_device takes int32 rowptr / col and fp32 val")
+        if rowptr.numel() != int(shape[0]) + 1 or col.numel() != val.numel():
+            raise ValueError("Csr.from_device: array lengths do not fit the shape")
+        self = cls.__new__(cls)
+        self.shape = (int(shape[0]), int(shape[1]))
+        self.nnz = int(col.numel())
+        self.rowptr, self.col, self.val = rowptr.contiguous(), col.contiguous(), val.contiguous()
+        m = sp.csr_matrix((val.cpu().numpy(), col.cpu().numpy(), rowptr.cpu().numpy()), shape=self.shape)
+        m.has_sorted_indices = True
+        m.has_canonical_format = True
+        self.host = m
+        self.dev = val.device
+        self._plans = {}
+        return self
+
     def entries(self) -> torch.Tensor:
         """(column, bits of the value) per stored entry, interleaved int32 (what k_spmm_rowline fetches with one 8-byte load)."""
         e = self._plans.get("entries")

@@ -73,6 +73,23 @@ class FullGraphAdj:
         return t
 
     @classmethod
+    def with_adjacency(cls, base: "FullGraphAdj", rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor):
+        """`base` with another A_hat, taken from device arrays (canonical CSR: `Csr.from_device`) that are SYMMETRIC by construction
+        (TAM's truncated graphs, `tam_utils.DeviceNsgt.step`): A_hat is its own transpose and nothing is re-checked on the host.
+        Everything of the raw adjacency -- `Rt`, `r_inv`, `raw_host`, the small device vectors -- and the `TamHead`s cached on `base` so
+        far are base's own objects; what depends on A_hat (row plans, the cached A_hat X) starts empty."""
+        self = cls.__new__(cls)
+        self.dev, self.n = base.dev, base.n
+        self.A = Csr.from_device(rowptr, col, val, (base.n, base.n))
+        self.symmetric = True
+        self.At = self.A
+        self.raw_host, self.Rt, self.r_inv_host = base.raw_host, base.Rt, base.r_inv_host
+        self._abn, self._loss, self._ax = {}, {}, {}
+        self._head = {k: h for k, h in base._head.items() if k[0] == "tam"}       # (the GGAD head structs hold row plans of A_hat)
+        self._devc = base._devc
+        return self
+
+    @classmethod
     def from_dense(cls, adj, raw_adj, device):
         import scipy.sparse as sp
         a = adj.detach().cpu().numpy() if isinstance(adj, torch.Tensor) else np.asarray(adj)

@@ -1,13 +1,17 @@
 """Host / device helpers of the full-graph TAM comparison model (`tam.py`, `utils_tam.py` of the reference) on CSR matrices.
 
 The reference holds the adjacency, the distance table and every truncated graph as dense N x N tensors and walks them row by
-row in Python; here they are CSR (scipy on the host for the once-per-cut truncation, whose only sequential part is the
-order of numpy's random draws; HIP kernels for everything per epoch):
+row in Python; here they are CSR and HIP kernels do everything per epoch.  The once-per-cut truncation has two paths that give
+the same graphs, bit for bit, and leave numpy's stream at the same position: scipy on the host (`graph_nsgt` +
+`normalize_adj_tensor`, the default) and `DeviceNsgt` (csrc/tam_nsgt.hip, `tam.py --device_cut`), which keeps the current graph
+as a byte mask over the entries of A + I and leaves only three small rounding-sensitive quantities to the host (the fp32 mean
+of the live distances, the per-row thresholds with their random draws, colsum^-1/2):
 
     load_mat / split_nodes            `utils_tam.py:140-179`   (python `random` driven split, incl. its index quirk)
     calc_distance                     `utils_tam.py:190-199`   -> `ggad_edge_dist_f32`, one value per stored entry of A + I
     graph_nsgt                        `utils_tam.py:222-240`   -> vectorised over rows, same draws from numpy's stream
     normalize_adj_tensor              `utils_tam.py:45-53`
+    DeviceNsgt                        both of the above        -> `ggad_tam_nsgt_*` (opt-in; thresholds from `nsgt_thresholds` too)
     max_message / inference           `tam.py:113-146`         -> `AffinityFn` (HIP row-normalise, CSR SpMM, row dots)
                                                                -> opt-in: `TamHeadFn` / `max_message_fused` (csrc/tam.hip)
 """
@@ -63,13 +67,40 @@ def load_mat(dataset: str, root: str = "./data"):
 def calc_distance(raw, feats: torch.Tensor) -> np.ndarray:
     """Attribute distance of every stored entry of `raw` (scipy CSR of A + I, sorted indices), aligned with `raw.indices`.
     The reference's N x N `dis_array` holds exactly these values at the non-zero positions of raw_adj and 0 elsewhere."""
+    return calc_distance_dev(raw, feats).cpu().numpy()
+
+
+def calc_distance_dev(raw, feats: torch.Tensor) -> torch.Tensor:
+    """`calc_distance` with the values left on the device (what `DeviceNsgt` reads)."""
     dev = feats.device
     x = feats.reshape(-1, feats.shape[-1]).contiguous().float()
     rp = torch.from_numpy(raw.indptr.astype(np.int32)).to(dev)
     ci = torch.from_numpy(raw.indices.astype(np.int32)).to(dev)
     out = torch.empty(raw.nnz, dtype=torch.float32, device=dev)
     call("ggad_edge_dist_f32", ptr(rp), ptr(ci), ptr(x), raw.shape[0], x.shape[1], ptr(out))
-    return out.cpu().numpy()
+    return out
+
+
+def nsgt_thresholds(mx: np.ndarray, cnt: np.ndarray, mean_dis, nprandom=np.random) -> np.ndarray:
+    """The cut threshold of every row (`utils_tam.py:228-236`), shared by `graph_nsgt` and `DeviceNsgt.step` so that the two cannot
+    drift apart.  `mx[i]` / `cnt[i]`: the largest distance and the number of the current entries of row i (mx of an empty row is not
+    read); `mean_dis`: the fp32 mean of the current non-zero distances.  A row with entries whose largest distance exceeds the mean
+    takes ONE number from numpy's global stream, in row order, and gets mean + u (max - mean) in fp32; every other row gets +inf
+    (nothing is farther than that: the row keeps all its entries)."""
+    n = len(cnt)
+    rows = np.nonzero(np.asarray(cnt) > 0)[0]
+    mxr = np.asarray(mx, dtype=np.float32)[rows]
+    qual = mxr > mean_dis
+    u = nprandom.random_sample(int(qual.sum()))                  # one draw per qualifying row, in row order
+    thr = np.full(n, np.inf, dtype=np.float32)
+    mean32 = np.float32(mean_dis)
+    thr[rows[qual]] = (mxr[qual] - mean32).astype(np.float32) * u.astype(np.float32) + mean32
+    return thr
+
+
+def _nsgt_mean(nz: np.ndarray):
+    """fp32 mean of the non-zero distances in torch's summation order (the reference's `torch.mean`); nan without any."""
+    return torch.from_numpy(nz).mean().numpy() if len(nz) else np.float32("nan")
 
 
 def graph_nsgt(raw, dis_vals: np.ndarray, adj, nprandom=np.random):
@@ -90,15 +121,12 @@ def graph_nsgt(raw, dis_vals: np.ndarray, adj, nprandom=np.random):
     if len(pos) and (pos.max() >= len(key_raw) or not np.array_equal(key_raw[pos], key_adj)):
         raise ValueError("graph_nsgt: the current graph has an entry the original one lacks")
     dis = np.asarray(dis_vals, dtype=np.float32)[pos]
-    nz = dis[dis != 0]
-    mean_dis = torch.from_numpy(nz).mean().numpy() if len(nz) else np.float32("nan")      # fp32 mean, torch's summation order
+    mean_dis = _nsgt_mean(dis[dis != 0])
     rows = np.nonzero(deg > 0)[0]
-    mx = np.maximum.reduceat(dis, adj.indptr[rows]) if len(rows) else np.zeros(0, np.float32)
-    qual = mx > mean_dis
-    u = nprandom.random_sample(int(qual.sum()))                  # one draw per qualifying row, in row order
-    thr = np.full(n, np.inf, dtype=np.float32)
-    mean32 = np.float32(mean_dis)
-    thr[rows[qual]] = (mx[qual] - mean32).astype(np.float32) * u.astype(np.float32) + mean32
+    mx = np.zeros(n, dtype=np.float32)
+    if len(rows):
+        mx[rows] = np.maximum.reduceat(dis, adj.indptr[rows])
+    thr = nsgt_thresholds(mx, deg, mean_dis, nprandom)
     keep = ~(dis > np.repeat(thr, deg))
     cut = sp.csr_matrix((keep.astype(np.float32), adj.indices.copy(), adj.indptr.copy()), shape=adj.shape)
     cut.eliminate_zeros()                                        # (in place: hence the copies above)
@@ -120,6 +148,118 @@ def normalize_adj_tensor(adj):
     rows = np.repeat(np.arange(adj.shape[0]), np.diff(adj.indptr))
     vals = (r[rows] * (adj.data * r[adj.indices]).astype(np.float32)).astype(np.float32)
     return sp.csr_matrix((vals, adj.indices.copy(), adj.indptr.copy()), shape=adj.shape)
+
+
+class _NsgtStatic:
+    """What every tree of a run shares: the CSR of raw = A + I with its distances and transpose map on the device, the scratch of a
+    step (steps run one after the other on one stream) and the pinned staging buffer of the distances."""
+
+    def __init__(self, raw, dis_vals, device):
+        import scipy.sparse as sp
+        dev = torch.device(device)
+        raw = sp.csr_matrix(raw)
+        if raw.shape[0] != raw.shape[1]:
+            raise ValueError("DeviceNsgt needs a square adjacency")
+        if not raw.has_canonical_format:
+            raw = raw.copy()
+            raw.sum_duplicates()
+            raw.sort_indices()
+        if raw.nnz >= 2 ** 31:
+            raise ValueError("matrix too large for int32 CSR")
+        n, nnz = int(raw.shape[0]), int(raw.nnz)
+        self.dev, self.n, self.nnz = dev, n, nnz
+        self.indptr, self.indices = raw.indptr.astype(np.int64), raw.indices.astype(np.int32)
+        self.rowptr = torch.from_numpy(raw.indptr.astype(np.int32)).to(dev)
+        self.col = torch.from_numpy(self.indices).to(dev)
+        if isinstance(dis_vals, torch.Tensor):
+            self.dis = dis_vals.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        else:
+            self.dis = torch.from_numpy(np.ascontiguousarray(dis_vals, dtype=np.float32).reshape(-1)).to(dev)
+        if self.dis.numel() != nnz:
+            raise ValueError("DeviceNsgt: one distance per stored entry of raw is needed")
+        self.tpos = torch.empty(max(1, nnz), dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        call("ggad_tam_nsgt_transpose_map", ptr(self.rowptr), ptr(self.col), n, ptr(self.tpos), ptr(status))
+        if int(status.item()) != 0:
+            raise ValueError("DeviceNsgt needs a raw adjacency with a symmetric pattern (the reference's adj + adj.T would leave the "
+                             "pattern of A + I otherwise); use the host path (`graph_nsgt` / `normalize_adj_tensor`) for this graph")
+        self.keep = torch.empty(max(1, nnz), dtype=torch.uint8, device=dev)
+        self.nz = torch.empty(max(1, nnz), dtype=torch.float32, device=dev)          # the live non-zero distances, CSR order
+        self.nz_ptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        self.scan_ws = torch.empty(max(1, int(_lib.load().ggad_scan_workspace_elems(n))), dtype=torch.int32, device=dev)
+        self.stat_mx = torch.empty(max(1, n), dtype=torch.float32, device=dev)
+        self.thr = torch.empty(max(1, n), dtype=torch.float32, device=dev)
+        self.r = torch.empty(max(1, n), dtype=torch.float32, device=dev)
+        self.stage = torch.empty(max(1, nnz), dtype=torch.float32, pin_memory=True)
+        self.stage_np = self.stage.numpy()
+
+    def rowstat(self, alive, stat_i):
+        """(cnt, mx, nzcnt) of the rows of the graph `alive` on the host; the two counts stay in `stat_i` (2 x n int32) on the device."""
+        call("ggad_tam_nsgt_rowstat", ptr(self.rowptr), ptr(self.dis), ptr(alive), self.n, ptr(stat_i[0]), ptr(self.stat_mx),
+             ptr(stat_i[1]))
+        si = stat_i.cpu().numpy()
+        return si[0, :self.n].copy(), self.stat_mx.cpu().numpy()[:self.n], si[1, :self.n].copy()
+
+
+class DeviceNsgt:
+    """`graph_nsgt` + `normalize_adj_tensor` of one tree on the device (csrc/tam_nsgt.hip).  `raw`: scipy CSR of A + I with a SYMMETRIC
+    pattern (ValueError otherwise); `dis_vals`: the distance of each of its entries (`calc_distance`, or `calc_distance_dev`'s tensor).
+    The current graph is a byte per entry of raw; a `step` is a few streaming passes over them and gives exactly what the host path
+    gives: the same pattern, the same bits in every normalised value, numpy's stream at the same position.  Three quantities are
+    rounding-sensitive and therefore come from the host calls `graph_nsgt` / `normalize_adj_tensor` make: the fp32 mean of the live
+    non-zero distances (torch's summation order over the vector the device compacts), the thresholds (`nsgt_thresholds`, O(n)) and
+    r = colsum^-1/2 (`torch.pow` on the n live row counts -- the column sums, the pattern being symmetric)."""
+
+    def __init__(self, raw, dis_vals, device, _static=None):
+        s = self._s = _static if _static is not None else _NsgtStatic(raw, dis_vals, device)
+        self.alive = torch.ones(max(1, s.nnz), dtype=torch.uint8, device=s.dev)
+        if _static is None:                        # per row: live entries / live non-zero distances (device), + the maximum (host)
+            self._stat_i = torch.empty((2, max(1, s.n)), dtype=torch.int32, device=s.dev)
+            s.stat0 = s.rowstat(self.alive, self._stat_i)
+            s.stat0_i = self._stat_i.clone()
+        else:
+            self._stat_i = s.stat0_i.clone()
+        self._stat = s.stat0
+
+    def fork(self) -> "DeviceNsgt":
+        """Another tree over the same raw graph: shares the static part, owns a fresh all-alive mask."""
+        return DeviceNsgt(None, None, None, _static=self._s)
+
+    def step(self, nprandom=np.random):
+        """One truncation round: advances the mask and returns (rowptr, col, val), device tensors of the truncated, normalised graph
+        (canonical CSR, int32 / int32 / fp32)."""
+        s = self._s
+        n, dev = s.n, s.dev
+        cnt, mx, nzc = self._stat
+        args = (ptr(s.rowptr), ptr(s.col), ptr(s.dis), ptr(self.alive), n)
+        tot = int(nzc.sum())
+        call("ggad_tam_nsgt_compact", *args, 0, ptr(self._stat_i[1]), None, ptr(s.nz_ptr), None, ptr(s.nz), ptr(s.scan_ws))
+        s.stage[:tot].copy_(s.nz[:tot], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        mean_dis = _nsgt_mean(s.stage_np[:tot])
+        s.thr[:n].copy_(torch.from_numpy(nsgt_thresholds(mx, cnt, mean_dis, nprandom)))
+        call("ggad_tam_nsgt_cut", ptr(s.rowptr), ptr(s.dis), ptr(s.tpos), ptr(s.thr), n, s.nnz, ptr(self.alive), ptr(s.keep))
+        cnt, mx, nzc = self._stat = s.rowstat(self.alive, self._stat_i)
+        r = torch.pow(torch.from_numpy(cnt.astype(np.float32)), -0.5)      # colsum = live row count: the pattern is symmetric
+        r[torch.isinf(r)] = 0.0
+        s.r[:n].copy_(r)
+        total = int(cnt.sum())
+        rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        col = torch.empty(total, dtype=torch.int32, device=dev)
+        val = torch.empty(total, dtype=torch.float32, device=dev)
+        call("ggad_tam_nsgt_compact", *args, 1, ptr(self._stat_i[0]), ptr(s.r), ptr(rowptr), ptr(col), ptr(val), ptr(s.scan_ws))
+        return rowptr, col, val
+
+    def pattern(self):
+        """The current graph as a host scipy CSR (data = 1), like `graph_nsgt` returns it."""
+        import scipy.sparse as sp
+        s = self._s
+        live = self.alive[:s.nnz].cpu().numpy().astype(bool)
+        rows = np.repeat(np.arange(s.n, dtype=np.int64), np.diff(s.indptr))[live]
+        indptr = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=s.n)))).astype(np.int32)
+        m = sp.csr_matrix((np.ones(int(live.sum()), np.float32), s.indices[live], indptr), shape=(s.n, s.n))
+        m.has_sorted_indices = True
+        return m
 
 
 class AffinityFn(torch.autograd.Function):
@@ -282,19 +422,23 @@ def normalize_score(ano_score: np.ndarray) -> np.ndarray:
 
 
 def train_cut(model, optimiser, features: torch.Tensor, adj: FullGraphAdj, normal_label_idx, num_epoch: int, use_graph: bool = True,
-              log_every: int = 0, fused: bool = False):
+              log_every: int = 0, fused: bool = False, head: "TamHead" = None):
     """The epoch loop of one truncation round (`tam.py:186-201`): forward, `max_message` loss, `inference`, backward, Adam step.
     The reference calls `zero_grad()` ONCE per round (`:182`), so the gradients of a round accumulate from epoch to epoch;
     the caller does the same (this function never clears them).  After two eager epochs the epoch (forward, both affinity
     passes, backward into the accumulating gradients, fused Adam) is captured into one hipGraph and replayed.
     `fused=True`: the loss comes from `max_message_fused` and the round's message is that call's raw affinity; the second
-    `inference` pass (which recomputes the same numbers from the same embedding) is not run.
+    `inference` pass (which recomputes the same numbers from the same embedding) is not run.  `head`: with `fused`, a `TamHead` of
+    (the raw adjacency of adj, normal_label_idx) built beforehand, used instead of a new one (it does not depend on the round's graph).
     Returns (losses [num_epoch] fp32 tensor on the device, message of the last epoch)."""
     dev = features.device
     idx = torch.as_tensor(np.asarray(normal_label_idx, dtype=np.int64), device=dev)
     losses = torch.zeros(max(1, int(num_epoch)), dtype=torch.float32, device=dev)
     state = {}
-    head = TamHead(adj, normal_label_idx) if fused else None
+    if not fused:
+        head = None
+    elif head is None:
+        head = TamHead(adj, normal_label_idx)
 
     def epoch():
         node_emb, feat1, feat2 = model.forward(features, adj)

@@ -1086,6 +1086,35 @@ int ggad_tam_head_bwd_f32(const int32_t *rowptr, const int32_t *col, const float
                           int32_t n_hub, int32_t n_pieces, const float *a, const float *scal, const float *inv, const float *g,
                           float *d_emb, float *workspace, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * TAM's truncation round on the device (tam_nsgt.hip; reference utils_tam.py:222-240 and :45-53).  (rowptr, col): the CSR of
+ * raw = A + I over n nodes, columns sorted inside a row, nnz = rowptr[n] < 2^31 entries, SYMMETRIC pattern; dis: one distance per
+ * entry; alive: one byte per entry, non-zero = the entry is in the current graph.  Every launch goes on `stream`; no floating-point
+ * atomics; one wave walks one row.
+ *
+ * ggad_tam_nsgt_transpose_map  tpos[e] = position of entry (j, i) for entry e = (i, j).  *status (device word, zeroed by the call)
+ *                              is 0 afterwards if every entry has its mirror; bit 0: some entry has none, bit 1: a column is
+ *                              outside [0, n).  tpos of such an entry is e itself, so tpos always stays inside [0, nnz).
+ * ggad_tam_nsgt_rowstat        per row over the live entries: cnt = their number, mx = the largest dis (-inf for a row without
+ *                              live entries; a NaN distance is ignored), nzcnt = the number with dis != 0.
+ * ggad_tam_nsgt_compact        out_rowptr (n + 1) = exclusive scan of counts (n), out_rowptr[n] = their sum, then per row in
+ *                              ascending column order:  mode 0: out_val = dis of the live entries with dis != 0 (counts = nzcnt;
+ *                              r and out_col may be NULL);  mode 1: out_col = the columns of the live entries, out_val = r[i] * r[j]
+ *                              as one rounded fp32 product (counts = cnt).  out_col / out_val hold sum(counts) elements; a row
+ *                              never writes at or past out_rowptr[i + 1].  workspace: ggad_scan_workspace_elems(n) int32.
+ * ggad_tam_nsgt_cut            keep[e] = alive[e] && !(dis[e] > thr[row of e]), then alive[e] = keep[e] | keep[tpos[e]] (an entry
+ *                              survives if either direction does).  Two launches; keep: nnz bytes of scratch, not alive itself.
+ * ---------------------------------------------------------------------------------- */
+int ggad_tam_nsgt_transpose_map(const int32_t *rowptr, const int32_t *col, int32_t n, int32_t *tpos, int32_t *status,
+                                ggad_stream_t stream);
+int ggad_tam_nsgt_rowstat(const int32_t *rowptr, const float *dis, const uint8_t *alive, int32_t n, int32_t *cnt, float *mx,
+                          int32_t *nzcnt, ggad_stream_t stream);
+int ggad_tam_nsgt_compact(const int32_t *rowptr, const int32_t *col, const float *dis, const uint8_t *alive, int32_t n, int32_t mode,
+                          const int32_t *counts, const float *r, int32_t *out_rowptr, int32_t *out_col, float *out_val,
+                          int32_t *workspace, ggad_stream_t stream);
+int ggad_tam_nsgt_cut(const int32_t *rowptr, const float *dis, const int32_t *tpos, const float *thr, int32_t n, int64_t nnz,
+                      uint8_t *alive, uint8_t *keep, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

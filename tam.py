@@ -9,7 +9,8 @@ PYTHONHASHSEED (its `random` / `numpy` / `torch` seeding is commented out, `:42-
 be repeated.  Adjacency, distances and truncated graphs are CSR; the GCN layers, both affinity passes, the backward and Adam
 run in the kernels of libggad_hip.so; after two eager epochs every epoch of a round is one replayed hipGraph.
 `--synthetic` / `--device` / `--quiet` / `--no_graph` / `--num_epoch` / `--lr` / `--fused_head` (the affinity head and its loss in
-the fused kernels of `csrc/tam.hip`, off by default) are additions.
+the fused kernels of `csrc/tam.hip`, off by default) / `--device_cut` (the truncation between two rounds in the kernels of
+`csrc/tam_nsgt.hip` instead of scipy on the host: same graphs, same draws from numpy's stream; off by default) are additions.
 """
 import argparse
 import os
@@ -29,7 +30,7 @@ from ggad_amd.model_tam import Model  # noqa: E402
 from ggad_amd.utils import preprocess_features  # noqa: E402
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser(description="Truncated Affinity Maximization for Graph Anomaly Detection")
     p.add_argument("--dataset", type=str, default="photo")
     p.add_argument("--lr", type=float)
@@ -51,7 +52,9 @@ def parse():
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--no_graph", action="store_true", help="do not replay a captured hipGraph of the training epoch")
     p.add_argument("--fused_head", action="store_true", help="affinity head and loss in the fused kernels of csrc/tam.hip")
-    a = p.parse_args()
+    p.add_argument("--device_cut", action="store_true",
+                   help="truncate and normalise the graph between two rounds on the device (csrc/tam_nsgt.hip) instead of in scipy")
+    a = p.parse_args(argv)
     if a.lr is None:
         a.lr = 1e-5                                                    # tam.py:35
     if a.num_epoch is None:
@@ -111,31 +114,63 @@ def main():
             coo = raw.tocoo()
             dis_vals = np.asarray(cand[coo.row, coo.col], dtype=np.float32)
     if dis_vals is None:
-        dis_vals = T.calc_distance(raw, feats[0])                      # one value per entry of A + I      tam.py:168
+        dis_vals = T.calc_distance_dev(raw, feats[0])                  # one value per entry of A + I      tam.py:168
+        if not args.device_cut:
+            dis_vals = dis_vals.cpu().numpy()                          # (--device_cut: they stay on the device)
         if not args.synthetic:
             os.makedirs("distance_save", exist_ok=True)
-            np.save(dis_path, dis_vals)
-    all_cut = [raw.copy() for _ in range(args.N_tree)]                 # tam.py:159-161
+            np.save(dis_path, dis_vals.cpu().numpy() if args.device_cut else dis_vals)
+    _, _, epoch_times = train_rounds(args, dev, raw, dis_vals, feats, models, optimisers, normal_label_idx, y_all, idx_test_dev)
+    end = time.time()
+    print(end - start)
+    print("epochs/s (training windows of all rounds): {:.1f}; nodes/s: {:.1f}".format(
+        1.0 / float(np.mean(epoch_times)), nb_nodes / float(np.mean(epoch_times))))
+
+
+def train_rounds(args, dev, raw, dis_vals, feats, models, optimisers, normal_label_idx, y_all, idx_test_dev):
+    """The `--cutting` x `--N_tree` loop of `tam.py:172-232` with its prints: round-major, tree-minor, so that numpy's stream is drawn
+    from in the reference's order on either truncation path.  Returns (the loss tensors and the messages of every (round, tree) in
+    that order, the seconds per epoch of each)."""
+    if args.device_cut:
+        # the raw graph once: its CSR, distances and transpose map for the truncation, R / r_inv / the fused head for every round
+        trees = [T.DeviceNsgt(raw, dis_vals, dev)]
+        trees += [trees[0].fork() for _ in range(1, args.N_tree)]
+        ones = sp.csr_matrix((np.ones(raw.nnz, np.float32), raw.indices, raw.indptr), shape=raw.shape)
+        base = FullGraphAdj(T.normalize_adj_tensor(ones), raw, dev)
+        head = T.tam_head(base, normal_label_idx) if args.fused_head else None
+    else:
+        all_cut = [raw.copy() for _ in range(args.N_tree)]             # tam.py:159-161
+        head = None
     index = 0
     message_mean_list = []
     epoch_times = []
+    all_losses, all_messages = [], []
     for n_cut in range(args.cutting):
         print("n_cut.{}".format(n_cut))
         message_list = []
         for n_t in range(args.N_tree):
-            cut = T.graph_nsgt(raw, dis_vals, all_cut[n_t])            # tam.py:180
+            if args.device_cut:
+                csr = trees[n_t].step()                                # tam.py:180 and utils_tam.py:45-53
+            else:
+                cut = T.graph_nsgt(raw, dis_vals, all_cut[n_t])        # tam.py:180
             optimisers[index].zero_grad()                              # once per round                    tam.py:181
             print("<<<< cutting num .{}<<<<<<".format(n_cut))
-            full = FullGraphAdj(T.normalize_adj_tensor(cut), raw, dev)
+            if args.device_cut:
+                full = FullGraphAdj.with_adjacency(base, *csr)
+            else:
+                full = FullGraphAdj(T.normalize_adj_tensor(cut), raw, dev)
             torch.cuda.synchronize()
             t0 = time.time()
             losses, message_sum = T.train_cut(models[index], optimisers[index], feats, full, normal_label_idx, args.num_epoch,
                                               use_graph=not args.no_graph, log_every=0 if args.quiet else 50,
-                                              fused=args.fused_head)
+                                              fused=args.fused_head, head=head)
             torch.cuda.synchronize()
             epoch_times.append((time.time() - t0) / max(1, args.num_epoch))
             message_list.append(message_sum.detach().unsqueeze(0))
-            all_cut[n_t] = cut
+            all_losses.append(losses)
+            all_messages.append(message_sum.detach().clone())
+            if not args.device_cut:
+                all_cut[n_t] = cut
             index += 1
         for mes in message_list:                                       # tam.py:203-207
             m = mes[0]
@@ -151,10 +186,7 @@ def main():
         score = 1 - (mm - mm.min()) / (mm.max() - mm.min())
         print("AP:", average_precision(score, y_all))
         print("{} AUC:{:.4f}".format(args.dataset, roc_auc(score, y_all)))
-    end = time.time()
-    print(end - start)
-    print("epochs/s (training windows of all rounds): {:.1f}; nodes/s: {:.1f}".format(
-        1.0 / float(np.mean(epoch_times)), nb_nodes / float(np.mean(epoch_times))))
+    return all_losses, all_messages, epoch_times
 
 
 if __name__ == "__main__":
