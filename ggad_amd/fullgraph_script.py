@@ -1,7 +1,7 @@
 """What the full-graph entry scripts (`run.py`, `ocgnn.py`, `anomalyDAE.py`, `aegis.py`, `gaan.py`, `dominant.py`, `tam.py`) share:
 the command line the reference's scripts have in common, the loader (a `.mat` file or a synthetic graph of the published size),
-feature / adjacency preparation, process setup, the capture of the training epoch as a hipGraph, the per-epoch noise feed of
-`gaan.py` / `aegis.py`, and the closing prints.  What differs between the scripts -- their defaults, print cadence and timed window
+feature / adjacency preparation, process setup, the capture of the training epoch as a hipGraph (`capture` / `CapturedEpoch`, which the
+mini-batch loop of `model_handler_dominate.py` uses too), the per-epoch noise feed of `gaan.py` / `aegis.py`, and the closing prints.  What differs between the scripts -- their defaults, print cadence and timed window
 -- stays in the scripts.
 """
 from __future__ import annotations
@@ -156,25 +156,29 @@ def capture(epoch_fn, before=None):
 
 class CapturedEpoch:
     """A training loop's epoch: eager (allocations, plan caches, Adam state) until epoch `at`, captured there -- if `enabled` and
-    `gate()` holds -- and replayed from that epoch on."""
+    `gate()` holds -- and replayed from that epoch on.  The mini-batch handlers pass `step` a `key` (the addresses of the epoch's
+    plan buffers, which the captured launches hold): from epoch `at` on a key other than the one captured under is captured again."""
 
     def __init__(self, epoch_fn, *, enabled=True, at=2, before_capture=None, after_capture=None, gate=None):
         self.epoch_fn, self.enabled, self.at = epoch_fn, enabled, at
         self.before_capture, self.after_capture, self.gate = before_capture, after_capture, gate
-        self.graph = self.static = None
+        self.graph = self.static = self.key = None
 
     @property
     def captured(self) -> bool:
         return self.graph is not None
 
-    def step(self, epoch, before_replay=None):
+    def step(self, epoch, before_replay=None, key=None):
         """Run epoch `epoch`; returns what `epoch_fn` returns (once captured: the static outputs).  `before_replay` runs ahead of every
-        replay, the capturing epoch's included: the place to refill a buffer the captured epoch reads."""
-        if self.enabled and self.graph is None and epoch == self.at and (self.gate is None or self.gate()):
+        replay, the capturing epoch's included: the place to refill a buffer the captured epoch reads.  Without a `key` the one
+        capture is due at epoch `at`; with one, from `at` on whenever there is no graph or it was captured under another key."""
+        due = self.graph is None and epoch == self.at if key is None else epoch >= self.at and (self.graph is None or key != self.key)
+        if self.enabled and due and (self.gate is None or self.gate()):
             self.graph, self.static = capture(self.epoch_fn, self.before_capture)
+            self.key = key
             if self.after_capture is not None:
                 self.after_capture()
-        if self.graph is None:
+        if self.graph is None or key != self.key:
             return self.epoch_fn()
         if before_replay is not None:
             before_replay()

@@ -78,6 +78,52 @@ def _node_array(nodes) -> np.ndarray:
     return np.asarray(nodes, dtype=np.int64).reshape(-1)
 
 
+def _ragged_weights(nodes, to_neighs, device):
+    """(seg_ptr, cols, w) on `device` for the ragged weighted gather kernel (`ggad_seg_wsum`) of the comparison models' aggregators:
+    row i holds N(i) + {i} in ascending order with weights mask.div(row).div(col), the counts taken over the rows of THIS batch
+    (`src/graphsage_dominant.py:194-216`)."""
+    nodes = _node_array(nodes)
+    samp = [set(tn).union({int(nodes[i])}) for i, tn in enumerate(to_neighs)]
+    sizes = np.fromiter((len(s) for s in samp), dtype=np.int64, count=len(samp))
+    seg_ptr = np.zeros(len(samp) + 1, dtype=np.int32)
+    np.cumsum(sizes, out=seg_ptr[1:])
+    cols = np.fromiter((v for s in samp for v in sorted(s)), dtype=np.int64, count=int(seg_ptr[-1]))
+    _, inv = np.unique(cols, return_inverse=True)
+    col_cnt = np.bincount(inv).astype(np.float32)[inv]
+    row_cnt = np.repeat(sizes.astype(np.float32), sizes)
+    w = ((np.float32(1.0) / np.sqrt(row_cnt)) / np.sqrt(col_cnt)).astype(np.float32)        # mask.div(row).div(col)  :212-216
+    return tuple(torch.from_numpy(a).to(device) for a in (seg_ptr, cols.astype(np.int32), w))
+
+
+def _init_encoder(enc, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample, base_model, gcn, cuda):
+    """The attributes every `GCNEncoder.__init__` of the reference sets before its weights (`src/graphsage.py:368-386`); returns the
+    device of the feature table."""
+    enc.features = _features(features)
+    enc.feat_dim = feature_dim
+    enc.adj_lists = adj_lists
+    enc.aggregator = aggregator
+    enc.aggregator.features = enc.features
+    enc.num_sample = num_sample
+    if base_model is not None:
+        enc.base_model = base_model
+    enc.gcn = gcn
+    enc.embed_dim = embed_dim
+    enc.cuda = cuda
+    enc.aggregator.cuda = cuda
+    return enc.features.weight.device
+
+
+def _init_recon_encoder(enc, *args):
+    """`_init_encoder`, then the two weights the DOMINANT-style and AEGIS-style encoders share, in the reference's order of torch RNG
+    draws: xavier for `weight`, `nn.Linear`'s default for `fc` (embed -> feature space, `src/graphsage_dominant.py:259-265`)."""
+    dev = _init_encoder(enc, *args)
+    w = torch.empty(enc.embed_dim, enc.feat_dim)
+    init.xavier_uniform_(w)
+    enc.weight = nn.Parameter(w.to(dev))
+    enc.fc = nn.Linear(enc.embed_dim, enc.feat_dim, bias=False).to(dev)
+    return dev
+
+
 def _label_array(label, n) -> np.ndarray:
     if label is None:
         return np.zeros(n, dtype=np.int64)
@@ -184,19 +230,7 @@ class GCNEncoder(nn.Module):
     def __init__(self, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample=10, base_model=None,
                  gcn=False, cuda=False, feature_transform=False):
         super().__init__()
-        self.features = _features(features)
-        self.feat_dim = feature_dim
-        self.adj_lists = adj_lists
-        self.aggregator = aggregator
-        self.aggregator.features = self.features
-        self.num_sample = num_sample
-        if base_model is not None:
-            self.base_model = base_model
-        self.gcn = gcn
-        self.embed_dim = embed_dim
-        self.cuda = cuda
-        self.aggregator.cuda = cuda
-        dev = self.features.weight.device
+        dev = _init_encoder(self, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample, base_model, gcn, cuda)
         self.engine = MiniBatchEngine(feature_dim, embed_dim, dev)
         # same CPU RNG consumption as the reference constructor (:388-391): xavier for weight, Linear default for fc
         w = torch.empty(embed_dim, feature_dim)

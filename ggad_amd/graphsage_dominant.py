@@ -24,7 +24,8 @@ from torch.nn import init
 from ._lib import call, ptr
 from .fullgraph import LinearFn
 from .graph import DeviceGraph
-from .graphsage import Encoder, FeatureTable, MeanAggregator, _as_graph, _features, _node_array  # noqa: F401  (re-exports)
+from .graphsage import (Encoder, FeatureTable, MeanAggregator, _as_graph, _features, _init_recon_encoder,  # noqa: F401  (re-exports)
+                        _node_array, _ragged_weights)
 from .minibatch import BatchChunk
 
 
@@ -57,21 +58,11 @@ class GCNAggregator(nn.Module):
 
     def forward(self, nodes, to_neighs):
         """Explicit neighbour sets, as the reference passes them (`:266`): the ragged weighted gather kernel."""
-        nodes = _node_array(nodes)
-        samp = [set(tn).union({int(nodes[i])}) for i, tn in enumerate(to_neighs)]
-        sizes = np.fromiter((len(s) for s in samp), dtype=np.int64, count=len(samp))
-        seg_ptr = np.zeros(len(samp) + 1, dtype=np.int32)
-        np.cumsum(sizes, out=seg_ptr[1:])
-        cols = np.fromiter((v for s in samp for v in sorted(s)), dtype=np.int64, count=int(seg_ptr[-1]))
-        _, inv = np.unique(cols, return_inverse=True)
-        col_cnt = np.bincount(inv).astype(np.float32)[inv]
-        row_cnt = np.repeat(sizes.astype(np.float32), sizes)
-        w = ((np.float32(1.0) / np.sqrt(row_cnt)) / np.sqrt(col_cnt)).astype(np.float32)        # mask.div(row).div(col)  :212-216
         dev = self.features.weight.device
         f = self.features.weight.shape[1]
-        sp, sc, sw = (torch.from_numpy(a).to(dev) for a in (seg_ptr, cols.astype(np.int32), w))
-        out = torch.empty(len(samp), f, device=dev)
-        call("ggad_seg_wsum", ptr(self.features.weight.data), f, ptr(sp), ptr(sc), ptr(sw), len(samp), ptr(out))
+        sp, sc, sw = _ragged_weights(nodes, to_neighs, dev)
+        out = torch.empty(len(sp) - 1, f, device=dev)
+        call("ggad_seg_wsum", ptr(self.features.weight.data), f, ptr(sp), ptr(sc), ptr(sw), len(sp) - 1, ptr(out))
         return out
 
 
@@ -79,23 +70,8 @@ class GCNEncoder(nn.Module):
     def __init__(self, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample=10, base_model=None, gcn=False,
                  cuda=False, feature_transform=False, recon_device=None):
         super().__init__()
-        self.features = _features(features)
-        self.feat_dim = feature_dim
-        self.adj_lists = adj_lists
-        self.aggregator = aggregator
-        self.aggregator.features = self.features
-        self.num_sample = num_sample
-        if base_model is not None:
-            self.base_model = base_model
-        self.gcn = gcn
-        self.embed_dim = embed_dim
-        self.cuda = cuda
-        self.aggregator.cuda = cuda
-        dev = self.features.weight.device
-        w = torch.empty(embed_dim, self.feat_dim)
-        init.xavier_uniform_(w)                                                  # :259-261, same RNG draws in the same order
-        self.weight = nn.Parameter(w.to(dev))
-        self.fc = nn.Linear(embed_dim, feature_dim, bias=False).to(dev)          # :265
+        # :259-265, same RNG draws in the same order
+        _init_recon_encoder(self, features, feature_dim, embed_dim, adj_lists, aggregator, num_sample, base_model, gcn, cuda)
         # recon_device: None / False = the path below; True or a `ReconDevice` = the fused step and score kernels (`csrc/recon_mb.hip`)
         self.recon_device = None
         if recon_device is not None and recon_device is not False:

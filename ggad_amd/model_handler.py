@@ -15,11 +15,15 @@ Extra, optional config keys:  ``device`` (cuda index), ``num_batches`` (default 
 hard override `:317`), ``data`` = (adj_lists | DeviceGraph | (rowptr, col), feat_data, labels) to bypass
 the file loader, ``log_every``, ``n_pseudo`` (pseudo-anomalies per batch, default 50: the reference's `:342-347`).  Under `torch.distributed` (backend nccl = RCCL) batches are dealt
 round-robin over the ranks and gradients are all-reduced once per step.
+
+The loader and split, the adjacency coercion, the checkpoint rule and the epoch loop of the labelled-batch models (`_train_sage`,
+`_train_sage_device`, `_train_pcgnn` build model, optimiser and containers and hand them to it) live in `handler_loop.py`; the GGAD
+loop (blocks of epochs through `trainer.run_steps`) is in `train` below.
 """
 from __future__ import annotations
 
 import argparse
-import datetime
+import operator
 import os
 import random
 import time
@@ -28,12 +32,29 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .dgraph import load_dgraphfin, normalize_features, split_dgraphfin
 from .graph import DeviceGraph
 from .graphsage import GCN, Encoder, FeatureTable, GCNAggregator, GCNEncoder, GraphSage, MeanAggregator
+from .handler_loop import BestCheckpoint, device_graph, load_and_split, sweep_report, train_labelled
 from .sage_utils import test_sage
 from .sampler import PyCompatRandom
 from .trainer import BatchSchedule, DGraphTrainer
+
+
+def _autograd_step(gnn_model, optimizer):
+    """The optimiser step of the labelled-batch models for `train_labelled`: `loss` returns one tensor (GraphSage: the first repair of
+    the module docstring) or (loss, loss_constraint) (`:352-353`); the first is back-propagated."""
+    def step(batch_nodes, batch_label):
+        optimizer.zero_grad()
+        out = gnn_model.loss(batch_nodes, batch_label)
+        out = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+        out[0].backward()
+        optimizer.step()
+        return out
+    return step
+
+
+def _report_sage(epoch, means, epoch_time):
+    print(f"Epoch: {epoch}, loss: {means[0]}, time: {epoch_time}s")
 
 
 class ModelHandler(object):
@@ -45,28 +66,7 @@ class ModelHandler(object):
                              "the device path")
         if bool(getattr(args, "sage_epoch", False)) and not bool(getattr(args, "sage_device", False)):
             raise ValueError("config key `sage_epoch` needs `sage_device: true`: the epoch path replays the kernels of the device path")
-        data = getattr(args, "data", None)
-        if data is not None:
-            homo, feat_data, labels = data
-            labels = np.array(labels)
-        elif args.data_name == "dgraphfin":
-            homo, feat_data, labels = load_dgraphfin("../data/dgraphfin.npz", args.data_dir + "dgraphfin_adj_list")
-        else:
-            raise ValueError("only data_name 'dgraphfin' (or an explicit `data` entry) is supported by the GGAD path")
-        sp = split_dgraphfin(labels, args.seed, getattr(args, "test_ratio", 0.67))     # model_handler.py:29-30,150-178
-        labels = sp["labels"]
-        print(f"Run on {args.data_name}, postive/total num: {np.sum(labels)}/{len(labels)}, train num {len(sp['y_train'])}," +
-              f"valid num {len(sp['y_valid'])}, valid positive num {np.sum(sp['y_valid'])} , test num {len(sp['y_test'])}, "
-              f"test positive num {np.sum(sp['y_test'])}")
-        print(f"Classification threshold: {args.thres}")
-        print(f"Feature dimension: {feat_data.shape[1]}")
-        feat_data = normalize_features(feat_data)                                      # model_handler.py:225
-        print(f"Model: {args.model}, multi-relation aggregator: {args.multi_relation}, emb_size: {args.emb_size}.")
-        self.args = args
-        self.dataset = {"feat_data": feat_data, "labels": labels, "adj_lists": homo, "homo": homo,
-                        "idx_train": sp["idx_train"], "idx_valid": sp["idx_valid"], "idx_test": sp["idx_test"],
-                        "y_train": sp["y_train"], "y_valid": sp["y_valid"], "y_test": sp["y_test"],
-                        "idx_labeled": sp["idx_labeled"], "idx_anomaly": sp["idx_anomaly"]}
+        self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
 
     def train(self):
         args = self.args
@@ -90,18 +90,13 @@ class ModelHandler(object):
         n, f = feat_data.shape
         # same RNG consumption as the reference: nn.Embedding's default init draws N x F normals (:263)
         nn.Embedding(n, f)
-        if isinstance(adj_lists, DeviceGraph):
-            graph = adj_lists
-        elif isinstance(adj_lists, tuple):
-            graph = DeviceGraph(adj_lists[0], adj_lists[1], dev)
-        else:
-            # the reference's pickled dict of sets: converted once, then served from a binary CSR cache beside it
-            # (keyed by size + mtime of the pickle; written under a per-process temporary name: ranks may convert concurrently)
-            cache = src = None
-            if getattr(args, "data_name", "") == "dgraphfin" and getattr(args, "data", None) is None:
-                src = args.data_dir + "dgraphfin_adj_list"
-                cache = os.path.join(args.data_dir, "dgraphfin_adj_list.csr.npz")
-            graph = DeviceGraph.from_adj_lists_cached(adj_lists, n, dev, cache, source_path=src)
+        # the reference's pickled dict of sets: converted once, then served from a binary CSR cache beside it
+        # (keyed by size + mtime of the pickle; written under a per-process temporary name: ranks may convert concurrently)
+        cache = src = None
+        if getattr(args, "data_name", "") == "dgraphfin" and getattr(args, "data", None) is None:
+            src = args.data_dir + "dgraphfin_adj_list"
+            cache = os.path.join(args.data_dir, "dgraphfin_adj_list.csr.npz")
+        graph = device_graph(adj_lists, n, dev, cache, source_path=src)
         features = FeatureTable(torch.FloatTensor(np.asarray(feat_data, dtype=np.float32)))
         agg_gcn = GCNAggregator(features, cuda=True)
         enc_gcn = GCNEncoder(features, f, args.emb_size, graph, agg_gcn, gcn=True, cuda=True)
@@ -110,10 +105,7 @@ class ModelHandler(object):
         engine.lr, engine.wd = float(args.lr), float(args.weight_decay)
         engine.sync_params()
 
-        timestamp = datetime.datetime.fromtimestamp(int(time.time())).strftime("%Y-%m-%d %H-%M-%S")
-        dir_saver = args.save_dir + timestamp
-        path_saver = os.path.join(dir_saver, "{}_{}.pkl".format(args.data_name, args.model))
-        f1_mac_best, auc_best, ep_best = 0, 0, -1
+        best = BestCheckpoint(args.save_dir, args.data_name, args.model, write=rank == 0)   # every rank follows the rule, rank 0 saves
 
         num_batches = int(getattr(args, "num_batches", 150))                            # :317
         rng = PyCompatRandom.from_python_state(random.getstate())
@@ -192,24 +184,15 @@ class ModelHandler(object):
                                                                                args.thres, dist=dist, verbose=rank == 0)
                 self.valid_history.append((epoch, (f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val)))
                 self.sweep_ap.append(getattr(test_sage, "last_ap", None))
-                if auc_val > auc_best:
-                    f1_mac_best, auc_best, ep_best = f1_mac_val, auc_val, epoch
-                    if rank == 0:
-                        if not os.path.exists(dir_saver):
-                            os.makedirs(dir_saver)
-                        print("  Saving model ...")
-                        torch.save(gnn_model.state_dict(), path_saver)
+                best.offer(epoch, f1_mac_val, auc_val, gnn_model)
             if dist:
                 dist.barrier()
             total_time += time.time() - t0
             epoch += 1
         random.setstate(rng.to_python_state())       # hand the stream back to python `random`
         self.end_state = {k: v.detach().clone() for k, v in gnn_model.state_dict().items() if "features" not in k}   # before the restore
-        if ep_best >= 0:
-            if rank == 0:
-                print("Restore model from epoch {}".format(ep_best))
-                print("Model path: {}".format(path_saver))
-                gnn_model.load_state_dict(torch.load(path_saver))
+        if best.ep_best >= 0:
+            best.restore(gnn_model)
             if dist and world > 1:
                 dist.broadcast(engine.params, src=0)          # every rank tests the restored weights
             engine.sync_params()
@@ -219,6 +202,13 @@ class ModelHandler(object):
 
 
     # ---------------------------------------------------------------------------------------------------------------- SAGE
+    def _cuda_device(self):
+        if not torch.cuda.is_available():
+            raise RuntimeError("ModelHandler.train needs an MI355X: there is no CPU fallback")
+        dev = torch.device("cuda", int(getattr(self.args, "device", torch.cuda.current_device())))
+        torch.cuda.set_device(dev)
+        return dev
+
     def _train_sage(self):
         """`model: 'SAGE'`: MeanAggregator -> Encoder(gcn=False) -> GraphSage(2, enc) as `src/model_handler.py:278-293` builds
         them, trained by the loop of `:310-370` with the two repairs named in the module docstring.  Host side as in the reference
@@ -226,14 +216,8 @@ class ModelHandler(object):
         rows, the two projections and their gradients, Adam -- runs in libggad_hip.so."""
         from .fullgraph import FlatAdam
         args = self.args
-        if not torch.cuda.is_available():
-            raise RuntimeError("ModelHandler.train needs an MI355X: there is no CPU fallback")
-        dev = torch.device("cuda", int(getattr(args, "device", torch.cuda.current_device())))
-        torch.cuda.set_device(dev)
+        dev = self._cuda_device()
         feat_data, adj_lists = self.dataset["feat_data"], self.dataset["adj_lists"]
-        idx_train = list(self.dataset["idx_train"])
-        idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
-                                                self.dataset["idx_test"], self.dataset["y_test"])   # :260-261
         n, f = feat_data.shape
         nn.Embedding(n, f)                                            # RNG consumption of :263
         if isinstance(adj_lists, tuple):
@@ -248,51 +232,10 @@ class ModelHandler(object):
         features.to(dev)
         optimizer = FlatAdam([p for p in gnn_model.parameters() if p.requires_grad], lr=args.lr, weight_decay=args.weight_decay)
         self.model = gnn_model
-        num_batches = int(getattr(args, "num_batches", 150))           # :317
-        n_pseudo = int(getattr(args, "n_pseudo", 50))
-        idx_anomaly = list(self.dataset["idx_anomaly"])
-        labels = self.dataset["labels"]
-        timestamp = datetime.datetime.fromtimestamp(int(time.time())).strftime("%Y-%m-%d %H-%M-%S")
-        dir_saver = args.save_dir + timestamp
-        path_saver = os.path.join(dir_saver, "{}_{}.pkl".format(args.data_name, args.model))
-        f1_mac_best, auc_best, ep_best = 0, 0, -1
-        total_time = 0.0
         self.sage_losses = []
-        for epoch in range(args.num_epochs):
-            t_epoch = time.time()
-            random.shuffle(idx_train)                                  # :314
-            loss_sum, epoch_time = 0.0, 0.0
-            for batch in range(num_batches):
-                t0 = time.time()
-                i0, i1 = batch * args.batch_size, min((batch + 1) * args.batch_size, len(idx_train))
-                batch_nodes = idx_train[i0:i1]
-                random.shuffle(idx_anomaly)                            # :341
-                batch_nodes = batch_nodes + idx_anomaly[:n_pseudo]     # :342,347
-                batch_label = labels[np.array(batch_nodes)]
-                optimizer.zero_grad()
-                loss = gnn_model.loss(batch_nodes, torch.as_tensor(batch_label, device=dev).long())    # repair 1
-                loss.backward()
-                optimizer.step()
-                epoch_time += time.time() - t0
-                self.sage_losses.append(float(loss.item()))
-                loss_sum += self.sage_losses[-1]
-            print(f"Epoch: {epoch}, loss: {loss_sum / num_batches}, time: {epoch_time}s")
-            total_time += time.time() - t_epoch
-            if epoch % args.valid_epochs == 0:
-                print("Valid at epoch {}".format(epoch))
-                f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val = self._test_graphsage(idx_valid, y_valid, gnn_model, args.batch_size,
-                                                                                          args.thres)
-                if auc_val > auc_best:
-                    f1_mac_best, auc_best, ep_best = f1_mac_val, auc_val, epoch
-                    if not os.path.exists(dir_saver):
-                        os.makedirs(dir_saver)
-                    print("  Saving model ...")
-                    torch.save(gnn_model.state_dict(), path_saver)
-        if ep_best >= 0:
-            print("Restore model from epoch {}".format(ep_best))
-            print("Model path: {}".format(path_saver))
-            gnn_model.load_state_dict(torch.load(path_saver))
-        return self._test_graphsage(idx_test, y_test, gnn_model, args.batch_size, args.thres)
+        return train_labelled(args, self.dataset, gnn_model, list(self.dataset["idx_train"]), list(self.dataset["idx_anomaly"]),
+                              shuffle=random.shuffle, join=operator.add, step=_autograd_step(gnn_model, optimizer),
+                              report=_report_sage, sweep=self._test_graphsage, log=self.sage_losses)
 
     def _train_sage_device(self, dev, adj_lists, features, agg_sage):
         """`_train_sage` with config key `sage_device: true` (sage_device.py): the adjacency is a `DeviceGraph` (a (rowptr, col)
@@ -309,10 +252,8 @@ class ModelHandler(object):
         from .sage_device import SageDevice
         args = self.args
         n, f = self.dataset["feat_data"].shape
-        if not isinstance(adj_lists, DeviceGraph):
-            adj_lists = DeviceGraph.from_adj_lists(adj_lists, n, dev)
-        idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
-                                                self.dataset["idx_test"], self.dataset["y_test"])   # :260-261
+        adj_lists = device_graph(adj_lists, n, dev)
+        idx_sweep = list(self.dataset["idx_test"])          # validation runs on the test split (:260-261)
         rng = PyCompatRandom.from_python_state(random.getstate())
         try:
             sage = SageDevice(adj_lists, features, f, args.emb_size, 10, rng=rng)      # the encoder's default num_sample (:291 sets
@@ -322,68 +263,25 @@ class ModelHandler(object):
             features.to(dev)
             optimizer = FlatAdam([p for p in gnn_model.parameters() if p.requires_grad], lr=args.lr, weight_decay=args.weight_decay)
             self.model = gnn_model
-            num_batches = int(getattr(args, "num_batches", 150))           # :317
-            n_pseudo = int(getattr(args, "n_pseudo", 50))
             idx_train = np.array(list(self.dataset["idx_train"]), dtype=np.int64)
             idx_anomaly = np.array(list(self.dataset["idx_anomaly"]), dtype=np.int64)
-            labels = self.dataset["labels"]
-            timestamp = datetime.datetime.fromtimestamp(int(time.time())).strftime("%Y-%m-%d %H-%M-%S")
-            dir_saver = args.save_dir + timestamp
-            path_saver = os.path.join(dir_saver, "{}_{}.pkl".format(args.data_name, args.model))
-            f1_mac_best, auc_best, ep_best = 0, 0, -1
             self.sage_losses = []
-            self.sage_epoch = None
+            self.sage_epoch = epoch_fn = None
             if bool(getattr(args, "sage_epoch", False)):
                 from .sage_epoch import SageEpoch
-                self.sage_epoch = SageEpoch(sage, enc_sage.weight, gnn_model.weight, optimizer, idx_train, idx_anomaly, labels,
-                                            args.batch_size, n_pseudo, num_batches)
-            for epoch in range(args.num_epochs):
-                loss_sum, epoch_time = 0.0, 0.0
-                if self.sage_epoch is not None:
+                self.sage_epoch = SageEpoch(sage, enc_sage.weight, gnn_model.weight, optimizer, idx_train, idx_anomaly,
+                                            self.dataset["labels"], args.batch_size, int(getattr(args, "n_pseudo", 50)),
+                                            int(getattr(args, "num_batches", 150)))
+
+                def epoch_fn(epoch):
                     # what the stream is asked for after this epoch is drawn while the device trains it: the validation sweep, the
                     # next epoch, or -- after the last epoch -- the test sweep (a restored checkpoint changes no draw)
-                    if epoch % args.valid_epochs == 0:
-                        ahead = lambda: sage.presample(list(idx_valid))
-                    elif epoch + 1 < args.num_epochs:
-                        ahead = "epoch"
-                    else:
-                        ahead = lambda: sage.presample(list(idx_test))
-                    t0 = time.time()
-                    epoch_losses = self.sage_epoch.run_epoch(ahead)
-                    epoch_time = time.time() - t0
-                    for l in epoch_losses:
-                        self.sage_losses.append(float(l))
-                        loss_sum += self.sage_losses[-1]
-                else:
-                    rng.shuffle(idx_train)                                 # :314
-                    for batch in range(num_batches):
-                        t0 = time.time()
-                        i0, i1 = batch * args.batch_size, min((batch + 1) * args.batch_size, len(idx_train))
-                        rng.shuffle(idx_anomaly)                           # :341
-                        batch_nodes = np.concatenate([idx_train[i0:i1], idx_anomaly[:n_pseudo]])     # :342,347
-                        optimizer.zero_grad()
-                        loss = gnn_model.loss(batch_nodes, labels[batch_nodes])
-                        loss.backward()
-                        optimizer.step()
-                        epoch_time += time.time() - t0
-                        self.sage_losses.append(float(loss.item()))
-                        loss_sum += self.sage_losses[-1]
-                print(f"Epoch: {epoch}, loss: {loss_sum / num_batches}, time: {epoch_time}s")
-                if epoch % args.valid_epochs == 0:
-                    print("Valid at epoch {}".format(epoch))
-                    f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val = self._test_graphsage(idx_valid, y_valid, gnn_model,
-                                                                                              args.batch_size, args.thres)
-                    if auc_val > auc_best:
-                        f1_mac_best, auc_best, ep_best = f1_mac_val, auc_val, epoch
-                        if not os.path.exists(dir_saver):
-                            os.makedirs(dir_saver)
-                        print("  Saving model ...")
-                        torch.save(gnn_model.state_dict(), path_saver)
-            if ep_best >= 0:
-                print("Restore model from epoch {}".format(ep_best))
-                print("Model path: {}".format(path_saver))
-                gnn_model.load_state_dict(torch.load(path_saver))
-            return self._test_graphsage(idx_test, y_test, gnn_model, args.batch_size, args.thres)
+                    if epoch % args.valid_epochs != 0 and epoch + 1 < args.num_epochs:
+                        return self.sage_epoch.run_epoch("epoch")
+                    return self.sage_epoch.run_epoch(lambda: sage.presample(idx_sweep))
+            return train_labelled(args, self.dataset, gnn_model, idx_train, idx_anomaly, shuffle=rng.shuffle,
+                                  join=lambda a, b: np.concatenate([a, b]), step=_autograd_step(gnn_model, optimizer),
+                                  report=_report_sage, sweep=self._test_graphsage, log=self.sage_losses, epoch_fn=epoch_fn)
         finally:
             random.setstate(rng.to_python_state())       # hand the stream back to python `random`
 
@@ -403,10 +301,7 @@ class ModelHandler(object):
         from .layers import InterAgg, IntraAgg, PCALayer
         from . import synth
         args = self.args
-        if not torch.cuda.is_available():
-            raise RuntimeError("ModelHandler.train needs an MI355X: there is no CPU fallback")
-        dev = torch.device("cuda", int(getattr(args, "device", torch.cuda.current_device())))
-        torch.cuda.set_device(dev)
+        dev = self._cuda_device()
         feat_data = self.dataset["feat_data"]
         relations = getattr(args, "relations", None)
         if relations is None and isinstance(self.dataset["adj_lists"], (list, tuple)) and len(self.dataset["adj_lists"]) == 3 \
@@ -417,14 +312,10 @@ class ModelHandler(object):
                              "(dict of neighbour sets, or (rowptr, col)); the reference's branch never ran (its handler passes one)")
         if bool(getattr(args, "pcgnn_device", False)):
             # relations stay CSR in HBM (pcgnn_device.py): no dict of sets is built; `InterAgg` checks every relation once
-            from .graph import DeviceGraph
-            adjs = [DeviceGraph(r[0], r[1], dev) if isinstance(r, tuple) else DeviceGraph.from_adj_lists(r, feat_data.shape[0], dev)
-                    for r in relations]
+            adjs = [device_graph(r, feat_data.shape[0], dev) for r in relations]
         else:
             adjs = [synth.csr_to_adj_lists(r[0], r[1]) if isinstance(r, tuple) else r for r in relations]
         idx_train = list(self.dataset["idx_train"])
-        idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
-                                                self.dataset["idx_test"], self.dataset["y_test"])   # :260-261
         n, f = feat_data.shape
         nn.Embedding(n, f)                                            # RNG consumption of :263
         features = FeatureTable(torch.FloatTensor(np.asarray(feat_data, dtype=np.float32)))
@@ -437,55 +328,18 @@ class ModelHandler(object):
         features.to(dev)
         optimizer = FlatAdam([p for p in gnn_model.parameters() if p.requires_grad], lr=args.lr, weight_decay=args.weight_decay)
         self.model = gnn_model
-        num_batches = int(getattr(args, "num_batches", 150))           # :317
-        n_pseudo = int(getattr(args, "n_pseudo", 50))
-        idx_anomaly = list(self.dataset["idx_anomaly"])
-        labels = self.dataset["labels"]
-        timestamp = datetime.datetime.fromtimestamp(int(time.time())).strftime("%Y-%m-%d %H-%M-%S")
-        dir_saver = args.save_dir + timestamp
-        path_saver = os.path.join(dir_saver, "{}_{}.pkl".format(args.data_name, args.model))
-        f1_mac_best, auc_best, ep_best = 0, 0, -1
         self.pcgnn_losses = []
-        for epoch in range(args.num_epochs):
-            random.shuffle(idx_train)                                  # :314
-            loss_sum, con_sum, epoch_time = 0.0, 0.0, 0.0
-            for batch in range(num_batches):
-                t0 = time.time()
-                i0, i1 = batch * args.batch_size, min((batch + 1) * args.batch_size, len(idx_train))
-                batch_nodes = idx_train[i0:i1]
-                random.shuffle(idx_anomaly)                            # :341
-                batch_nodes = batch_nodes + idx_anomaly[:n_pseudo]     # :342,347
-                batch_label = torch.as_tensor(labels[np.array(batch_nodes)], device=dev).long()
-                optimizer.zero_grad()
-                loss, loss_constraint = gnn_model.loss(batch_nodes, batch_label)           # :352-353
-                loss.backward()
-                optimizer.step()
-                epoch_time += time.time() - t0
-                self.pcgnn_losses.append((float(loss.item()), float(loss_constraint.item())))
-                loss_sum += self.pcgnn_losses[-1][0]
-                con_sum += self.pcgnn_losses[-1][1]
-            print(f"Epoch: {epoch}, loss: {loss_sum / num_batches}, loss_constraint: {con_sum / num_batches}, time: {epoch_time}s")
-            if epoch % args.valid_epochs == 0:
-                print("Valid at epoch {}".format(epoch))
-                f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val = self._test_pcgnn(idx_valid, y_valid, gnn_model, args.batch_size,
-                                                                                      args.thres)
-                if auc_val > auc_best:
-                    f1_mac_best, auc_best, ep_best = f1_mac_val, auc_val, epoch
-                    if not os.path.exists(dir_saver):
-                        os.makedirs(dir_saver)
-                    print("  Saving model ...")
-                    torch.save(gnn_model.state_dict(), path_saver)
-        if ep_best >= 0:
-            print("Restore model from epoch {}".format(ep_best))
-            print("Model path: {}".format(path_saver))
-            gnn_model.load_state_dict(torch.load(path_saver))
-        return self._test_pcgnn(idx_test, y_test, gnn_model, args.batch_size, args.thres)
+
+        def report(epoch, means, epoch_time):
+            print(f"Epoch: {epoch}, loss: {means[0]}, loss_constraint: {means[1]}, time: {epoch_time}s")
+        return train_labelled(args, self.dataset, gnn_model, idx_train, list(self.dataset["idx_anomaly"]), shuffle=random.shuffle,
+                              join=operator.add, step=_autograd_step(gnn_model, optimizer), report=report, sweep=self._test_pcgnn,
+                              log=self.pcgnn_losses)
 
     @staticmethod
     def _test_pcgnn(test_cases, labels, model, batch_size, thres=0.5):
         """What the undefined `test_pcgnn` of `src/model_handler.py:392,411` has to be for that call to work: `test_sage`'s protocol
         (`src/utils.py:207-247`) on the class-1 GNN score of `PCALayer.to_prob(nodes, labels, train_flag=False)`."""
-        from .metrics import binary_report
         test_cases = list(test_cases)
         labels = np.asarray(labels)
         probs = []
@@ -498,18 +352,12 @@ class ModelHandler(object):
                 dev = next(model.parameters()).device
                 gnn_prob, _ = model.to_prob(chunk, torch.as_tensor(labels[lo:hi], device=dev).long(), train_flag=False)
                 probs.append(gnn_prob[:, 1])
-        probs = torch.cat(probs)
-        r = binary_report(probs, torch.as_tensor(labels, device=probs.device), thres)
-        print(f"   GNN F1-binary-1: {r['f1_1']:.4f}\tF1-binary-0: {r['f1_0']:.4f}" +
-              f"\tF1-macro: {r['f1_macro']:.4f}\tG-Mean: {r['gmean']:.4f}\tAUC: {r['auc']:.4f}")
-        print("Testing AP:", r["ap"])
-        return r["f1_macro"], r["f1_1"], r["f1_0"], r["auc"], r["gmean"]
+        return sweep_report(torch.cat(probs), labels, thres)
 
     @staticmethod
     def _test_graphsage(test_cases, labels, model, batch_size, thres=0.5):
         """`test_sage` (`src/utils.py:207-247`) for the two-class GraphSage head: `to_prob(nodes)` (repair 2: one argument), the
         score of a node = its class-1 probability."""
-        from .metrics import binary_report
         test_cases = list(test_cases)
         probs = []
         with torch.no_grad():
@@ -523,9 +371,4 @@ class ModelHandler(object):
                     if not chunk:
                         continue
                     probs.append(model.to_prob(chunk)[:, 1])
-        probs = torch.cat(probs)
-        r = binary_report(probs, torch.as_tensor(np.asarray(labels), device=probs.device), thres)
-        print(f"   GNN F1-binary-1: {r['f1_1']:.4f}\tF1-binary-0: {r['f1_0']:.4f}" +
-              f"\tF1-macro: {r['f1_macro']:.4f}\tG-Mean: {r['gmean']:.4f}\tAUC: {r['auc']:.4f}")
-        print("Testing AP:", r["ap"])
-        return r["f1_macro"], r["f1_1"], r["f1_0"], r["auc"], r["gmean"]
+        return sweep_report(torch.cat(probs), labels, thres)

@@ -162,6 +162,37 @@ def test_handler_epochs_equal_the_oracle_loop(which, pw, frac):
     assert int(h.dataset["labels"].sum()) == int(y.sum()) + int(n_lab * frac)
 
 
+@pytest.mark.parametrize("which", ["dominate", "anomalydae"])
+def test_handler_captured_epochs_equal_the_eager_ones(which):
+    """The default path with `capture: true` (epoch 0 eager, epoch 1 captured and replayed, epochs 2 and 3 replays of that graph on
+    new plans) against `capture: false`, on the smallest shape that reaches a replay: 3,000 nodes, 4 batches of 40, 4 epochs.  A
+    replay launches the kernels of the eager loop on the same plan buffers in the same order, and none of them is order-dependent
+    (no float atomics), so the yardstick is bit equality, as for the AEGIS device path: every loss, every entry of the state_dict,
+    the validation numbers; and python's `random` stream ends in the same state."""
+    mh = importlib.import_module(f"ggad_amd.model_handler_{which}")
+    n, f = 3000, 17
+    rowptr, col = synth.make_graph(n, 30000, 3, kind="powerlaw", max_degree=200)
+    feat_raw = synth.make_features(n, f, 3)
+    y = synth.make_labels(n, 0.05, 3).astype(np.int32)
+    runs = []
+    for capture in (True, False):
+        torch.manual_seed(72)
+        np.random.seed(72)
+        h = mh.ModelHandler(_handler_cfg(((rowptr, col), feat_raw, y), batch_size=40, num_batches=4, num_epochs=4, valid_epochs=2,
+                                         capture=capture))
+        h.train()
+        runs.append((np.array(h.epoch_losses), {k: v.detach().cpu().numpy() for k, v in h.model.state_dict().items()},
+                     h.valid_history, random.getstate()))
+    (l_cap, sd_cap, valid_cap, state_cap), (l_eager, sd_eager, valid_eager, state_eager) = runs
+    assert l_cap.shape == (4, 4) and np.isfinite(l_cap).all() and len(np.unique(l_cap)) == 16         # (it trains: no two alike)
+    assert np.array_equal(l_cap, l_eager)
+    assert sd_cap.keys() == sd_eager.keys()
+    for k in sd_cap:
+        assert np.array_equal(sd_cap[k], sd_eager[k]), k
+    assert [e for e, _, _ in valid_cap] == [0, 2] and valid_cap == valid_eager
+    assert state_cap == state_eager
+
+
 def test_aegis_minibatch_model_against_the_oracle_restatement(tmp_path, capsys):
     """Mini-batch AEGIS-style model (`src/graphsage_aegis.py`, `src/model_handler_aegis.py`).  PARITY UNPINNED: its
     discriminator is `torch_geometric.nn.MLP`, absent from the image, so the HIP path (two 1-hop aggregates per batch from one plan,

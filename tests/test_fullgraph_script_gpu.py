@@ -1,7 +1,8 @@
 """The capture helper of the full-graph scripts (`ggad_amd.fullgraph_script.CapturedEpoch` / `capture`) on the smallest thing that can
 go wrong: one `torch.nn.Linear(4, 4)` under a `FlatAdam`, an epoch of zero_grad / forward on a fixed (8, 4) input plus an (8, 4) noise
 buffer / backward / step, 7 epochs.  The loops run once, in a child process under a time limit (this file run as a program prints
-what they gave as one JSON line); the tests compare the results."""
+what they gave as one JSON line); the tests compare the results.  The mini-batch handlers' form -- `at=1` and a `key` per epoch,
+a changed key captured again -- runs on the same model."""
 import json
 import os
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 EPOCHS, AT = 7, 2
+KEYS = ["a"] * 4 + ["b"] * 3            # the key of every epoch: it changes once, at epoch 4
 
 
 def _setup():
@@ -73,6 +75,19 @@ def _helper_loop(enabled=True, gate=None, draws=None):
     return _result(lin, losses, events=events, captured=cap.captured, gate_calls=gate_calls)
 
 
+def _keyed_loop(enabled=True, keys=None):
+    """7 epochs through `CapturedEpoch(at=1)`, `step` given `keys[epoch]` (None: the keyless form)."""
+    from ggad_amd.fullgraph_script import CapturedEpoch
+    lin, opt, noise, epoch_fn, log = _setup()
+    cap = CapturedEpoch(epoch_fn, enabled=enabled, at=1, before_capture=opt.zero_grad)
+    losses, events = [], []
+    for epoch in range(EPOCHS):
+        del log[:]
+        losses.append(cap.step(epoch, lambda: log.append("before_replay"), key=None if keys is None else keys[epoch]).item())
+        events.append(list(log))
+    return _result(lin, losses, events=events, captured=cap.captured)
+
+
 def _eager_loop(draws=None):
     lin, opt, noise, epoch_fn, _ = _setup()
     losses = []
@@ -100,7 +115,8 @@ def _measure():
     draws = torch.randn(EPOCHS, 8, 4, generator=torch.Generator().manual_seed(1))
     return dict(eager=_helper_loop(enabled=False), captured=_helper_loop(), gate_closed=_helper_loop(gate=lambda: False),
                 gate_open=_helper_loop(gate=lambda: True), noise_eager=_eager_loop(draws), noise_captured=_helper_loop(draws=draws),
-                function=_function_loop(), plain_eager=_eager_loop())
+                function=_function_loop(), plain_eager=_eager_loop(), keyed=_keyed_loop(keys=KEYS),
+                keyed_eager=_keyed_loop(enabled=False, keys=KEYS), keyless_at_1=_keyed_loop())
 
 
 @pytest.fixture(scope="module")
@@ -149,6 +165,25 @@ def test_replay_reads_the_buffer_that_before_replay_filled(res):
 
 def test_function_form_equals_the_helper(res):
     assert _same(res["function"], res["captured"])
+
+
+def test_a_key_that_differs_from_the_captured_one_is_captured_again(res):
+    """Two captures, at epoch 1 (`at`) and at epoch 4 (the key changes); every other epoch from 1 on replays; bit for bit the
+    `enabled=False` run."""
+    ev = res["keyed"]["events"]
+    assert ev[0] == ["epoch_fn"]
+    assert ev[1] == ev[4] == ["epoch_fn (capturing)", "before_replay"]
+    assert ev[2] == ev[3] == ev[5] == ev[6] == ["before_replay"]
+    assert res["keyed"]["captured"] is True and res["keyed_eager"]["captured"] is False
+    assert res["keyed_eager"]["events"] == [["epoch_fn"]] * EPOCHS
+    assert _same(res["keyed"], res["keyed_eager"]) and _same(res["keyed_eager"], res["plain_eager"])
+
+
+def test_without_a_key_the_same_epochs_are_captured_once(res):
+    ev = res["keyless_at_1"]["events"]
+    assert ev[0] == ["epoch_fn"] and ev[1] == ["epoch_fn (capturing)", "before_replay"]
+    assert ev[2:] == [["before_replay"]] * (EPOCHS - 2)
+    assert _same(res["keyless_at_1"], res["plain_eager"])
 
 
 if __name__ == "__main__":
