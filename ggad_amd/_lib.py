@@ -262,6 +262,9 @@ SIGNATURES = {
     "ggad_tam_nsgt_rowstat": (c_int32, [_P, _P, _P, _I, _P, _P, _P, _P]),
     "ggad_tam_nsgt_compact": (c_int32, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ggad_tam_nsgt_cut": (c_int32, [_P, _P, _P, _P, _I, _L, _P, _P, _P]),
+    "ggad_rank_metrics_max_pos": (c_int32, []),
+    "ggad_rank_metrics_workspace_elems": (c_int64, [_L]),
+    "ggad_rank_metrics_f32": (c_int32, [_P, _P, _L, _F, _P, _P, _P]),
 }
 
 

@@ -1,0 +1,90 @@
+"""A validation sweep that stays on the device between validations (config key `eval_cache`).
+
+`sage_utils.score_nodes` plans every slice of `batch_size` ids again on every sweep, although an inference plan is 1-hop only
+and its output -- the aggregated row `x1[i]` of every id -- depends on the graph, the frozen feature table, the id list and the
+slice boundaries (the aggregation normalises per slice, quirk 2), never on the weights.  The score is
+`sigmoid(w . relu(W x1[i]))`, row by row (`k_score`, csrc/step.hip: one wave per row, a fixed fma order, nothing that depends on
+the launch size).  `ResidentSweep` therefore builds the plans ONCE, keeps the `(n, F)` rows, and a sweep is one `ggad_mb_score`
+launch over them: bit for bit what `score_nodes` returns.  The metrics come from the counting kernels of csrc/rank_metrics.hip
+(`metrics.rank_report`) instead of two device sorts.
+"""
+from __future__ import annotations
+
+from typing import Dict, Sequence
+
+import numpy as np
+import torch
+
+from ._lib import call, ptr
+from .minibatch import BatchChunk
+
+
+class ResidentSweep:
+    """The aggregated inference rows of `test_cases`, cached on the device, and the uint8 labels beside them.
+
+    The cache depends on: the graph (`model.enc.adj_lists`), the feature table (`model.enc.features.weight`), the ids of
+    `test_cases` in their order, `batch_size` (the slice boundaries) -- and on nothing else; the weights enter in `scores()` only.
+    A caller that changes the feature table or the graph calls `invalidate()`; the rows are then rebuilt by the next `scores()`.
+    The ids are copied at construction: a list mutated in place afterwards is NOT detected (build a new sweep for a new list)."""
+
+    def __init__(self, model, test_cases: Sequence[int], labels, batch_size: int, batches_per_launch: int = 2048):
+        self.model = model
+        self.engine = model.enc.engine
+        self.cases = np.array(test_cases, dtype=np.int64).reshape(-1)
+        self.n = int(len(self.cases))
+        lab = np.asarray(labels).reshape(-1)
+        if len(lab) != self.n:
+            raise ValueError("ResidentSweep: labels / test_cases length mismatch")
+        self.labels = torch.from_numpy(lab.astype(np.uint8)).to(self.engine.dev)          # uploaded once
+        self.batch_size = int(batch_size)
+        self.batches_per_launch = int(batches_per_launch)
+        self.x1 = None
+        self.builds = 0                 # plans built so far (tests: none between two sweeps)
+        self._build()
+
+    def _build(self) -> None:
+        """Walk the ids exactly as `score_nodes` does (same slices, same `per_launch` bound, same plan) and keep every chunk's x1."""
+        enc, eng = self.model.enc, self.engine
+        F = eng.F
+        self.x1 = torch.empty((self.n, F), dtype=torch.float32, device=eng.dev)
+        if self.n == 0:
+            return
+        from .graphsage import _as_graph
+        graph = _as_graph(enc.adj_lists, enc.features.weight.shape[0], eng.dev)
+        bs = self.batch_size
+        per_launch = int(max(1, min(self.batches_per_launch, (1 << 29) // max(1, graph.n))))
+        # local: its two counter arrays are per_launch x N ints each (gigabytes at DGraph size) and nothing needs them afterwards
+        ch = BatchChunk(graph, enc.features.weight.data, enc.embed_dim, per_launch, per_launch * bs, per_launch * bs * 8, train=False)
+        step = per_launch * bs
+        for s in range(0, self.n, step):
+            part = self.cases[s:s + step]
+            batches = [part[i:i + bs] for i in range(0, len(part), bs)]
+            ch.build(batches)
+            self.builds += 1
+            # device to device, on the stream the build ran on
+            self.x1[s:s + len(part)].copy_(ch.x1[:ch.n_rows * F].view(ch.n_rows, F))
+        torch.cuda.current_stream(eng.dev).synchronize()          # the chunk's buffers go back to the allocator below
+        del ch
+
+    def invalidate(self) -> None:
+        """Drop the cached rows; the next `scores()` builds them again.  For callers that change what the cache depends on: the graph
+        (`model.enc.adj_lists`) or the feature table (`model.enc.features.weight`).  The weights are not among its inputs.  The ids
+        and `batch_size` are fixed at construction: an id list mutated in place afterwards is NOT detected, here or anywhere."""
+        self.x1 = None
+
+    def scores(self) -> torch.Tensor:
+        """Device float32 `(n,)` probabilities under the engine's CURRENT weights: one `ggad_mb_score` launch over the cache."""
+        if self.x1 is None:
+            self._build()
+        eng = self.engine
+        out = torch.empty(self.n, dtype=torch.float32, device=eng.dev)
+        eng.sync_params()
+        if self.n:
+            call("ggad_mb_score", ptr(eng.params), eng.D, eng.F, ptr(self.x1), self.n, ptr(out))
+        return out
+
+    def report(self, thres: float) -> Dict[str, float]:
+        """The dict of `metrics.binary_report` for the current weights, from `metrics.rank_report` (the faster of the two metric blocks
+        at 1.74 M scores: profiles/eval_cache_time_line.json)."""
+        from .metrics import rank_report
+        return rank_report(self.scores(), self.labels, thres)

@@ -7,7 +7,10 @@ sklearn.  Definitions follow scikit-learn's (the reference's metric library), in
   average_precision_score  sum_n (R_n - R_{n-1}) P_n over the distinct thresholds, descending
   f1_score / confusion     from the thresholded predictions (score >= thres)
 
-sklearn itself stays the checker in the tests (tests/test_metrics.py)."""
+sklearn itself stays the checker in the tests (tests/test_metrics.py).
+
+`rank_report` returns the same dict from float32 scores and uint8 labels through the counting kernels of csrc/rank_metrics.hip:
+no full sort (only the positives are sorted), four launches and ONE read-back."""
 from __future__ import annotations
 
 from typing import Dict
@@ -66,3 +69,49 @@ def binary_report(scores: torch.Tensor, labels: torch.Tensor, thres: float) -> D
     gmean = float((tp * tn / ((tp + fn) * (tn + fp))) ** 0.5) if (tp + fn) and (tn + fp) else float("nan")
     return {"auc": roc_auc(scores, labels), "ap": average_precision(scores, labels), "f1_1": f1_1, "f1_0": f1_0,
             "f1_macro": 0.5 * (f1_1 + f1_0), "gmean": gmean, "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+
+
+_ONE_CLASS = "Only one class present in y_true. ROC AUC score is not defined in that case."
+
+
+def rank_report(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float) -> Dict[str, float]:
+    """`binary_report` (same keys) for float32 device scores and uint8 device labels from `ggad_rank_metrics_f32`: AUROC as one
+    float64 division of exact integer counts, AP as a fixed-order float64 sum, the confusion counts as integers; one read-back of
+    eight doubles.  One class only: the `ValueError` of `binary_report`.  More positives than `ggad_rank_metrics_max_pos()`: the
+    result of `binary_report` (its two device sorts).  A NaN score or a label other than 0/1: `ValueError`."""
+    from . import _lib
+    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+        raise ValueError("rank_report takes float32 scores and uint8 labels of the same 1-D shape")
+    if scores.device.type != "cuda" or labels_u8.device != scores.device:
+        raise ValueError("rank_report takes scores and labels on the same GPU (there is no CPU path: use binary_report)")
+    lib = _lib.load()
+    n = scores.numel()
+    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
+    with torch.cuda.device(scores.device):
+        ws = torch.empty(max(1, int(lib.ggad_rank_metrics_workspace_elems(n))), dtype=torch.int32, device=scores.device)
+        out8 = torch.empty(8, dtype=torch.float64, device=scores.device)
+        _lib.call("ggad_rank_metrics_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, float(thres), _lib.ptr(out8), _lib.ptr(ws))
+        return _report_from_out8(out8.cpu().tolist(), lambda: binary_report(scores, labels_u8, thres))
+
+
+def _report_from_out8(o, fallback) -> Dict[str, float]:
+    """The `binary_report` dict from the eight numbers of `ggad_rank_metrics_f32` (host values); `fallback()` serves status 2."""
+    status = int(o[7])
+    if status == 3:
+        raise ValueError("rank_report: a score is NaN")
+    if status == 4:
+        raise ValueError("rank_report: a label is neither 0 nor 1")
+    if status == 2:
+        return fallback()
+    if status == 1:
+        raise ValueError(_ONE_CLASS)
+    tp, fp, fn, tn = (int(v) for v in o[2:6])
+
+    def f1(t, f_p, f_n):
+        d = 2 * t + f_p + f_n
+        return 2.0 * t / d if d else 0.0
+
+    f1_1, f1_0 = f1(tp, fp, fn), f1(tn, fn, fp)
+    gmean = float((tp * tn / ((tp + fn) * (tn + fp))) ** 0.5) if (tp + fn) and (tn + fp) else float("nan")
+    return {"auc": float(o[0]), "ap": float(o[1]), "f1_1": f1_1, "f1_0": f1_0, "f1_macro": 0.5 * (f1_1 + f1_0), "gmean": gmean,
+            "tp": tp, "fp": fp, "fn": fn, "tn": tn}

@@ -66,6 +66,13 @@ class ModelHandler(object):
                              "the device path")
         if bool(getattr(args, "sage_epoch", False)) and not bool(getattr(args, "sage_device", False)):
             raise ValueError("config key `sage_epoch` needs `sage_device: true`: the epoch path replays the kernels of the device path")
+        if bool(getattr(args, "eval_cache", False)):
+            if getattr(args, "model", None) != "GCN":
+                raise ValueError("config key `eval_cache` needs `model: 'GCN'`: the resident sweep caches the inference rows of the GGAD "
+                                 "encoder (the sweeps of the other models are not cached)")
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise ValueError("config key `eval_cache` runs on one GPU: the resident sweep is not sharded over the ranks of a "
+                                 "torch.distributed world yet")
         self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
 
     def train(self):
@@ -149,6 +156,15 @@ class ModelHandler(object):
         self.trainer, self.model = trainer, gnn_model
         self.sweep_ap = []                                      # AP of every sweep, validation sweeps then the test sweep (the reference prints it)
         self.epoch_losses, self.valid_history = [], []          # {total, cls, margin, rec} of every batch; (epoch, five metrics) of every sweep
+        # config key `eval_cache`: one resident sweep per distinct id list (validation and test are the same list, :260-261): the plans
+        # are built once, a sweep is one score launch over the cached rows and the counting kernels of csrc/rank_metrics.hip
+        sweep_valid = sweep_test = None
+        if bool(getattr(args, "eval_cache", False)):
+            from .eval_cache import ResidentSweep
+            sweep_valid = ResidentSweep(gnn_model, idx_valid, y_valid, args.batch_size)
+            sweep_test = sweep_valid if (idx_test is idx_valid and y_test is y_valid) else \
+                ResidentSweep(gnn_model, idx_test, y_test, args.batch_size)
+        self.eval_sweeps = (sweep_valid, sweep_test)
         trainer.start_stream(steps_per_epoch * args.num_epochs)        # sampler thread alive across the validation pauses
         total_time = 0.0
         epoch = 0
@@ -181,7 +197,8 @@ class ModelHandler(object):
                 if rank == 0:
                     print("Valid at epoch {}".format(epoch))
                 f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val = test_sage(idx_valid, y_valid, gnn_model, args.batch_size,
-                                                                               args.thres, dist=dist, verbose=rank == 0)
+                                                                               args.thres, dist=dist, verbose=rank == 0,
+                                                                               resident=sweep_valid)
                 self.valid_history.append((epoch, (f1_mac_val, f1_1_val, f1_0_val, auc_val, gmean_val)))
                 self.sweep_ap.append(getattr(test_sage, "last_ap", None))
                 best.offer(epoch, f1_mac_val, auc_val, gnn_model)
@@ -196,7 +213,7 @@ class ModelHandler(object):
             if dist and world > 1:
                 dist.broadcast(engine.params, src=0)          # every rank tests the restored weights
             engine.sync_params()
-        res = test_sage(idx_test, y_test, gnn_model, args.batch_size, args.thres, dist=dist, verbose=rank == 0)
+        res = test_sage(idx_test, y_test, gnn_model, args.batch_size, args.thres, dist=dist, verbose=rank == 0, resident=sweep_test)
         self.sweep_ap.append(getattr(test_sage, "last_ap", None))
         return res
 

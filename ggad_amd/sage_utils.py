@@ -100,10 +100,15 @@ def score_nodes(model, test_cases: Sequence[int], batch_size: int, batches_per_l
     return out if device else out.cpu().numpy()
 
 
-def test_sage(test_cases, labels, model, batch_size, thres=0.5, device_metrics=True, dist=None, verbose=True):
+def test_sage(test_cases, labels, model, batch_size, thres=0.5, device_metrics=True, dist=None, verbose=True, resident=None):
     """Reference `test_sage` (`src/utils.py:207-247`): same prints, same return tuple.  `dist`: shard the sweep over the
-    ranks (every rank returns the same metrics; pass verbose=False on the ranks that must not print)."""
-    if device_metrics:
+    ranks (every rank returns the same metrics; pass verbose=False on the ranks that must not print).  `resident`: a
+    `ResidentSweep` (eval_cache.py) built for these `test_cases`, `labels` and `batch_size`; scores and metrics then come from it."""
+    if resident is not None:
+        r = resident.report(thres)
+        f1_binary_1, f1_binary_0, f1_macro, auc_gnn, ap, gmean = r["f1_1"], r["f1_0"], r["f1_macro"], r["auc"], r["ap"], r["gmean"]
+        tn, fp, fn, tp = r["tn"], r["fp"], r["fn"], r["tp"]
+    elif device_metrics:
         from .metrics import binary_report
         probs = score_nodes(model, test_cases, batch_size, device=True, dist=dist)
         r = binary_report(probs, torch.as_tensor(np.asarray(labels), device=probs.device), thres)

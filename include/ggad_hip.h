@@ -1115,6 +1115,22 @@ int ggad_tam_nsgt_compact(const int32_t *rowptr, const int32_t *col, const float
 int ggad_tam_nsgt_cut(const int32_t *rowptr, const float *dis, const int32_t *tpos, const float *thr, int32_t n, int64_t nnz,
                       uint8_t *alive, uint8_t *keep, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Rank metrics of a binary classifier (rank_metrics.hip): AUROC, average precision and the confusion counts of `score >= thres`
+ * from n float32 scores and n uint8 labels (0 / 1), with scikit-learn's definitions (distinct thresholds, tied scores) as exact
+ * counts: only the positives are sorted (one workgroup, in LDS), every negative is bucketed against them by binary search into
+ * integer histograms.  Four launches on `stream`, no host synchronisation, no floating-point atomics; n <= INT32_MAX.
+ *
+ * out8 (device, 8 doubles) = {auroc, ap, tp, fp, fn, tn, n_pos, status}; status 0 ok, 1 one class only (auroc NaN; ap 0.0 without
+ * positives), 2 n_pos above ggad_rank_metrics_max_pos() (the counts are valid, auroc / ap NaN), 3 a NaN score, 4 a label other
+ * than 0/1.  workspace: ggad_rank_metrics_workspace_elems(n) int32 elements, no preparation needed: the workspace is cleared by the
+ * launches themselves, so the call is capturable and replayable.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_rank_metrics_max_pos(void);
+int64_t ggad_rank_metrics_workspace_elems(int64_t n);          /* int32 elements */
+int ggad_rank_metrics_f32(const float *score, const uint8_t *label, int64_t n, float thres, double *out8, int32_t *workspace,
+                          ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
