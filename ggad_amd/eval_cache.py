@@ -20,7 +20,8 @@ from .minibatch import BatchChunk
 
 
 class ResidentSweep:
-    """The aggregated inference rows of `test_cases`, cached on the device, and the uint8 labels beside them.
+    """The aggregated inference rows of `test_cases`, cached on the device, and the uint8 labels beside them (`labels=None`: an
+    unlabelled id list, which `top_k` ranks and `report` refuses).
 
     The cache depends on: the graph (`model.enc.adj_lists`), the feature table (`model.enc.features.weight`), the ids of
     `test_cases` in their order, `batch_size` (the slice boundaries) -- and on nothing else; the weights enter in `scores()` only.
@@ -32,10 +33,13 @@ class ResidentSweep:
         self.engine = model.enc.engine
         self.cases = np.array(test_cases, dtype=np.int64).reshape(-1)
         self.n = int(len(self.cases))
-        lab = np.asarray(labels).reshape(-1)
-        if len(lab) != self.n:
-            raise ValueError("ResidentSweep: labels / test_cases length mismatch")
-        self.labels = torch.from_numpy(lab.astype(np.uint8)).to(self.engine.dev)          # uploaded once
+        self.labels = None                                       # `labels=None`: an unlabelled id list (top_k only; report() raises)
+        if labels is not None:
+            lab = np.asarray(labels).reshape(-1)
+            if len(lab) != self.n:
+                raise ValueError("ResidentSweep: labels / test_cases length mismatch")
+            self.labels = torch.from_numpy(lab.astype(np.uint8)).to(self.engine.dev)      # uploaded once
+        self.ids = torch.from_numpy(self.cases).to(self.engine.dev)                       # for top_k, uploaded once
         self.batch_size = int(batch_size)
         self.batches_per_launch = int(batches_per_launch)
         self.x1 = None
@@ -83,8 +87,16 @@ class ResidentSweep:
             call("ggad_mb_score", ptr(eng.params), eng.D, eng.F, ptr(self.x1), self.n, ptr(out))
         return out
 
-    def report(self, thres: float) -> Dict[str, float]:
+    def report(self, thres: float, scores: torch.Tensor = None) -> Dict[str, float]:
         """The dict of `metrics.binary_report` for the current weights, from `metrics.rank_report` (the faster of the two metric blocks
-        at 1.74 M scores: profiles/eval_cache_time_line.json)."""
+        at 1.74 M scores: profiles/eval_cache_time_line.json).  `scores`: a result of `scores()` the caller already holds."""
         from .metrics import rank_report
-        return rank_report(self.scores(), self.labels, thres)
+        if self.labels is None:
+            raise ValueError("ResidentSweep.report: this sweep was built without labels (an id list to rank: use top_k)")
+        return rank_report(self.scores() if scores is None else scores, self.labels, thres)
+
+    def top_k(self, k: int, scores: torch.Tensor = None):
+        """`metrics.top_k` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) with the
+        sweep's ids and resident labels: the `Ranked` head of the list, `ids` = node ids.  Nothing is uploaded and no plan is built."""
+        from .metrics import top_k
+        return top_k(self.scores() if scores is None else scores, k, self.labels, self.ids)

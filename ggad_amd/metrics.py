@@ -10,10 +10,15 @@ sklearn.  Definitions follow scikit-learn's (the reference's metric library), in
 sklearn itself stays the checker in the tests (tests/test_metrics.py).
 
 `rank_report` returns the same dict from float32 scores and uint8 labels through the counting kernels of csrc/rank_metrics.hip:
-no full sort (only the positives are sorted), four launches and ONE read-back."""
+no full sort (only the positives are sorted), four launches and ONE read-back.
+
+`top_k` is the ranked list: the k highest scores in a FIXED order (score descending, equal scores by ascending position; the head
+of a saturated sigmoid ranking is full of exact ties, and `torch.topk` fixes neither which tied elements it returns nor their
+order), with the running count of positives beside it, from `ggad_topk_f32` (csrc/topk.hip): six launches and ONE read-back."""
 from __future__ import annotations
 
-from typing import Dict
+from dataclasses import dataclass
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -115,3 +120,78 @@ def _report_from_out8(o, fallback) -> Dict[str, float]:
     gmean = float((tp * tn / ((tp + fn) * (tn + fp))) ** 0.5) if (tp + fn) and (tn + fp) else float("nan")
     return {"auc": float(o[0]), "ap": float(o[1]), "f1_1": f1_1, "f1_0": f1_0, "f1_macro": 0.5 * (f1_1 + f1_0), "gmean": gmean,
             "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+
+
+@dataclass
+class Ranked:
+    """The head of a ranking (`top_k`): rank j is the j-th highest score, equal scores in ascending position.  `pos` int32 positions
+    in the scored array, `ids` int64 (the caller's ids at those positions, or `pos` widened), `scores` float32, `cum_pos` int32 --
+    the label-1 elements among ranks 0..j -- or None without labels; all four on the device, `m` = min(k, n) long.  `n_pos`: the
+    label-1 elements among ALL scored elements (0 without labels); `tied_left_out`: elements that tie with the last rank's score and
+    did not make the list (> 0: the cut fell inside a tie)."""
+    pos: torch.Tensor
+    ids: torch.Tensor
+    scores: torch.Tensor
+    cum_pos: Optional[torch.Tensor]
+    m: int
+    n_pos: int
+    tied_left_out: int
+
+
+def top_k(scores: torch.Tensor, k: int, labels_u8: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None) -> Ranked:
+    """The `min(k, n)` highest of float32 device `scores`, ranked by score descending and, among equal scores, by ascending position
+    (-0.0 ties with +0.0): one `ggad_topk_f32` call and one read-back of its four meta words.  `labels_u8` (uint8, same shape):
+    `cum_pos` and `n_pos` are filled.  `ids` (int64, same shape): `Ranked.ids = ids[pos]`.  A NaN score, a label other than 0/1 or a
+    `k` outside 1..ggad_topk_max_k(): `ValueError`."""
+    from . import _lib
+    if scores.dtype != torch.float32 or scores.dim() != 1:
+        raise ValueError("top_k takes float32 scores of a 1-D shape")
+    if scores.device.type != "cuda":
+        raise ValueError("top_k takes scores on a GPU (there is no CPU path)")
+    if labels_u8 is not None and (labels_u8.dtype != torch.uint8 or labels_u8.shape != scores.shape or labels_u8.device != scores.device):
+        raise ValueError("top_k takes uint8 labels of the scores' shape on the same GPU")
+    if ids is not None and (ids.shape != scores.shape or ids.device != scores.device):
+        raise ValueError("top_k takes ids of the scores' shape on the same GPU")
+    lib = _lib.load()
+    check_k(k, "top_k", lib)
+    k = int(k)
+    n = scores.numel()
+    scores = scores.contiguous()
+    labels_u8 = labels_u8.contiguous() if labels_u8 is not None else None
+    dev = scores.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(int(lib.ggad_topk_workspace_elems(n, k)), dtype=torch.int32, device=dev)
+        pos = torch.empty(k, dtype=torch.int32, device=dev)
+        val = torch.empty(k, dtype=torch.float32, device=dev)
+        cum = torch.empty(k, dtype=torch.int32, device=dev) if labels_u8 is not None else None
+        meta = torch.empty(4, dtype=torch.int64, device=dev)
+        _lib.call("ggad_topk_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, k, _lib.ptr(pos), _lib.ptr(val), _lib.ptr(cum),
+                  _lib.ptr(meta), _lib.ptr(ws))
+        m, status, n_pos, left = (int(v) for v in meta.cpu().tolist())
+    if status == 3:
+        raise ValueError("top_k: a score is NaN")
+    if status == 4:
+        raise ValueError("top_k: a label is neither 0 nor 1")
+    pos = pos[:m]
+    wide = pos.long()
+    return Ranked(pos=pos, ids=ids.long()[wide] if ids is not None else wide, scores=val[:m], cum_pos=cum[:m] if cum is not None else None,
+                  m=m, n_pos=n_pos, tied_left_out=left)
+
+
+def check_k(k, who: str, lib=None) -> None:
+    """`ValueError` unless 1 <= k <= ggad_topk_max_k() (asked of the library: no GPU needed)."""
+    from . import _lib
+    cap = int((lib or _lib.load()).ggad_topk_max_k())
+    if int(k) != k or not 1 <= int(k) <= cap:
+        raise ValueError(f"{who}: k = {k} is outside 1..ggad_topk_max_k() = {cap} (the pairs one workgroup sorts in LDS)")
+
+
+def precision_recall_at(ranked: Ranked, j: int) -> Tuple[float, float]:
+    """(precision@j, recall@j) of a labelled `Ranked`, 1 <= j <= m: hits among the first j ranks over j and over `n_pos` (NaN when
+    there are no positives at all)."""
+    if ranked.cum_pos is None:
+        raise ValueError("precision_recall_at needs a ranking made with labels")
+    if not 1 <= int(j) <= ranked.m:
+        raise ValueError(f"precision_recall_at: j = {j} is outside 1..m = {ranked.m}")
+    hits = int(ranked.cum_pos[int(j) - 1])
+    return hits / int(j), (hits / ranked.n_pos if ranked.n_pos else float("nan"))

@@ -16,6 +16,10 @@ hard override `:317`), ``data`` = (adj_lists | DeviceGraph | (rowptr, col), feat
 the file loader, ``log_every``, ``n_pseudo`` (pseudo-anomalies per batch, default 50: the reference's `:342-347`).  Under `torch.distributed` (backend nccl = RCCL) batches are dealt
 round-robin over the ranks and gradients are all-reduced once per step.
 
+``top_k: K`` / ``top_k_out`` (`model: 'GCN'`, one GPU): the K highest scores of the closing test sweep are ranked on the device in a
+fixed order (`metrics.top_k`, csrc/topk.hip), kept in `self.ranked`, reported in one line and written to an `.npz`;
+`ModelHandler(config).score(checkpoint)` does the sweep, the report and the ranking from a saved checkpoint without training.
+
 The loader and split, the adjacency coercion, the checkpoint rule and the epoch loop of the labelled-batch models (`_train_sage`,
 `_train_sage_device`, `_train_pcgnn` build model, optimiser and containers and hand them to it) live in `handler_loop.py`; the GGAD
 loop (blocks of epochs through `trainer.run_steps`) is in `train` below.
@@ -35,7 +39,7 @@ import torch.nn as nn
 from .graph import DeviceGraph
 from .graphsage import GCN, Encoder, FeatureTable, GCNAggregator, GCNEncoder, GraphSage, MeanAggregator
 from .handler_loop import BestCheckpoint, device_graph, load_and_split, sweep_report, train_labelled
-from .sage_utils import test_sage
+from .sage_utils import score_nodes, test_sage
 from .sampler import PyCompatRandom
 from .trainer import BatchSchedule, DGraphTrainer
 
@@ -51,6 +55,23 @@ def _autograd_step(gnn_model, optimizer):
         optimizer.step()
         return out
     return step
+
+
+def write_ranked(path, ranked, labels=None):
+    """The `.npz` of config key `top_k_out`: `node` int64, `score` float32, `label` uint8, `cum_positives` int32 (both empty without
+    labels), `n_pos`, `tied_left_out`.  `labels`: the labels of the scored list, indexed by `ranked.pos`.  Entries are stored with a
+    fixed date, so equal rankings give equal files byte for byte."""
+    import zipfile
+    pos = ranked.pos.cpu().numpy()
+    has = labels is not None and ranked.cum_pos is not None
+    arrays = {"node": ranked.ids.cpu().numpy().astype(np.int64), "score": ranked.scores.cpu().numpy().astype(np.float32),
+              "label": np.asarray(labels).reshape(-1)[pos].astype(np.uint8) if has else np.zeros(0, dtype=np.uint8),
+              "cum_positives": ranked.cum_pos.cpu().numpy().astype(np.int32) if has else np.zeros(0, dtype=np.int32),
+              "n_pos": np.int64(ranked.n_pos), "tied_left_out": np.int64(ranked.tied_left_out)}
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+        for name, a in arrays.items():
+            with z.open(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w", force_zip64=True) as fh:
+                np.lib.format.write_array(fh, np.asanyarray(a), allow_pickle=False)
 
 
 def _report_sage(epoch, means, epoch_time):
@@ -73,27 +94,29 @@ class ModelHandler(object):
             if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                 raise ValueError("config key `eval_cache` runs on one GPU: the resident sweep is not sharded over the ranks of a "
                                  "torch.distributed world yet")
+        top_k, top_k_out = getattr(args, "top_k", 0) or 0, str(getattr(args, "top_k_out", "") or "")
+        if top_k or top_k_out:
+            if getattr(args, "model", None) != "GCN":
+                raise ValueError("config keys `top_k` / `top_k_out` need `model: 'GCN'`: the ranked list is made from the scores of the "
+                                 "GGAD test sweep (the other models' sweeps are not ranked)")
+            if not top_k:
+                raise ValueError("config key `top_k_out` needs `top_k: K` with K > 0: there is no ranking to write while `top_k` is 0")
+            from .metrics import check_k
+            check_k(top_k, "config key `top_k`")
+            if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+                raise ValueError("config keys `top_k` / `top_k_out` run on one GPU: the ranking is not made under a torch.distributed "
+                                 "world of several ranks yet")
+        self.ranked = None
         self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
 
-    def train(self):
+    def _build_gcn(self):
+        """The GGAD model as `src/model_handler.py:263-296` builds it, shared by `train` and `score`: device, graph (through the
+        binary CSR cache of the real data set), `FeatureTable`, aggregator, encoder, `GCN`, and the engine's optimiser settings.
+        Draws from torch's RNG exactly what the reference does.  Returns (dev, graph, features, gnn_model, engine)."""
         args = self.args
-        if args.model == "SAGE":
-            return self._train_sage()
-        if args.model == "PCGNN":
-            return self._train_pcgnn()
-        if args.model != "GCN":
-            raise NotImplementedError("models 'GCN' (GGAD), 'SAGE' and 'PCGNN' are trainable")
-        if not torch.cuda.is_available():
-            raise RuntimeError("ModelHandler.train needs an MI355X: the GGAD hot path has no CPU fallback")
-        dist = torch.distributed if (torch.distributed.is_available() and torch.distributed.is_initialized()) else None
-        world = dist.get_world_size() if dist else 1
-        rank = dist.get_rank() if dist else 0
         dev = torch.device("cuda", int(getattr(args, "device", torch.cuda.current_device())))
         torch.cuda.set_device(dev)
         feat_data, adj_lists = self.dataset["feat_data"], self.dataset["adj_lists"]
-        idx_train = self.dataset["idx_train"]
-        idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
-                                                self.dataset["idx_test"], self.dataset["y_test"])   # :260-261
         n, f = feat_data.shape
         # same RNG consumption as the reference: nn.Embedding's default init draws N x F normals (:263)
         nn.Embedding(n, f)
@@ -111,6 +134,86 @@ class ModelHandler(object):
         engine = enc_gcn.engine
         engine.lr, engine.wd = float(args.lr), float(args.weight_decay)
         engine.sync_params()
+        return dev, graph, features, gnn_model, engine
+
+    def _rank(self, scores, ids, labels, sweep, k, verbose=True):
+        """Config key `top_k` / `score(k=)`: the `Ranked` head of `scores` (the device scores of a sweep over `ids`, already made: nothing
+        is scored again), kept in `self.ranked`; one printed line; the `.npz` of config key `top_k_out`."""
+        from .metrics import precision_recall_at, top_k
+        if sweep is not None:
+            ranked = sweep.top_k(k, scores=scores)
+        else:
+            lab = None if labels is None else torch.from_numpy(np.asarray(labels).reshape(-1).astype(np.uint8)).to(scores.device)
+            ranked = top_k(scores, k, lab, torch.from_numpy(np.asarray(ids, dtype=np.int64).reshape(-1)).to(scores.device))
+        self.ranked = ranked
+        if verbose:
+            if ranked.cum_pos is not None and ranked.m:
+                prec, rec = precision_recall_at(ranked, ranked.m)
+                print(f"Top-{ranked.m}: precision@K {prec:.4f}\trecall@K {rec:.4f}\thits {int(ranked.cum_pos[-1])} of {ranked.n_pos}"
+                      f"\ttied left out {ranked.tied_left_out}")
+            else:
+                print(f"Top-{ranked.m}: no labels\ttied left out {ranked.tied_left_out}")
+            out = str(getattr(self.args, "top_k_out", "") or "")
+            if out:
+                write_ranked(out, ranked, labels)
+        return ranked
+
+    def score(self, checkpoint, ids=None, labels=None, k=None):
+        """Scores from a saved checkpoint, without training: the model is built as `train` builds it, the state dict of `checkpoint`
+        (a `.pkl` of `BestCheckpoint`) is loaded and the engine synchronised exactly as the restore at the end of `train` does, and
+        `ids` are swept in `test_sage`'s slices of `batch_size` (whose per-slice normalisation matters).  Default: the test split with
+        its labels, which follows from the config alone (`split_dgraphfin` reseeds itself from `seed`).  With labels `test_sage`'s report
+        is printed and its 5-tuple kept in `self.metrics`; with `k` (default: config key `top_k`) > 0 the scores are ranked (`_rank`).
+        Honours `eval_cache`.  Returns (device float32 scores, `Ranked` or None)."""
+        args = self.args
+        if args.model != "GCN":
+            raise NotImplementedError("ModelHandler.score serves model 'GCN' (GGAD)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("ModelHandler.score needs an MI355X: the GGAD hot path has no CPU fallback")
+        k = int(getattr(args, "top_k", 0) or 0) if k is None else int(k)
+        if k:
+            from .metrics import check_k
+            check_k(k, "ModelHandler.score")
+        _, _, _, gnn_model, engine = self._build_gcn()
+        self.model = gnn_model
+        gnn_model.load_state_dict(torch.load(checkpoint))
+        engine.sync_params()
+        if ids is None:
+            ids, labels = self.dataset["idx_test"], self.dataset["y_test"]
+        sweep = None
+        if bool(getattr(args, "eval_cache", False)):
+            from .eval_cache import ResidentSweep
+            sweep = ResidentSweep(gnn_model, ids, labels, args.batch_size)
+        self.eval_sweeps = (sweep, sweep)
+        self.metrics, self.sweep_ap = None, []
+        if labels is not None:
+            keep = []
+            self.metrics = test_sage(ids, labels, gnn_model, args.batch_size, args.thres, resident=sweep, keep=keep)
+            self.sweep_ap.append(getattr(test_sage, "last_ap", None))
+            scores = keep[0]
+        else:
+            scores = sweep.scores() if sweep is not None else score_nodes(gnn_model, ids, args.batch_size, device=True)
+        self.test_scores = scores
+        self.ranked = self._rank(scores, ids, labels, sweep, k) if k else None
+        return scores, self.ranked
+
+    def train(self):
+        args = self.args
+        if args.model == "SAGE":
+            return self._train_sage()
+        if args.model == "PCGNN":
+            return self._train_pcgnn()
+        if args.model != "GCN":
+            raise NotImplementedError("models 'GCN' (GGAD), 'SAGE' and 'PCGNN' are trainable")
+        if not torch.cuda.is_available():
+            raise RuntimeError("ModelHandler.train needs an MI355X: the GGAD hot path has no CPU fallback")
+        dist = torch.distributed if (torch.distributed.is_available() and torch.distributed.is_initialized()) else None
+        world = dist.get_world_size() if dist else 1
+        rank = dist.get_rank() if dist else 0
+        idx_train = self.dataset["idx_train"]
+        idx_valid, y_valid, idx_test, y_test = (self.dataset["idx_test"], self.dataset["y_test"],
+                                                self.dataset["idx_test"], self.dataset["y_test"])   # :260-261
+        _, graph, features, gnn_model, engine = self._build_gcn()
 
         best = BestCheckpoint(args.save_dir, args.data_name, args.model, write=rank == 0)   # every rank follows the rule, rank 0 saves
 
@@ -213,8 +316,14 @@ class ModelHandler(object):
             if dist and world > 1:
                 dist.broadcast(engine.params, src=0)          # every rank tests the restored weights
             engine.sync_params()
-        res = test_sage(idx_test, y_test, gnn_model, args.batch_size, args.thres, dist=dist, verbose=rank == 0, resident=sweep_test)
+        top_k = int(getattr(args, "top_k", 0) or 0)
+        keep = [] if top_k else None                 # config key `top_k`: the sweep's device scores are kept and ranked, not made twice
+        res = test_sage(idx_test, y_test, gnn_model, args.batch_size, args.thres, dist=dist, verbose=rank == 0, resident=sweep_test,
+                        keep=keep)
         self.sweep_ap.append(getattr(test_sage, "last_ap", None))
+        if top_k:
+            self.test_scores = keep[0]
+            self._rank(keep[0], idx_test, y_test, sweep_test, top_k, verbose=rank == 0)
         return res
 
 

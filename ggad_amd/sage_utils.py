@@ -100,12 +100,15 @@ def score_nodes(model, test_cases: Sequence[int], batch_size: int, batches_per_l
     return out if device else out.cpu().numpy()
 
 
-def test_sage(test_cases, labels, model, batch_size, thres=0.5, device_metrics=True, dist=None, verbose=True, resident=None):
+def test_sage(test_cases, labels, model, batch_size, thres=0.5, device_metrics=True, dist=None, verbose=True, resident=None,
+              keep=None):
     """Reference `test_sage` (`src/utils.py:207-247`): same prints, same return tuple.  `dist`: shard the sweep over the
     ranks (every rank returns the same metrics; pass verbose=False on the ranks that must not print).  `resident`: a
-    `ResidentSweep` (eval_cache.py) built for these `test_cases`, `labels` and `batch_size`; scores and metrics then come from it."""
+    `ResidentSweep` (eval_cache.py) built for these `test_cases`, `labels` and `batch_size`; scores and metrics then come from it.
+    `keep`: a list that receives the sweep's scores (device tensor on the two device paths), for a caller that ranks them."""
     if resident is not None:
-        r = resident.report(thres)
+        probs = resident.scores()
+        r = resident.report(thres, scores=probs)
         f1_binary_1, f1_binary_0, f1_macro, auc_gnn, ap, gmean = r["f1_1"], r["f1_0"], r["f1_macro"], r["auc"], r["ap"], r["gmean"]
         tn, fp, fn, tp = r["tn"], r["fp"], r["fn"], r["tp"]
     elif device_metrics:
@@ -126,6 +129,8 @@ def test_sage(test_cases, labels, model, batch_size, thres=0.5, device_metrics=T
         conf = confusion_matrix(labels, preds)
         tn, fp, fn, tp = conf.ravel()
         gmean = conf_gmean(conf)
+    if keep is not None:
+        keep.append(probs)
     if verbose:
         print(f"   GNN F1-binary-1: {f1_binary_1:.4f}\tF1-binary-0: {f1_binary_0:.4f}" +
               f"\tF1-macro: {f1_macro:.4f}\tG-Mean: {gmean:.4f}\tAUC: {auc_gnn:.4f}")

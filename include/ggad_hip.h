@@ -1131,6 +1131,24 @@ int64_t ggad_rank_metrics_workspace_elems(int64_t n);          /* int32 elements
 int ggad_rank_metrics_f32(const float *score, const uint8_t *label, int64_t n, float thres, double *out8, int32_t *workspace,
                           ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Exact, deterministic top-k of n float32 scores (topk.hip).  Ranking: score descending; equal scores by ascending position in the
+ * input; -0.0 ties with +0.0; +-inf are ordinary values.  With m = min(k, n): out_pos[0..m) the positions of the top m in that order,
+ * out_score[j] their scores bit for bit, out_cumpos[j] (may be NULL) the number of label-1 elements among ranks 0..j (label may be
+ * NULL: all 0); entries m..k) hold pos -1, score 0, cumpos out_cumpos[m-1] (0 when m = 0).  out_meta (device, 4 int64) = {m, status,
+ * P = label-1 elements among all n, elements that tie with rank m-1's score and were left out}; status 0 ok, 3 a NaN score, 4 a label
+ * other than 0/1 (the other outputs are then unspecified): the codes of ggad_rank_metrics_f32.
+ *
+ * 1 <= k <= ggad_topk_max_k() (16,384: the pairs of one workgroup's sort in LDS), 0 <= n <= INT32_MAX; outside: GGAD_E_INVALID and no
+ * launch.  Six launches on `stream`, no host synchronisation, integer atomics only, nothing that waits on another workgroup; equal
+ * inputs give equal bits.  workspace: ggad_topk_workspace_elems(n, k) int32 elements (0 = refused), no preparation needed: every word
+ * a launch reads was written by an earlier launch of the same call, so the call is capturable and replayable.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_topk_max_k(void);
+int64_t ggad_topk_workspace_elems(int64_t n, int32_t k);       /* int32 elements; 0 = refused */
+int ggad_topk_f32(const float *score, const uint8_t *label, int64_t n, int32_t k, int32_t *out_pos, float *out_score,
+                  int32_t *out_cumpos, int64_t *out_meta, int32_t *workspace, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,8 +61,15 @@ def use_handler(name):
     HANDLER = H
 
 
+SCORE = None          # --score CKPT: score from this checkpoint instead of training
+
+
 def run_once(config):
     set_random_seed(config["seed"])
+    if SCORE is not None:
+        handler = HANDLER(config)
+        handler.score(SCORE)
+        return handler.metrics
     return HANDLER(config).train()
 
 
@@ -116,11 +123,25 @@ if __name__ == "__main__":
     ap.add_argument("--num_epochs", type=int, default=None, help="override the config's num_epochs")
     ap.add_argument("--handler", choices=["ggad", "dominant", "anomalydae", "aegis"], default="ggad",
                     help="which ModelHandler drives the run: GGAD (default) or one of the mini-batch comparison models")
+    ap.add_argument("--score", type=str, default=None, metavar="CKPT",
+                    help="--handler ggad only: no training; load this checkpoint (the .pkl a run saved), sweep the test split of the "
+                         "config's seed, print its report and, with top_k > 0, the ranked list")
+    ap.add_argument("--top_k", type=int, default=None, help="override the config's top_k (rank the K highest test scores; 0 = off)")
+    ap.add_argument("--top_k_out", type=str, default=None, help="override the config's top_k_out (.npz of the ranked list)")
     a = ap.parse_args()
+    if a.score is not None and a.handler != "ggad":
+        ap.error("--score serves --handler ggad only")
+    if a.score is not None and a.multi_run:
+        ap.error("--score scores one checkpoint: it does not go with --multi_run")
     with open(a.config, "r") as fh:
         cfg = yaml.load(fh, Loader=yaml.FullLoader)
     if a.num_epochs is not None:
         cfg["num_epochs"] = a.num_epochs
+    if a.top_k is not None:
+        cfg["top_k"] = a.top_k
+    if a.top_k_out is not None:
+        cfg["top_k_out"] = a.top_k_out
+    SCORE = a.score
     use_handler(a.handler)
     init_distributed()
     torch.set_num_threads(min(8, os.cpu_count() or 1))        # host tensors are tiny here; 128 intra-op threads only add jitter
