@@ -16,6 +16,7 @@
 // atomics, no workgroup waits on another, so a replayed hipGraph equals an eager epoch bit for bit.  Variance partials are
 // (count, mean, M2) merged with Chan's formula, not sums of squares.
 #include "common.h"
+#include "handoff.h"
 
 #define BN_C 64            // channels the kernels take (hid_dim of both MLPs, model_AEGIS.py:163)
 #define BN_ROWS 256        // rows per statistics workgroup before the grid saturates
@@ -24,27 +25,6 @@
 #define LOSS_MAX_G 256
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
-// agent-scope hand-off of one workgroup's partials to the last workgroup of the launch (cdna_hip_programming §6 Guideline 16, the
-// counter form): every wave drains its stores, the barrier, one release fence, the ticket.  Returns true in the last workgroup,
-// after its acquire; that workgroup puts the ticket back to zero.
-__device__ __forceinline__ bool last_workgroup(int32_t *ticket, int *flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = (t == (int)gridDim.x - 1) ? 1 : 0;
-    if (*flag) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-  return *flag != 0;
-}
 
 // (n, mean, M2) <- (n, mean, M2) merged with (nb, mb, M2b): Chan et al.; an empty side leaves the other unchanged
 __device__ __forceinline__ void chan_merge(float &n, float &mean, float &m2, float nb, float mb, float m2b) {
@@ -114,7 +94,7 @@ __global__ __launch_bounds__(256) void k_bn_stats(const float *__restrict__ h1, 
     part[1 + BN_C + t] = pq;
     if (t == 0) part[0] = pn;
   }
-  if (!last_workgroup(ticket, &flag)) return;
+  if (!ggad_last_of(ticket, (int)gridDim.x, &flag)) return;
   // t = quarter * 64 + column: quarter q merges partials [G q / 4, G (q + 1) / 4)
   const int q = t >> 6, c = t & 63;
   {
@@ -252,7 +232,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_sums(const float *__restrict__ h
     for (int s = 0; s < 16; ++s) acc += s_dl[s];
     part[t] = acc;
   }
-  if (!last_workgroup(ticket, &flag)) return;
+  if (!ggad_last_of(ticket, (int)gridDim.x, &flag)) return;
   if (t < W) {
     float acc = 0.f;
     for (int q = 0; q < G; ++q) acc += ws[(int64_t)q * W + t];
@@ -328,7 +308,7 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float *__restrict__ p, i
     ws[2 * b] = ((s_ae[0] + s_ae[1]) + s_ae[2]) + s_ae[3];
     ws[2 * b + 1] = ((s_g[0] + s_g[1]) + s_g[2]) + s_g[3];
   }
-  if (!last_workgroup(ticket, &flag)) return;
+  if (!ggad_last_of(ticket, (int)gridDim.x, &flag)) return;
   if (w == 0) {
     float a = 0.f, q = 0.f;
     for (int k = lane; k < G; k += GGAD_WAVE) {

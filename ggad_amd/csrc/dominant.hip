@@ -22,6 +22,7 @@
 // ceil(F/16) <= DOM_MAX_FT, ceil(H/16) <= DOM_MAX_HT and the tile's LDS fits 64 KiB; ggad_dominant_ae_supported says so.
 // n_h = 300 holds F <= 96.
 #include "common.h"
+#include "handoff.h"
 
 #define DOM_THREADS 512                  // 8 waves
 #define DOM_WAVES (DOM_THREADS / GGAD_WAVE)
@@ -37,26 +38,6 @@
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// agent-scope hand-off to the last of `count` workgroups that share `ticket` (the counter form of aegis.hip): every wave drains
-// its stores, the barrier, one release fence, the ticket.  Returns true in the last one, after its acquire; it resets the ticket.
-__device__ __forceinline__ bool dom_last_of(int32_t *ticket, int count, int *flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = (t == count - 1) ? 1 : 0;
-    if (*flag) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-  return *flag != 0;
-}
 
 // out[e] = sum_{k < cnt} src[k * P + e] in k order, cnt <= DOM_GROUP (plain loads behind the acquire; all cnt of an element in
 // flight before the first add)
@@ -229,11 +210,11 @@ __global__ __launch_bounds__(DOM_THREADS) void k_dominant_ae(
   // first level: the last workgroup of group g adds the group's partials in order
   const int NG = (int)((G + DOM_GROUP - 1) / DOM_GROUP), g = (int)(b / DOM_GROUP);
   const int g0 = g * DOM_GROUP, gcnt = (int)((G - g0) < DOM_GROUP ? (G - g0) : DOM_GROUP);
-  if (!dom_last_of(tickets + g, gcnt, &flag)) return;
+  if (!ggad_last_of(tickets + g, gcnt, &flag)) return;
   float *gpart = ws + G * P + (int64_t)g * P;
   dom_sum_partials(ws + (int64_t)g0 * P, gcnt, P, gpart);
   // second level: the last group adds the group sums in order into the outputs
-  if (!dom_last_of(tickets + DOM_MAX_G / DOM_GROUP, NG, &flag)) return;
+  if (!ggad_last_of(tickets + DOM_MAX_G / DOM_GROUP, NG, &flag)) return;
   const float *gs = ws + G * P;
   for (int64_t e = tid; e < P; e += DOM_THREADS) {
     float v[DOM_MAX_G / DOM_GROUP];
@@ -292,7 +273,7 @@ __global__ __launch_bounds__(256) void k_dominant_recon(const float *__restrict_
   if (lane == 0) s_l[w] = ls;
   __syncthreads();
   if (tid == 0) ws[b] = ((s_l[0] + s_l[1]) + s_l[2]) + s_l[3];
-  if (!dom_last_of(ticket, (int)G, &flag)) return;
+  if (!ggad_last_of(ticket, (int)G, &flag)) return;
   if (tid == 0) {
     float s = 0.f;
     for (int64_t k = 0; k < G; ++k) s += __hip_atomic_load(ws + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

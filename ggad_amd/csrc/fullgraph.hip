@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "handoff.h"
 
 namespace {
 
@@ -1107,25 +1108,10 @@ __global__ void __launch_bounds__(1024) k_prelu_bwd_final_wide(const float *__re
   if (threadIdx.x == 0 && da) *da = qa[0];
 }
 
-// Hand-offs between workgroups of ONE launch without an agent-scope release FENCE: that fence writes back every dirty line of the
-// XCD's L2 -- in a kernel that is itself streaming out N x H floats (dz) each of its 320 fences flushed that stream: 50 us instead of
-// 20.  The partial sums are instead STORED with agent-scope relaxed atomics (sc1: written through to memory), the wave drains its
-// store counter (s_waitcnt vmcnt(0)) before the workgroup barrier, one thread draws the ticket (agent-scope RMW), and the reader uses
-// agent-scope relaxed atomic LOADS (sc1: not served from a stale L2 line of an earlier launch).  Same hardware reasoning as the
-// tagged-slot barrier of step_xcd.hip and the granules of exchange.cpp; tests/test_fullgraph_gpu.py re-runs the kernel on the same
-// workspace with different data and checks every sum.
-__device__ __forceinline__ void st_agent16(float4 *p, float4 v) {
-  unsigned long long *q = reinterpret_cast<unsigned long long *>(p);
-  __hip_atomic_store(q, ((unsigned long long)__float_as_uint(v.y) << 32) | __float_as_uint(v.x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(q + 1, ((unsigned long long)__float_as_uint(v.w) << 32) | __float_as_uint(v.z), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float4 ld_agent16(const float4 *p) {
-  const unsigned long long *q = reinterpret_cast<const unsigned long long *>(p);
-  const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return make_float4(__uint_as_float((unsigned)a), __uint_as_float((unsigned)(a >> 32)), __uint_as_float((unsigned)b), __uint_as_float((unsigned)(b >> 32)));
-}
-__device__ __forceinline__ float ld_agent(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// k_prelu_bwd_one hands its partial sums off WITHOUT an agent-scope release fence (handoff.h, ggad_last_of_sc1): that fence writes
+// back every dirty line of the XCD's L2 -- in a kernel that is itself streaming out N x H floats (dz) each of its 320 fences flushed
+// that stream: 50 us instead of 20.  So every partial is stored with st_agent16 and every load of one is ld_agent / ld_agent16.
+// tests/test_fullgraph_gpu.py re-runs the kernel on the same workspace with different data and checks every sum.
 
 // the fixed-order reduction of the S partial rows by ONE workgroup of 1,024 threads (W <= 1024): shared by the trailing launch
 // k_prelu_bwd_final and by the last workgroup of k_prelu_bwd_one
@@ -1249,12 +1235,7 @@ __global__ void __launch_bounds__(1024) k_prelu_bwd_one(const float4 *__restrict
   //   workgroup performs it does not matter.  ticket[0]: groups done, ticket[1 + g]: workgroups of group g done; all left at zero.
   const int gid = blockIdx.x / PB_GRP, n_groups = (gridDim.x + PB_GRP - 1) / PB_GRP;
   const int gsize = min(PB_GRP, (int)gridDim.x - gid * PB_GRP);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's write-through stores are acknowledged ...
-  __syncthreads();                                   // ... every wave's are: the ticket may be drawn
-  if (t == 0) last = (__hip_atomic_fetch_add(ticket + 1 + gid, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gsize - 1) ? 1 : 0;
-  __syncthreads();
-  if (!last) return;
-  if (t == 0) ticket[1 + gid] = 0;
+  if (!ggad_last_of_sc1(ticket + 1 + gid, gsize, &last)) return;
   if (t < 2 * nvec) {                                // float4 column t of [db | da] of the group row
     const float4 *src = (t < nvec ? part_db : part_da) + (int64_t)gid * PB_GRP * nvec + (t < nvec ? t : t - nvec);
     float4 v[PB_GRP];
@@ -1266,12 +1247,7 @@ __global__ void __launch_bounds__(1024) k_prelu_bwd_one(const float4 *__restrict
       if (k < gsize) { acc.x += v[k].x; acc.y += v[k].y; acc.z += v[k].z; acc.w += v[k].w; }
     st_agent16((t < nvec ? gpart_db : gpart_da) + (int64_t)gid * nvec + (t < nvec ? t : t - nvec), acc);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (t == 0) last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == n_groups - 1) ? 1 : 0;
-  __syncthreads();
-  if (!last) return;
-  if (t == 0) *ticket = 0;
+  if (!ggad_last_of_sc1(ticket, n_groups, &last)) return;
   prelu_final_body<true>(reinterpret_cast<const float *>(gpart_db), reinterpret_cast<const float *>(gpart_da), n_groups, nvec * 4, db, da,
                          reinterpret_cast<float *>(sb), reinterpret_cast<float *>(sa));
 }
@@ -1622,18 +1598,9 @@ __global__ void __launch_bounds__(LF_T) k_loss_fwd_fused(const float *__restrict
       }
     }
   }
-  // this workgroup's aff / ws stores reach memory before its ticket: the barrier orders every wave's stores before thread 0 (they have
-  // reached the L2: workgroup-scope release), thread 0's agent-scope release writes the L2's dirty lines back -- ONE write-back per
-  // workgroup (a release fence in every wave -- 2,300 L2 write-backs per launch -- made this kernel 28-32 us at Reddit size)
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    last = (__hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) ? 1 : 0;
-  }
-  __syncthreads();
-  if (!last) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // ... and everyone else's are read from memory, not from a stale line
-  if (threadIdx.x == 0) *ticket = 0;
+  // this workgroup's aff / ws stores reach memory before its ticket (handoff.h): ONE release per workgroup (a release fence in every
+  // wave -- 2,300 L2 write-backs per launch -- made this kernel 28-32 us at Reddit size)
+  if (!ggad_last_of(ticket, (int)gridDim.x, &last)) return;
   auto block_sum = [&](float v) {                             // 16 waves, added in wave order
     v = wave_sum(v);
     __syncthreads();
@@ -1867,7 +1834,7 @@ __global__ void __launch_bounds__(256) k_adam_multi(AdamMulti A, float lr, float
   }
   if (tickets) {
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {                                    // this ticket hands over no data, it only counts arrivals (handoff.h)
       const int nb = A.blk0[t + 1] - A.blk0[t];
       if (__hip_atomic_fetch_add(tickets + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nb - 1) {
         tickets[t] = 0;

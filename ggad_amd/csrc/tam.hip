@@ -23,6 +23,7 @@
 // most four).  A row's sum runs in CSR order with TAM_FLY neighbour rows in flight per wave; every load is unconditional with its
 // index clamped (a clamped entry gets the weight 0).  No float atomics, no workgroup waits on another: equal inputs give equal bits.
 #include "common.h"
+#include "handoff.h"
 #include <algorithm>
 
 #define TAM_MAX_H 256
@@ -31,8 +32,6 @@
 #define TAM_MAX_G 256        // workgroups (partial slots) of k_tam_reduce
 #define TAM_SLOT 8           // words per slot: lo, hi, S, n_lo, n_hi, n_nan, -, -
 #define TAM_SCAL 8           // floats of the scalar block: loss, lo, hi, n_lo, n_hi, S, -, -
-
-__device__ __forceinline__ float tam_ld(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ------------------------------------------------------------------------------------------------ inv
 __global__ void __launch_bounds__(256) k_tam_inv(const float *__restrict__ E, int n, int h, float *__restrict__ inv) {
@@ -134,25 +133,19 @@ __global__ void __launch_bounds__(256) k_tam_gather(const int32_t *__restrict__ 
   }
 
   if (hb >= 0) {
-    // the piece's part of den_i, then the hub's ticket: the whole wave drains and releases its stores before lane 0 draws
+    // the piece's part of den_i, then the hub's ticket (handoff.h, the wave form)
     float *pv = part_v + (int64_t)piece * h;
 #pragma unroll
     for (int q = 0; q < Q; ++q)
       if (lane + 64 * q < h) pv[lane + 64 * q] = acc[q];
     const int first = hub_pp[hb], cnt = hub_pp[hb + 1] - first;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    int t = 0;
-    if (lane == 0) t = __hip_atomic_fetch_add(tickets + hb, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    t = __shfl(t, 0, GGAD_WAVE);
-    if (t != cnt - 1) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (lane == 0) __hip_atomic_store(tickets + hb, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!ggad_last_wave_of(tickets + hb, cnt)) return;
 #pragma unroll
     for (int q = 0; q < Q; ++q) acc[q] = 0.f;
     for (int k = 0; k < cnt; ++k) {                        // piece order
       const float *pk = part_v + (int64_t)(first + k) * h;
 #pragma unroll
-      for (int q = 0; q < Q; ++q) acc[q] += tam_ld(pk + ch[q]);
+      for (int q = 0; q < Q; ++q) acc[q] += ld_agent(pk + ch[q]);
     }
   }
   float dot = 0.f;
@@ -196,25 +189,6 @@ __device__ __forceinline__ void tam_block_merge(TamPart &x, TamPart *sh) {
     for (int w = 1; w < 4; ++w) tam_merge(x, sh[w]);
 }
 
-// the hand-off of aegis.hip's last_workgroup: every wave drains its stores, the barrier, one release fence, the ticket
-__device__ __forceinline__ bool tam_last_workgroup(int32_t *ticket, int *flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int t = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = (t == (int)gridDim.x - 1) ? 1 : 0;
-    if (*flag) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
-  return *flag != 0;
-}
-
 __global__ void __launch_bounds__(256) k_tam_reduce(const int32_t *__restrict__ rowptr, const float *__restrict__ inv,
                                                     const float *__restrict__ r_inv, const float *__restrict__ cnt, float K, int n,
                                                     const int32_t *__restrict__ hub_rows, const int32_t *__restrict__ hub_pp, int n_hub,
@@ -245,12 +219,12 @@ __global__ void __launch_bounds__(256) k_tam_reduce(const int32_t *__restrict__ 
     sl[0] = x.lo; sl[1] = x.hi; sl[2] = x.s;
     sl[3] = __int_as_float(x.n_lo); sl[4] = __int_as_float(x.n_hi); sl[5] = __int_as_float(x.n_nan);
   }
-  if (!tam_last_workgroup(ticket, &flag)) return;
+  if (!ggad_last_of(ticket, G, &flag)) return;
   TamPart y = {INFINITY, -INFINITY, 0.f, 0, 0, 0};
   if (t < G) {                                             // G <= 256: slot t in thread t, merged in slot order by the fixed tree
     const float *sl = slots + (int64_t)t * TAM_SLOT;
-    y.lo = tam_ld(sl); y.hi = tam_ld(sl + 1); y.s = tam_ld(sl + 2);
-    y.n_lo = __float_as_int(tam_ld(sl + 3)); y.n_hi = __float_as_int(tam_ld(sl + 4)); y.n_nan = __float_as_int(tam_ld(sl + 5));
+    y.lo = ld_agent(sl); y.hi = ld_agent(sl + 1); y.s = ld_agent(sl + 2);
+    y.n_lo = __float_as_int(ld_agent(sl + 3)); y.n_hi = __float_as_int(ld_agent(sl + 4)); y.n_nan = __float_as_int(ld_agent(sl + 5));
   }
   tam_block_merge(y, sh);
   if (t == 0) {

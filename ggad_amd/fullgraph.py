@@ -39,6 +39,7 @@ class FullGraphAdj:
     def __init__(self, adj_norm, raw, device):
         import scipy.sparse as sp
         self.dev = torch.device(device)
+        ticket_block(self.dev)                                   # exists before any capture of an epoch on this graph
         an = sp.csr_matrix(adj_norm)
         self.n = an.shape[0]
         self.A = Csr(an, self.dev)
@@ -392,16 +393,25 @@ def padded_constant(adj: "FullGraphAdj", x: torch.Tensor):
 
 
 _PRELU_ONE = os.environ.get("GGAD_PRELU_ONE", "1") != "0"            # 0: k_prelu_bwd_v4 + the trailing k_prelu_bwd_final launch (A/B)
-_TICKET_WORDS = {}
+_TICKET_BLOCKS: Dict[str, torch.Tensor] = {}
 
 
-def _ticket_word(device) -> torch.Tensor:
-    """One zeroed int32 per (device, stream): the ticket of the single-launch reductions (launches of one stream are ordered, so they
-    can share it; the kernels leave it zero).  Allocated on first use -- in an eager epoch, before any capture."""
-    key = (str(device), torch.cuda.current_stream(device).cuda_stream if torch.device(device).type == "cuda" else 0)
-    t = _TICKET_WORDS.get(key)
+def ticket_block(device) -> torch.Tensor:
+    """The device's ticket words of the single-launch reductions (csrc/handoff.h): zeroed int32, as many as the largest user needs.
+
+    Contract: the kernels leave the block zero, and all ticket-bearing launches of a device are ordered on one stream or in one
+    captured chain, so they can share it.  Allocated on first use, which must be outside a capture (`FullGraphAdj.__init__` sees
+    to it): a tensor made inside one would live in the graph's private pool with a fill node in every replay."""
+    device = torch.device(device)
+    t = _TICKET_BLOCKS.get(str(device))
     if t is None:
-        t = _TICKET_WORDS[key] = torch.zeros(max(1, int(_lib.load().ggad_prelu_bwd_one_tickets())), dtype=torch.int32, device=device)
+        if _capturing(device):
+            raise RuntimeError("ticket_block({}) would allocate inside a stream capture: build the FullGraphAdj (or call "
+                               "ticket_block) before capturing".format(device))
+        lib = _lib.load()
+        n = max(int(lib.ggad_prelu_bwd_one_tickets()), int(lib.ggad_dominant_tickets()), 1)
+        t = torch.zeros((n + 3) // 4 * 4, dtype=torch.int32, device=device)
+        t = _TICKET_BLOCKS[str(device)] = _TICKET_BLOCKS.setdefault(str(t.device), t)      # "cuda" and "cuda:0": one block
     return t
 
 
@@ -465,7 +475,7 @@ class GcnLayerFn(torch.autograd.Function):
         da = torch.empty(1, dtype=torch.float32, device=z.device)
         if _PRELU_ONE:                                                       # round 6: the column reduction inside the same launch
             call("ggad_prelu_bwd_one_f32", ptr(g), ptr(z), ptr(prelu_a), M, W, ptr_rows(dz), dz.stride(0), ptr(db), ptr(da), ptr(ws),
-                 ptr(_ticket_word(z.device)))
+                 ptr(ticket_block(z.device)))
         else:
             call("ggad_prelu_bwd_ld_f32", ptr(g), ptr(z), ptr(prelu_a), M, W, ptr_rows(dz), dz.stride(0), ptr(db), ptr(da), ptr(ws))
         if ctx.reordered:                                                    # x holds A_hat X here

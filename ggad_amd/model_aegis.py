@@ -37,7 +37,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import FullGraphAdj, GcnLayerFn, _capturing, _ticket_word, gemm, spmm
+from .fullgraph import FullGraphAdj, GcnLayerFn, _capturing, gemm, spmm, ticket_block
 from .graphsage_aegis import MLP
 from .model import GCN, AvgReadout, MaxReadout, MinReadout, WSReadout, as_full_adj
 from .model import Discriminator
@@ -77,7 +77,7 @@ def bn_forward(h1, h2, bn: nn.BatchNorm1d, act: int, rows=None, head=None, updat
     rc = int(_lib.load().ggad_aegis_bn_fwd_f32(
         ptr(h1), m1, h1.stride(0), ptr(h2) if h2 is not None else 0, m2, h2.stride(0) if h2 is not None else 0, C, ptr(gamma), ptr(beta),
         eps, mom, ptr(rm) if update else 0, ptr(rv) if update else 0, ptr(nbt) if update else 0, act, ptr(rows), n_out, y_ptr, ldy,
-        w2p, b2p, pp, ptr(mean), ptr(invstd), ptr(ws), ptr(_ticket_word(dev)), _lib.current_stream()))
+        w2p, b2p, pp, ptr(mean), ptr(invstd), ptr(ws), ptr(ticket_block(dev)), _lib.current_stream()))
     if rc == _lib.GGAD_E_UNSUPPORTED:
         raise ValueError("the AEGIS batch-norm kernels take {} channels, not {}".format(int(_lib.load().ggad_aegis_bn_channels()), C))
     if rc == _lib.GGAD_E_INVALID and M < 2:
@@ -103,7 +103,7 @@ def _bn_backward(h, gamma, beta, mean, invstd, act, dy=None, head=None):
         args = (ptr(dy), dy.stride(0), 0, 0, 0)
     ws = _bn_ws(M, C, dev)
     call("ggad_aegis_bn_bwd_f32", ptr(h), M, h.stride(0), C, ptr(gamma), ptr(beta), ptr(mean), ptr(invstd), act, *args, ptr(dh),
-         dh.stride(0), ptr(dgamma), ptr(dbeta), ptr(dw2), ptr(db2), ptr(ws), ptr(_ticket_word(dev)))
+         dh.stride(0), ptr(dgamma), ptr(dbeta), ptr(dw2), ptr(db2), ptr(ws), ptr(ticket_block(dev)))
     return dh, dgamma, dbeta, dw2, db2
 
 
@@ -224,7 +224,7 @@ def aegis_losses(p, zd, x, rs):
     ws = torch.empty(int(_lib.load().ggad_aegis_loss_workspace_elems(n, rs["n_rows"])), dtype=torch.float32, device=dev)
     p, zd = p.contiguous(), zd.contiguous()
     call("ggad_aegis_loss_fwd_f32", ptr(p), n, ptr(x), F_, ptr(zd), zd.stride(0), ptr(rs["rows"]), rs["n_rows"], ptr(attr),
-         vals.data_ptr(), vals.data_ptr() + 4, ptr(ws), ptr(_ticket_word(dev)))
+         vals.data_ptr(), vals.data_ptr() + 4, ptr(ws), ptr(ticket_block(dev)))
     pd, zdd = p.detach(), zd.detach()
     loss_g = _LossGFn.apply(p, vals[0], zdd, x, rs, attr)
     loss_ae = _LossAeFn.apply(zd, vals[1], pd, x, rs, attr)

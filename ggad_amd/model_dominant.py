@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import Csr, FullGraphAdj, _capturing, _ticket_word, gemm, spmm
+from .fullgraph import Csr, FullGraphAdj, _capturing, gemm, spmm, ticket_block
 from .model import AvgReadout, Discriminator, MaxReadout, MinReadout, WSReadout, as_full_adj
 from .model_anomalydae import LinearBiasFn
 
@@ -143,18 +143,6 @@ def ae_rows(adj: FullGraphAdj, idx_train, idx_test) -> dict:
     return s
 
 
-_TICKETS = {}
-
-
-def _tickets(dev) -> torch.Tensor:
-    """ggad_dominant_tickets() zeroed int32 per (device, stream), left zero by the kernels; allocated in an eager epoch."""
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    t = _TICKETS.get(key)
-    if t is None:
-        t = _TICKETS[key] = torch.zeros(int(_lib.load().ggad_dominant_tickets()), dtype=torch.int32, device=dev)
-    return t
-
-
 def _scaled(src: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(src)
     call("ggad_dominant_scale_f32", ptr(src), src.numel(), ptr(g), ptr(out))
@@ -179,7 +167,7 @@ def fused_ae(x, w1, b1, w2, b2, rs):
     rc = int(_lib.load().ggad_dominant_ae_f32(ptr(x), F_, ptr(rs["rows"]), m, t, ptr(w1), ptr(b1), ptr(w2), ptr(b2), H,
                                               ptr(score) if t else 0, ptr(loss), grads.data_ptr(), grads.data_ptr() + 4 * HF,
                                               grads.data_ptr() + 4 * (HF + H), grads.data_ptr() + 4 * (2 * HF + H), ptr(ws),
-                                              ptr(_tickets(dev)), _lib.current_stream()))
+                                              ptr(ticket_block(dev)), _lib.current_stream()))
     if rc == _lib.GGAD_E_UNSUPPORTED:
         raise ValueError("the fused DOMINANT autoencoder does not hold n_in = {}, n_h = {}: use the wide path".format(F_, H))
     _lib.check(rc, "ggad_dominant_ae_f32")
@@ -223,7 +211,7 @@ class ReconFn(torch.autograd.Function):
         dxh = torch.empty_like(xh)
         ws = torch.empty(int(_lib.load().ggad_dominant_recon_workspace_elems(n, rs["m"], rs["t"])), dtype=torch.float32, device=dev)
         call("ggad_dominant_recon_f32", ptr(x), ptr(xh), n, F_, ptr(rs["rows"]), rs["m"], rs["t"], ptr(rs["pos"]),
-             ptr(score) if rs["t"] else 0, ptr(loss), ptr(dxh), ptr(ws), ptr(_ticket_word(dev)))
+             ptr(score) if rs["t"] else 0, ptr(loss), ptr(dxh), ptr(ws), ptr(ticket_block(dev)))
         ctx.save_for_backward(dxh)
         ctx.mark_non_differentiable(score)
         return loss[0], score

@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import call, ptr
-from .fullgraph import FullGraphAdj, _capturing, _dev_i32, _ticket_word, gemm
+from .fullgraph import FullGraphAdj, _capturing, _dev_i32, gemm, ticket_block
 from .graphsage_aegis import MLP
 from .model import AvgReadout, Discriminator, MaxReadout, MinReadout, WSReadout, as_full_adj
 from .model_aegis import ACT_RELU, BnActFn, _LossAeFn, bn_forward, loss_rows
@@ -164,7 +164,7 @@ def _attr(x_, x, rs, value):
     attr = torch.empty(rs["n_rows"], dtype=torch.float32, device=dev)
     ws = torch.empty(int(_lib.load().ggad_aegis_loss_workspace_elems(0, rs["n_rows"])), dtype=torch.float32, device=dev)
     call("ggad_aegis_loss_fwd_f32", 0, 0, ptr(x), F_, ptr(x_), x_.stride(0), ptr(rs["rows"]), rs["n_rows"], ptr(attr), 0, ptr(value),
-         ptr(ws), ptr(_ticket_word(dev)))
+         ptr(ws), ptr(ticket_block(dev)))
     return attr
 
 

@@ -260,12 +260,16 @@ int ggad_adae_attr_bwd_f32(const float *x, const float *xhat, const int64_t *row
  *   (rows NULL: k < n_out <= M): y (row stride ldy) when w2 is NULL, else the head p[k] = sigmoid(y . w2 + b2) without y.
  *   M < 2 -> GGAD_E_INVALID (torch: more than 1 value per channel); C != ggad_aegis_bn_channels() -> GGAD_E_UNSUPPORTED, nothing
  *   launched.  Rows are 16-byte aligned (strides multiples of 4).  ws = ggad_aegis_bn_workspace_elems(M, C) floats; ticket = one
- *   zeroed int32 the kernels leave zero.  Two launches.
+ *   int32.  Two launches.
+ *   TICKET WORDS, here and at every `ticket` / `tickets` parameter of this header: int32 in device memory that count the workgroups
+ *   of a launch as they finish (csrc/handoff.h).  They must be ZERO before the first call; every launch leaves them zero, so they
+ *   need no clearing between calls; launches that are ordered on one stream (or in one captured chain) may share them, launches
+ *   that can run concurrently may not.
  * ggad_aegis_bn_bwd_f32: the backward of one block (h: M x C, ldh) from dy (M x C, lddy) or, with the head (w2 non-NULL), from p and
  *   dp = d loss / d p: dh (lddh), dgamma, dbeta and dw2 (C), db2 (1).  Same refusals, workspace and ticket.  Two launches.
  * ggad_aegis_loss_fwd_f32: loss_g = mean_{i<n} -max(log1p(-p_i), -100) (BCE against 0) and loss_ae = mean_k ||x_r - zd_r||, r =
  *   rows[k] (x: n x F, zd: row stride ldz >= F); attr[k] = ||x_r - zd_r|| is kept for the backward.  One launch; ws =
- *   ggad_aegis_loss_workspace_elems(n, n_rows); ticket as above.
+ *   ggad_aegis_loss_workspace_elems(n, n_rows); ticket as above (TICKET WORDS).
  * ggad_aegis_loss_bwd_f32: dp[i] = *gloss_g p_i / max(p_i (1 - p_i), 1e-12) / n (dp may be NULL) and dzd (n x ldz, every element
  *   written: *gloss_ae (zd - x) / (n_rows attr) on the listed rows (pos[i] = position in rows or -1) below column F, 0 elsewhere;
  *   dzd may be NULL).  One launch. */
@@ -316,10 +320,10 @@ int ggad_gaan_edge_bwd_f32(const float *emb, int64_t n, int32_t C, const int32_t
  * ggad_dominant_ae_f32: one launch: loss[0] = mean of e over the train rows, score[k] = e of test row k, and the gradients at
  *   d loss = 1 (dW1 H x F, dB1 H, dW2 F x H, dB2 F; every element written).  Only the listed rows are evaluated.  (F, H) outside
  *   ggad_dominant_ae_supported -> GGAD_E_UNSUPPORTED, nothing launched.  ws = ggad_dominant_ae_workspace_elems(m, t_rows, F, H)
- *   floats; tickets = ggad_dominant_tickets() int32, zero, left zero.  Fixed-order sums, no float atomics.
+ *   floats; tickets = ggad_dominant_tickets() int32 (TICKET WORDS above).  Fixed-order sums, no float atomics.
  * ggad_dominant_recon_f32: one launch from a computed x_ (xh, N x F): loss[0], score as above and dxh (N x F, every element
  *   written) = (xh - x) / (e m) on the train rows (pos[i] = position of node i in the train list, -1 off it), 0 elsewhere.
- *   ws = ggad_dominant_recon_workspace_elems(n, m, t_rows) floats; ticket = one zeroed int32, left zero.
+ *   ws = ggad_dominant_recon_workspace_elems(n, m, t_rows) floats; ticket = one int32 (TICKET WORDS above).
  * ggad_dominant_scale_f32: dst[i] = src[i] * g[0] for i < n (g in device memory).  One launch. */
 int32_t ggad_dominant_ae_supported(int32_t F, int32_t H);
 int32_t ggad_dominant_tickets(void);
@@ -606,8 +610,8 @@ int ggad_prelu_bwd_ld_f32(const float *g, const float *z, const float *prelu_a, 
                           float *da, float *workspace, ggad_stream_t stream);
 /* The same in ONE launch (ABI 10; autograd of `self.act(out)`, /root/reference/model.py:35): two levels of tickets -- the last workgroup
  * of every group of four adds the group's partial column sums, the last group reduces the group rows -- every sum in a fixed order.
- * `workspace`: ggad_prelu_bwd_one_workspace_elems(M, W) floats; `ticket`: ggad_prelu_bwd_one_tickets() int32 in device memory, zero
- * before the first call, left zero, not shared between launches that may run concurrently.  Shapes the vector kernel does not take run
+ * `workspace`: ggad_prelu_bwd_one_workspace_elems(M, W) floats; `ticket`: ggad_prelu_bwd_one_tickets() int32 in device memory (TICKET
+ * WORDS at ggad_aegis_bn_fwd_f32: zero before the first call, left zero, shared only by stream-ordered launches).  Shapes the vector kernel does not take run
  * the two launches. */
 int64_t ggad_prelu_bwd_one_workspace_elems(int32_t M, int32_t W);
 int32_t ggad_prelu_bwd_one_tickets(void);
@@ -795,7 +799,7 @@ int ggad_full_loss_bwd_scale_f32(const float *g_total, const float *g_aff, const
  * margin, recon, the four loss values and the coefficients (replaces ggad_rowdot_f32 + ggad_full_loss_f32: four launches);
  * backward: c, d logits, xc = c e_hat[J], d emb_con = g (con - abn) kcol, d emb_abnormal = -that (replaces ggad_full_loss_bwd_scale_f32 +
  * ggad_rows_scale_f32);  ggad_rownorm_bwd_add_f32 = ggad_rownorm_bwd_f32 with dXn[r] += c[q] S[q] for r = J[q] folded in (pos_n / pos_a:
- * position of row r in the normal / abnormal segment of J, or -1).  `ticket`: one int32, zero before the first call (left zero). */
+ * position of row r in the normal / abnormal segment of J, or -1).  `ticket`: one int32 (TICKET WORDS at ggad_aegis_bn_fwd_f32). */
 int64_t ggad_full_loss_fused_workspace_elems(int32_t n_out, int32_t H);
 int ggad_full_loss_fused_f32(const float *e_hat, const int32_t *J, const float *S, const float *r_inv_j, int32_t n_normal, int32_t n_out,
                              int32_t H, const float *logits, const float *emb_con, const float *emb_abn, float margin, float *aff,

@@ -97,8 +97,9 @@ LOSS_CASES["zero_difference_column"] = _loss(3000, 300, 700, 90, seed=18, zero_c
 
 
 def loss_case(name):
-    """Inputs of one `GgadLossFn` case: adjacency (scipy), float32 operands, index lists, and what the case expects."""
-    p = LOSS_CASES[name]
+    """Inputs of one `GgadLossFn` case (a name of LOSS_CASES, or the parameters of a case of the caller's own as `_loss` returns
+    them): adjacency (scipy), float32 operands, index lists, and what the case expects."""
+    p = LOSS_CASES[name] if isinstance(name, str) else name
     n, h, nn, na = p["n"], p["h"], p["nn"], p["na"]
     rng = np.random.default_rng(1000 + p["seed"])
     a = _graph(n, p["deg"], p["seed"])

@@ -145,3 +145,25 @@ def test_prepare_normalises_only_the_listed_datasets(dataset, normalised):
     assert full.n == n
     assert abs(full.A.host - (normalize_adj(adj) + sp.eye(n)).tocsr()).max() == 0
     assert abs(full.raw_host - (adj + sp.eye(n)).tocsr()).max() == 0
+
+
+# ------------------------------------------------------------------------------------------------ the ticket block
+def test_ticket_block_refuses_to_allocate_inside_a_capture(monkeypatch):
+    """`fullgraph.ticket_block` with nothing cached and a capture under way raises before it touches the device (here there is no
+    such device: reaching it would raise another error); built eagerly first -- what `FullGraphAdj.__init__` does -- the same call
+    inside the capture returns the block that exists."""
+    from ggad_amd import fullgraph as FG
+    monkeypatch.setattr(FG, "_TICKET_BLOCKS", {})
+    monkeypatch.setattr(FG, "_capturing", lambda dev: True)
+    with pytest.raises(RuntimeError, match="inside a stream capture"):
+        FG.ticket_block("cuda:7")
+    assert FG._TICKET_BLOCKS == {}
+    monkeypatch.setattr(FG, "_capturing", lambda dev: False)
+    a = sp.eye(5, format="csr")
+    FG.FullGraphAdj(a, a, "cpu")
+    block = FG._TICKET_BLOCKS["cpu"]
+    assert block.dtype == torch.int32 and block.numel() % 4 == 0 and not block.any()
+    lib = FG._lib.load()
+    assert block.numel() >= max(int(lib.ggad_prelu_bwd_one_tickets()), int(lib.ggad_dominant_tickets()), 1)
+    monkeypatch.setattr(FG, "_capturing", lambda dev: True)
+    assert FG.ticket_block("cpu").data_ptr() == block.data_ptr()
