@@ -1,10 +1,11 @@
 """Host-side sparse structures of the full-graph path: the device CSR (`Csr`) and the launch plans of its SpMM kernels.
 
-A plan is a set of integer tables built once per matrix on the host and cached: segment tables (`plan`, `rowslice_plan`) for the
-CSR / sliced / row-slice kernels, and the entry streams of the LDS-panel and LDS-ring products (`panel_plan`, `ring_plan`; kernels
+A plan is a set of integer tables built once per matrix on the host and cached: segment tables (`plan`, `sliced_plan`,
+`rowslice_plan`; the last two hang on the `plan` whose rows they cover, the sliced one per column-range count) for the CSR /
+sliced / row-slice kernels, and the entry streams of the LDS-panel and LDS-ring products (`panel_plan`, `ring_plan`; kernels
 k_spmm_panel / k_spmm_ring in csrc/fullgraph.hip, fill loops in csrc/spmm_panel_build.cpp / csrc/spmm_ring_build.cpp).  The two
 stream plans share their round layout, the dealing of rounds to waves and the XCD workgroup table (`_round_layout`, `_deal_rounds`,
-`_xcd_workgroup_table`); `fullgraph.py` chooses and launches the kernels.
+`_xcd_workgroup_table`); `fullgraph.spmm_route` chooses the kernel of a product and `fullgraph.spmm` launches it.
 """
 from __future__ import annotations
 
@@ -267,10 +268,22 @@ class Csr:
         p = dict(seg_beg=_dev_i32(sbeg, dev), seg_end=_dev_i32(send, dev), seg_out=_dev_i32(seg_out, dev), n_seg=total,
                  multi_row=_dev_i32(multi, dev), multi_first=_dev_i32(first[multi], dev), multi_count=_dev_i32(nseg[multi], dev),
                  n_multi=int(len(multi)), n_out=int(len(rows)), part=None, nnz=int((end - beg).sum()),
-                 rows=None if rows_sel is None else rows, long=None)
+                 rows=None if rows_sel is None else rows)
         if key is not None:
             self._plans[key] = p
         return p
+
+    def sliced_plan(self, p):
+        """The rows of segment plan `p` in the long segments the sliced kernel walks (8 index loads, one reduction and store per
+        wave), cut into GGAD_SPMM_COL_RANGES column ranges (default 1).  Cached on the plan, per range count."""
+        # (more than one range launches range by range so that one phase's operand rows fit an L2 -- measured slower, 1.35 -> 1.67 ms
+        # with 2 ranges on T-Finance: the sliced kernel is bound by the L1 line rate, not by L2 capacity, and shorter segments cost
+        # more prologues; kept for experiments)
+        ranges = max(1, int(os.environ.get("GGAD_SPMM_COL_RANGES", 1)))
+        long = p.setdefault("long", {})
+        if ranges not in long:
+            long[ranges] = self.plan(p["rows"], key=None, seg=int(_lib.load().ggad_spmm_sliced_seg_len()), col_ranges=ranges)
+        return long[ranges]
 
     def rowslice_plan(self, p, lines: bool = False):
         """Units of the column-sliced kernel for sparse neighbourhoods (k_spmm_rowslice) for the rows of segment plan `p` (whole

@@ -14,7 +14,7 @@ The reference keeps `adj` and `raw_adj` as dense (1,N,N) tensors and multiplies 
 from __future__ import annotations
 
 import os
-
+from collections import namedtuple
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -192,6 +192,7 @@ def gemm(A: torch.Tensor, B: torch.Tensor, trans_a: bool, trans_b: bool, bias=No
 
 
 _XS_WORKSPACE = {}
+Route = namedtuple("Route", "kind tables")          # what `spmm_route` returns: "rowline" / "ring" / "panel" / "sliced" / "rowslice" / "seg" + its plan
 
 
 def _use_sliced(csr: Csr, p, X: torch.Tensor) -> bool:
@@ -231,47 +232,62 @@ def padded_rows(n_rows: int, W: int, dev, consumer=None):
     is one of the sparse-neighbourhood products (what `_use_rowslice` selects: Reddit, Photo), its rows start on 128-byte lines
     (a view of a matrix with the row stride rounded up to 32 floats; the padding columns are never read) and `spmm` then runs the
     line-granular kernel; a plain contiguous matrix otherwise.  GGAD_SPMM_ROWLINE=0: always contiguous."""
+    plain = torch.empty(n_rows, W, dtype=torch.float32, device=dev)
     ld = (W + 31) // 32 * 32
     if consumer is not None and ld != W and os.environ.get("GGAD_SPMM_ROWLINE", "1") != "0":
         csr, p = consumer
         p = p if p is not None else csr.plan()
         X = torch.empty(n_rows, ld, dtype=torch.float32, device=dev)[:, :W]
-        if csr.nnz > 0 and _use_rowline(X) and _use_panel(csr, p, X) is None and not _use_sliced(csr, p, X) and _use_rowslice(csr, p, X):
+        if spmm_route(csr, p, X).kind == "rowline" and spmm_route(csr, p, plain).kind == "rowslice":      # (only where padding swaps the two)
             return X
-    return torch.empty(n_rows, W, dtype=torch.float32, device=dev)
+    return plain
 
 
-def _use_panel(csr: Csr, p, X: torch.Tensor):
-    """Products with dense neighbourhoods and factoring values (whole matrix, or a row subset of a matrix without separate
-    diagonal): the LDS-panel kernel (k_spmm_panel).  Returns its plan or None.  GGAD_SPMM_PANEL=0 turns it off, =1 forces it wherever a plan can be built."""
+def _panel_eligible(csr: Csr, p, X: torch.Tensor) -> bool:
+    """Products with dense neighbourhoods: candidates for the LDS kernels (k_spmm_ring, k_spmm_panel), which `spmm_route` takes where
+    the device has the LDS and a plan can be built.  GGAD_SPMM_PANEL=0 turns them off, =1 forces them wherever a plan can be built."""
     force = os.environ.get("GGAD_SPMM_PANEL")
     if force == "0" or X.shape[0] != csr.shape[1]:
-        return None
-    with torch.cuda.device(X.device):
-        if not _lib.load().ggad_spmm_panel_available():          # a device without 159 KB of LDS per workgroup: the sliced kernel
-            return None
-    w = X.shape[1]
+        return False
     nnz = p.get("nnz", csr.nnz)
     # (the floors were 2^20 entries and 64 per output row: the products over Amazon's loss rows -- 1,751 rows x 368 entries, and their transpose
     #  with 54 entries per row -- then took the sliced / segment kernels at ~80 ps per entry: epoch 0.725 against 0.694-0.698 ms with the ring,
     #  scripts/panel_threshold_ab.sh; sparse neighbourhoods (Reddit, Photo: 16 per row) fail the per-row test and keep their kernels)
     min_nnz = int(os.environ.get("GGAD_SPMM_PANEL_MIN_NNZ", str(1 << 18)))
     min_row = int(os.environ.get("GGAD_SPMM_PANEL_MIN_ROW", "32"))
-    if force != "1" and not (w >= 64 and nnz >= min_row * p["n_out"] and nnz >= min_nnz):
-        return None
-    ring = os.environ.get("GGAD_SPMM_RING", "1") != "0" and bool(_lib.load().ggad_spmm_ring_available())
-    # the LDS ring (k_spmm_ring) unless it is turned off or its plan does not qualify (fill, rounds, stream size): then the panels
-    for build in ((Csr.ring_plan, Csr.panel_plan) if ring else (Csr.panel_plan,)):
-        if p.get("rows") is not None:                                     # row subset: the plan lives on the segment plan
-            plan = build(csr, (w // 4 + 7) // 8, p["rows"], p.setdefault("panel_cache", {}))
-        else:
-            plan = build(csr, (w // 4 + 7) // 8)
-        if plan is not None:
-            return plan
-    return None
+    return force == "1" or (X.shape[1] >= 64 and nnz >= min_row * p["n_out"] and nnz >= min_nnz)
 
 
-def _xs_workspace(X: torch.Tensor, n_ws: int) -> torch.Tensor:
+def _lds_kernels(dev) -> Tuple[bool, bool]:
+    """(panel, ring): whether `dev` gives a workgroup the LDS of k_spmm_panel (159 KB) / of k_spmm_ring."""
+    with torch.cuda.device(dev):
+        return bool(_lib.load().ggad_spmm_panel_available()), bool(_lib.load().ggad_spmm_ring_available())
+
+
+def spmm_route(csr: Csr, p, X: torch.Tensor) -> Route:
+    """(kind, tables): the kernel `spmm` runs for the rows `p` (a `csr.plan`) of `csr` times `X`, and the plan its launcher takes.
+    The ONLY place that holds the precedence (top to bottom).  The switches are read on every call: nothing is cached
+    but the plans.  A ring / panel plan that does not qualify (values that do not factor, fill, rounds, stream size) is None."""
+    w = X.shape[1]
+    if X.dim() == 2 and X.stride(1) == 1 and X.stride(0) > w and csr.nnz > 0 and _use_rowline(X):
+        return Route("rowline", csr.rowslice_plan(p, lines=True))
+    if _panel_eligible(csr, p, X):
+        panel, ring = _lds_kernels(X.device)          # (without the panel's 159 KB of LDS per workgroup: the sliced kernel)
+        kinds = ("ring", "panel") if ring and os.environ.get("GGAD_SPMM_RING", "1") != "0" else ("panel",)
+        cache = None if p.get("rows") is None else p.setdefault("panel_cache", {})     # row subset: the plan lives on the segment plan
+        for kind in kinds if panel else ():
+            plan = (Csr.ring_plan if kind == "ring" else Csr.panel_plan)(csr, (w // 4 + 7) // 8, p.get("rows"), cache)
+            if plan is not None:
+                return Route(kind, plan)
+    if _use_sliced(csr, p, X):
+        return Route("sliced", csr.sliced_plan(p))
+    if _use_rowslice(csr, p, X):
+        return Route("rowslice", csr.rowslice_plan(p))
+    return Route("seg", p)
+
+
+def _xs_workspace(X: torch.Tensor) -> torch.Tensor:
+    n_ws = int(_lib.load().ggad_spmm_sliced_workspace_elems(X.shape[0], X.shape[1]))
     key = (str(X.device), torch.cuda.current_stream(X.device).cuda_stream)
     xs = _XS_WORKSPACE.get(key)
     if xs is None or xs.numel() < n_ws:          # one staging buffer per stream: consumed by the launch that follows its fill
@@ -280,21 +296,40 @@ def _xs_workspace(X: torch.Tensor, n_ws: int) -> torch.Tensor:
 
 
 def _part_buffer(p, W: int, dev):
-    """Partial sums of the rows that are split into several segments (cached on the plan)."""
-    if p["n_multi"] == 0:
-        return None
+    """Partial sums of the rows that are split into several segments (cached on the plan); None when no row is."""
     part = p.get("part")
-    if part is None or part.numel() < p["n_seg"] * W:
+    if p["n_multi"] > 0 and (part is None or part.numel() < p["n_seg"] * W):
         part = p["part"] = torch.empty(p["n_seg"] * W, dtype=torch.float32, device=dev)
     return part
+
+
+# One launcher per kind of `spmm_route`, called as (csr, the route's tables, X, W, opt): nothing but that kernel's arguments.
+_LAUNCH = {
+    "rowline": lambda csr, rs, X, W, opt: call(
+        "ggad_spmm_rowline_f32", ptr(csr.entries()), ptr(rs["unit_tab"]), rs["n_units"], ptr(rs["long_tab"]), rs["n_long"],
+        ptr(rs["hub_tab"]), rs["n_hub"], ptr_rows(X), X.stride(0), W, X.shape[0], *opt),
+    "ring": lambda csr, pp, X, W, opt: call(
+        "ggad_spmm_ring_f32", ptr(pp["wg"]), pp["n_wg"], ptr(pp["wave_sb"]), ptr(pp["idx"]), ptr(pp["ctl"]), ptr(pp["row_tab"]), pp["n_phases"],
+        pp["walkers"], ptr(pp["cs"]), ptr(pp["rs"]), ptr(pp["diag"]), ptr(X), W, W, X.shape[0], ptr(_xs_workspace(X)), *opt),
+    "panel": lambda csr, pp, X, W, opt: call(
+        "ggad_spmm_panel_f32", ptr(pp["wg"]), pp["n_wg"], ptr(pp["dir"]), ptr(pp["stream"]), ptr(pp["row_tab"]), pp["n_chunks"],
+        ptr(pp["cs"]), ptr(pp["rs"]), ptr(pp["diag"]), ptr(X), W, W, X.shape[0], ptr(_xs_workspace(X)), *opt),
+    "sliced": lambda csr, p, X, W, opt: call(
+        "ggad_spmm_sliced_f32", ptr(csr.col), ptr(csr.val), ptr(p["seg_beg"]), ptr(p["seg_end"]), ptr(p["seg_out"]), p["n_seg"],
+        ptr(p["multi_row"]), ptr(p["multi_first"]), ptr(p["multi_count"]), p["n_multi"], ptr(X), W, W, X.shape[0], ptr(_xs_workspace(X)),
+        *opt, ptr(_part_buffer(p, W, X.device))),
+    "rowslice": lambda csr, rs, X, W, opt: call(
+        "ggad_spmm_rowslice_f32", ptr(csr.rowptr), ptr(csr.col), ptr(csr.val), ptr(rs["unit_rows"]), ptr(rs["unit_out"]), rs["n_units"],
+        ptr(rs["long_rows"]), ptr(rs["long_out"]), rs["n_long"], ptr(rs["hub_rows"]), ptr(rs["hub_out"]), rs["n_hub"], ptr(X), W, W, *opt),
+    "seg": lambda csr, p, X, W, opt: call(
+        "ggad_spmm_csr_f32", ptr(csr.col), ptr(csr.val), ptr(p["seg_beg"]), ptr(p["seg_end"]), ptr(p["seg_out"]), p["n_seg"],
+        ptr(p["multi_row"]), ptr(p["multi_first"]), ptr(p["multi_count"]), p["n_multi"], ptr(X), W, W, *opt, ptr(_part_buffer(p, W, X.device))),
+}
 
 
 def spmm(csr: Csr, X: torch.Tensor, plan=None, bias=None, prelu_a=None, want_pre=False, out=None):
     """out = act(csr[rows] @ X + bias); `plan` = csr.plan(...) selects the rows (default: all).  `out`: destination (and shape of
     the pre-activation copy) with unit column stride; its row stride may exceed W."""
-    strided = X.dim() == 2 and X.stride(1) == 1 and X.stride(0) > X.shape[1] and csr.nnz > 0 and _use_rowline(X)     # padded rows: see padded_rows()
-    if not strided:
-        X = X.contiguous()
     W = X.shape[1]
     p = plan if plan is not None else csr.plan()
     if out is None:
@@ -302,44 +337,9 @@ def spmm(csr: Csr, X: torch.Tensor, plan=None, bias=None, prelu_a=None, want_pre
     elif tuple(out.shape) != (p["n_out"], W) or out.dtype != torch.float32:
         raise ValueError("spmm: out must be (rows, W) fp32")
     pre = torch.empty_strided(out.shape, out.stride(), dtype=torch.float32, device=X.device) if want_pre else None
-    opt = (ptr(bias) if bias is not None else 0, ptr(prelu_a) if prelu_a is not None else 0, ptr_rows(out), out.stride(0),
-           ptr_rows(pre) if pre is not None else 0)
-    pp = None if strided else _use_panel(csr, p, X)
-    if strided:
-        rs = csr.rowslice_plan(p, lines=True)
-        call("ggad_spmm_rowline_f32", ptr(csr.entries()), ptr(rs["unit_tab"]), rs["n_units"], ptr(rs["long_tab"]), rs["n_long"],
-             ptr(rs["hub_tab"]), rs["n_hub"], ptr_rows(X), X.stride(0), W, X.shape[0], *opt)
-    elif pp is not None:
-        xs = _xs_workspace(X, int(_lib.load().ggad_spmm_sliced_workspace_elems(X.shape[0], W)))
-        opt_p = lambda t: ptr(t) if t is not None else 0
-        if "wave_sb" in pp:
-            call("ggad_spmm_ring_f32", ptr(pp["wg"]), pp["n_wg"], ptr(pp["wave_sb"]), ptr(pp["idx"]), ptr(pp["ctl"]), ptr(pp["row_tab"]),
-                 pp["n_phases"], pp["walkers"], opt_p(pp["cs"]), opt_p(pp["rs"]), opt_p(pp["diag"]), ptr(X), W, W, X.shape[0], ptr(xs), *opt)
-        else:
-            call("ggad_spmm_panel_f32", ptr(pp["wg"]), pp["n_wg"], ptr(pp["dir"]), ptr(pp["stream"]), ptr(pp["row_tab"]), pp["n_chunks"],
-                 opt_p(pp["cs"]), opt_p(pp["rs"]), opt_p(pp["diag"]), ptr(X), W, W, X.shape[0], ptr(xs), *opt)
-    elif _use_sliced(csr, p, X):
-        if p["long"] is None:      # the sliced kernel walks long segments (8 index loads, one reduction and store per wave)
-            # (GGAD_SPMM_COL_RANGES > 1 cuts them at column-range boundaries and launches range by range so that one phase's
-            # operand rows fit an L2 -- measured slower, 1.35 -> 1.67 ms with 2 ranges on T-Finance: the sliced kernel is bound
-            # by the L1 line rate, not by L2 capacity, and shorter segments cost more prologues; kept for experiments)
-            ranges = max(1, int(os.environ.get("GGAD_SPMM_COL_RANGES", 1)))
-            p["long"] = csr.plan(p["rows"], key=None, seg=int(_lib.load().ggad_spmm_sliced_seg_len()), col_ranges=ranges)
-        p = p["long"]
-        part = _part_buffer(p, W, X.device)
-        xs = _xs_workspace(X, int(_lib.load().ggad_spmm_sliced_workspace_elems(X.shape[0], W)))
-        call("ggad_spmm_sliced_f32", ptr(csr.col), ptr(csr.val), ptr(p["seg_beg"]), ptr(p["seg_end"]), ptr(p["seg_out"]),
-             p["n_seg"], ptr(p["multi_row"]), ptr(p["multi_first"]), ptr(p["multi_count"]), p["n_multi"], ptr(X), W, W, X.shape[0],
-             ptr(xs), *opt, ptr(part) if part is not None else 0)
-    elif _use_rowslice(csr, p, X):
-        rs = csr.rowslice_plan(p)
-        call("ggad_spmm_rowslice_f32", ptr(csr.rowptr), ptr(csr.col), ptr(csr.val), ptr(rs["unit_rows"]), ptr(rs["unit_out"]), rs["n_units"],
-             ptr(rs["long_rows"]), ptr(rs["long_out"]), rs["n_long"], ptr(rs["hub_rows"]), ptr(rs["hub_out"]), rs["n_hub"], ptr(X), W, W, *opt)
-    else:
-        part = _part_buffer(p, W, X.device)
-        call("ggad_spmm_csr_f32", ptr(csr.col), ptr(csr.val), ptr(p["seg_beg"]), ptr(p["seg_end"]), ptr(p["seg_out"]), p["n_seg"],
-             ptr(p["multi_row"]), ptr(p["multi_first"]), ptr(p["multi_count"]), p["n_multi"], ptr(X), W, W, *opt,
-             ptr(part) if part is not None else 0)
+    opt = (ptr(bias), ptr(prelu_a), ptr_rows(out), out.stride(0), ptr_rows(pre) if pre is not None else 0)
+    kind, tables = spmm_route(csr, p, X)
+    _LAUNCH[kind](csr, tables, X if kind == "rowline" else X.contiguous(), W, opt)      # (padded rows: see padded_rows())
     return (out, pre) if want_pre else out
 
 

@@ -179,11 +179,10 @@ def bench_one(name: str, dev, epochs: int = 30, seed: int = 0, h: int = 300) -> 
     xa.copy_(x)                                                        # on the sparse configs: the line-granular product)
     t_spmm = _time_call(lambda: FG.spmm(full.A, xa))
     plan0 = full.A.plan()
-    pp0 = FG._use_panel(full.A, plan0, x)
-    kernel = (("k_spmm_ring" if "wave_sb" in pp0 else "k_spmm_panel") if pp0 is not None
-              else "k_spmm_sliced" if FG._use_sliced(full.A, plan0, x)
-              else "k_spmm_rowline" if not xa.is_contiguous()
-              else "k_spmm_rowslice" if FG._use_rowslice(full.A, plan0, x) else "k_spmm_seg")
+    route = FG.spmm_route(full.A, plan0, xa)                           # what the timed call above launched
+    kernel = {"rowline": "k_spmm_rowline", "ring": "k_spmm_ring", "panel": "k_spmm_panel", "sliced": "k_spmm_sliced",
+              "rowslice": "k_spmm_rowslice", "seg": "k_spmm_seg"}[route.kind]
+    pp0 = route.tables if route.kind in ("ring", "panel") else None
     t_gemm = _time_call(lambda: FG.gemm(x, w, False, True))
     spmm_bytes = 8.0 * nnz + 4.0 * (n + 1) + 8.0 * n * h
     spmm_flops = 2.0 * nnz * h

@@ -25,7 +25,8 @@ for name in (sys.argv[1:] or ["Amazon", "t_finance"]):
     for label, env in (("panel", {"GGAD_SPMM_RING": "0"}), ("ring/slice", {"GGAD_SPMM_RING": "1", "GGAD_RING_XCD": "slice"}),
                        ("ring/block", {"GGAD_SPMM_RING": "1", "GGAD_RING_XCD": "block"})):
         os.environ.update(env)
-        pp = FG._use_panel(csr, csr.plan(), x)
+        kind, pp = FG.spmm_route(csr, csr.plan(), x)
+        assert kind == label.split("/")[0], (label, kind)
         out = FG.spmm(csr, x)
         torch.cuda.synchronize()
         again = FG.spmm(csr, x)

@@ -27,7 +27,7 @@ n = mat.shape[0]
 csr = FG.Csr(mat, dev)
 x = torch.from_numpy(np.random.default_rng(1).standard_normal((n, 300)).astype(np.float32)).to(dev)
 t0 = time.time()
-pp = FG._use_panel(csr, csr.plan(), x)
+kind, pp = FG.spmm_route(csr, csr.plan(), x)
 t_plan = time.time() - t0
 t = FB._time_call(lambda: FG.spmm(csr, x), reps=30)
-print(f"{name} {label}: {t * 1e6:.1f} us per product incl. re-layout; plan {t_plan:.2f} s fill {pp['fill']:.3f} skew {pp.get('phase_skew', 0):.3f}", flush=True)
+print(f"{name} {label}: {kind} {t * 1e6:.1f} us per product incl. re-layout; plan {t_plan:.2f} s fill {pp['fill']:.3f} skew {pp.get('phase_skew', 0):.3f}", flush=True)

@@ -35,8 +35,8 @@ for name in (sys.argv[1:] or ["reddit", "photo"]):
         print(f"{name:8s} {tag:7s}: {t * 1e6:7.1f} us  ({floor_us / (t * 1e6):.3f} of the 8 TB/s floor {floor_us:.2f} us)", flush=True)
     xp = torch.empty(n, 320, device=dev)[:, :300]
     xp.copy_(x)
-    assert FG._use_rowline(xp)
-    rsp = full.A.rowslice_plan(full.A.plan(), lines=True)
+    kind, rsp = FG.spmm_route(full.A, full.A.plan(), xp)
+    assert kind == "rowline"
     print(name, "rowline plan: units", rsp["n_units"], "medium", rsp["n_long"], "hub", rsp["n_hub"], flush=True)
     res["rowline"] = FG.spmm(full.A, xp).clone()
     t = _time_call(lambda: FG.spmm(full.A, xp), 50)

@@ -29,8 +29,8 @@ for name in (sys.argv[1:] or ["t_finance"]):
             os.environ.pop("GGAD_SPMM_PANEL", None)
         else:
             os.environ["GGAD_SPMM_PANEL"] = mode
-        pp = FG._use_panel(full.Rt, plan, x)
+        kind = FG.spmm_route(full.Rt, plan, x).kind
         out = FG.spmm(full.Rt, x, plan=plan)
         t = _time_call(lambda: FG.spmm(full.Rt, x, plan=plan), 30)
-        print(name, "rows %d entries %d: %s %.1f us  checksum %.6e" % (len(J), plan["nnz"], "panel " if pp is not None else "sliced", t * 1e6,
-                                                                      float(out.double().sum())), flush=True)
+        print(name, "rows %d entries %d: %-6s %.1f us  checksum %.6e" % (len(J), plan["nnz"], kind, t * 1e6,
+                                                                        float(out.double().sum())), flush=True)

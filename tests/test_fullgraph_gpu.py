@@ -354,14 +354,13 @@ def test_spmm_sliced_column_ranges_and_empty_rows(monkeypatch):
     monkeypatch.setenv("GGAD_SPMM_SLICED", "1")
     for ranges in ("1", "3", "7"):
         monkeypatch.setenv("GGAD_SPMM_COL_RANGES", ranges)
-        for p in (csr.plan(), csr.plan(rows, key=("cr", ranges))):
-            p["long"] = None
         got = FG.spmm(csr, x).cpu().numpy()
         assert np.abs(got - ref).max() / scale < 2e-6, ranges
         assert (got[[7, 8, n - 1]] == 0).all()
         sub = FG.spmm(csr, x, plan=csr.plan(rows, key=("cr", ranges))).cpu().numpy()
         assert np.abs(sub - ref[rows]).max() / scale < 2e-6, ranges
-    lp = csr.plan()["long"]
+    kind, lp = FG.spmm_route(csr, csr.plan(), x)                  # (the switch still at 7 ranges: the plan of that range count)
+    assert kind == "sliced" and lp is csr.plan()["long"][7] and sorted(csr.plan()["long"]) == [1, 3, 7]
     assert lp["n_multi"] > 0 and int((lp["seg_out"] < 0).sum().item()) > 5
 
 
@@ -582,7 +581,7 @@ def test_spmm_lds_panel_equals_row_major(w, ring, monkeypatch):
         monkeypatch.setenv("GGAD_SPMM_SLICED", "0")
         o0, pre0 = FG.spmm(csr, x, bias=bias, prelu_a=slope, want_pre=True)
         monkeypatch.setenv("GGAD_SPMM_PANEL", "1")
-        assert ("wave_sb" in FG._use_panel(csr, csr.plan(), x)) == (ring == "1")
+        assert FG.spmm_route(csr, csr.plan(), x).kind == ("ring" if ring == "1" else "panel")
         o1, pre1 = FG.spmm(csr, x, bias=bias, prelu_a=slope, want_pre=True)
         o2 = FG.spmm(csr, x, bias=bias, prelu_a=slope)
         ref = csr.host.astype(np.float64) @ x.cpu().numpy().astype(np.float64) + bias.cpu().numpy().astype(np.float64)
@@ -592,13 +591,13 @@ def test_spmm_lds_panel_equals_row_major(w, ring, monkeypatch):
         assert torch.equal(o1.view(torch.int32), o2.view(torch.int32))
         rows = np.concatenate((rng.permutation(n)[:100], [5, 5]))               # a row subset (one row twice): panels when the
         sp_plan = csr.plan(rows, key=("p", w))                                 # matrix has no separate diagonal, else segments
-        assert (FG._use_panel(csr, sp_plan, x) is None) == (csr.value_factors()[2] is not None)
+        assert (FG.spmm_route(csr, sp_plan, x).kind not in ("ring", "panel")) == (csr.value_factors()[2] is not None)
         sub = FG.spmm(csr, x, plan=sp_plan, bias=bias).cpu().numpy()
         assert np.abs(sub - ref[rows]).max() / scale < 2e-6
     weighted = (U.normalize_adj(a) + sp.eye(n)).tocsr()
     weighted.data = weighted.data * rng.uniform(0.5, 1.5, size=weighted.nnz)
     csr = FG.Csr(weighted, DEV)
-    assert FG._use_panel(csr, csr.plan(), x) is None
+    assert FG.spmm_route(csr, csr.plan(), x).kind not in ("ring", "panel")
 
 
 @pytest.mark.parametrize("ring", ["1", "0"])
@@ -614,10 +613,52 @@ def test_spmm_lds_panel_single_partial_panel_and_rectangular(ring, monkeypatch):
         a.data[:] = 1.0
         csr = FG.Csr(a, DEV)
         x = torch.from_numpy(rng.standard_normal((n_src, 300)).astype(np.float32)).to(DEV)
-        assert FG._use_panel(csr, csr.plan(), x) is not None
+        assert FG.spmm_route(csr, csr.plan(), x).kind in ("ring", "panel")
         got = FG.spmm(csr, x).cpu().numpy()
         ref = a.astype(np.float64) @ x.cpu().numpy().astype(np.float64)
         assert np.abs(got - ref).max() / (np.abs(ref).max() + 1.0) < 2e-6, (n_rows, n_src)
+
+
+_SPMM_ENTRY = {"rowline": "ggad_spmm_rowline_f32", "ring": "ggad_spmm_ring_f32", "panel": "ggad_spmm_panel_f32",
+               "sliced": "ggad_spmm_sliced_f32", "rowslice": "ggad_spmm_rowslice_f32", "seg": "ggad_spmm_csr_f32"}
+
+
+@pytest.mark.parametrize("kind,w,env", [("seg", 28, {}), ("rowslice", 160, {}), ("rowline", 300, {}),
+                                        ("sliced", 64, {"GGAD_SPMM_SLICED": "1", "GGAD_SPMM_PANEL": "0"}),
+                                        ("panel", 64, {"GGAD_SPMM_PANEL": "1", "GGAD_SPMM_RING": "0"}),
+                                        ("ring", 64, {"GGAD_SPMM_PANEL": "1", "GGAD_SPMM_RING": "1"})])
+def test_spmm_launches_the_kernel_its_route_names(kind, w, env, monkeypatch):
+    """`spmm` launches the ONE entry point that `spmm_route` names, for each of the six kinds at the smallest shape that reaches its
+    launcher (one row longer than a segment of either segment kernel: partial sums and the hub table are marshalled too), with
+    bias + PReLU + pre-activation; the pre-activation against scipy in float64."""
+    import scipy.sparse as sp
+    rng = np.random.default_rng(len(kind) + w)
+    if kind in ("ring", "panel"):
+        a = sp.random(900, 900, density=0.2, random_state=7, format="csr", dtype=np.float32)
+        a.data[:] = 1.0
+    else:
+        n = 300 if kind == "seg" else 600
+        a = sp.random(n, n, density=8.0 / n, random_state=7, format="lil", dtype=np.float32)
+        a[5, :] = rng.standard_normal(n).astype(np.float32)
+        a = a.tocsr()
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    csr = FG.Csr(a, DEV)
+    xh = rng.standard_normal((a.shape[1], w)).astype(np.float32)
+    x = FG.padded_rows(a.shape[1], w, DEV, (csr, None))                 # (padded at w = 300 only: the producer's side of "rowline")
+    x.copy_(torch.from_numpy(xh))
+    assert x.is_contiguous() == (kind != "rowline")
+    bias = torch.from_numpy(rng.standard_normal(w).astype(np.float32)).to(DEV)
+    slope = torch.tensor([0.25], device=DEV)
+    assert FG.spmm_route(csr, csr.plan(), x).kind == kind
+    launched, real = [], FG.call
+    monkeypatch.setattr(FG, "call", lambda name, *args: (launched.append(name), real(name, *args))[1])
+    out, pre = FG.spmm(csr, x, bias=bias, prelu_a=slope, want_pre=True)
+    assert [name for name in launched if name.startswith("ggad_spmm_")] == [_SPMM_ENTRY[kind]]
+    ref = csr.host.astype(np.float64) @ xh.astype(np.float64) + bias.cpu().numpy().astype(np.float64)
+    scale = np.abs(ref).max() + 1.0
+    assert np.abs(pre.cpu().numpy() - ref).max() / scale < 2e-6
+    assert np.abs(out.cpu().numpy() - np.where(ref > 0, ref, 0.25 * ref)).max() / scale < 2e-6
 
 
 def test_spmm_at_t_finance_size_against_scipy_and_exact_scaling():
@@ -633,7 +674,7 @@ def test_spmm_at_t_finance_size_against_scipy_and_exact_scaling():
     rng = np.random.default_rng(1)
     xh = rng.standard_normal((n, w)).astype(np.float32)
     x = torch.from_numpy(xh).to(DEV)
-    assert FG._use_sliced(csr, csr.plan(), x) and FG._use_panel(csr, csr.plan(), x) is not None
+    assert FG._use_sliced(csr, csr.plan(), x) and FG.spmm_route(csr, csr.plan(), x).kind in ("ring", "panel")
     bias = torch.from_numpy(rng.standard_normal(w).astype(np.float32)).to(DEV)
     slope = torch.tensor([0.1], device=DEV)
     out, pre = FG.spmm(csr, x, bias=bias, prelu_a=slope, want_pre=True)
