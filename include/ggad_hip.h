@@ -11,6 +11,10 @@
  *   - plain pointers + sizes only; every pointer is a DEVICE pointer unless the name
  *     ends in _host; no ownership transfer: the caller (PyTorch allocator in the Python
  *     host layer) allocates every input, output and workspace;
+ *   - a workspace (`workspace`, `ws`, `scratch`, `part`, `xs_workspace`) carries nothing from call to call and may be larger than
+ *     the call needs.  The full-graph entry points state their contract at the parameter: "contents on entry are arbitrary" (any
+ *     bit pattern, NaN included; tests/test_dirty_memory_gpu.py and tests/test_handoff_gpu.py hold them to it) or the exact
+ *     requirement (ticket words and the TAM head's workspace: zero before the first call);
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*) and is
  *     asynchronous; functions are re-entrant per stream and keep no global mutable
  *     state: the only cross-call state is in buffers the caller passes (counter slots,
@@ -63,7 +67,7 @@ int ggad_mb_supported(int32_t D, int32_t F);
  * ---------------------------------------------------------------------------------- */
 
 /* out[0..n] = exclusive prefix sum of in[0..n-1] (out[n] = total).  n <= 4,194,304.
- * workspace: int32[ggad_scan_workspace_elems(n)]. */
+ * workspace: int32[ggad_scan_workspace_elems(n)]; contents on entry are arbitrary (tile sums and offsets: never addresses). */
 int64_t ggad_scan_workspace_elems(int64_t n);
 int ggad_exclusive_scan_i32(const int32_t *in, int32_t *out, int64_t n, int32_t *workspace, ggad_stream_t stream);
 
@@ -218,15 +222,17 @@ int ggad_ocgnn_loss_f32(const float *emb, const int64_t *idx, int64_t n_idx, int
  *   ggad_adae_gat_bwd_f32:   from g = d loss / d z: dals, dald (N each), dy (N x F); dpre = d loss / d pre-activation per edge,
  *                            float[nnz + N] (slot tptr[i] + i + k: entry k of target row i, the added self loop last); tmap[e] =
  *                            index in A_hat^T of entry e of A_hat (aptr / acol / aval).
- *   ggad_adae_colsum_f32:    out[f] = sum_r w[r] M[r, f] (w NULL: 1) in a fixed order; ws = ggad_adae_colsum_workspace_elems(F).
+ *   ggad_adae_colsum_f32:    out[f] = sum_r w[r] M[r, f] (w NULL: 1) in a fixed order; ws = ggad_adae_colsum_workspace_elems(F)
+ *                            floats, contents on entry are arbitrary (every row range stores its sum, an empty one its zero).
  * Reconstruction loss on the rows rows[0..n_rows) (int64, duplicate-free) of z (N x F), with rptr / rcol / rval = the compact CSR
  * of A_hat[rows, :]:
  *   attr_i = ||x_i - xhat_i||, stru_i = sqrt(sum_{j<N} (A_ij - sigmoid(z_i . z_j))^2), score_i = 0.5 attr_i + 0.5 stru_i,
- *   loss = mean_i score_i (loss may be NULL: scoring only).  The N x N matrix is never formed; ws = ggad_adae_stru_fwd_workspace_elems;
+ *   loss = mean_i score_i (loss may be NULL: scoring only).  The N x N matrix is never formed; ws = ggad_adae_stru_fwd_workspace_elems
+ *   floats, contents on entry are arbitrary;
  *   s_edge (may be NULL): sigmoid(z_i . z_j) per entry of the compact CSR, what the backward reads.
  * ggad_adae_stru_bwd_f32: dz (N x F, every row written) = d loss / d z scaled by *gloss (device float); pos[j] = position of node
  *   j in rows or -1; tptr (N + 1) / trow / tedge = the entries of the compact CSR grouped by column (row position, entry index);
- *   ws = ggad_adae_stru_bwd_workspace_elems; F <= 768.
+ *   ws = ggad_adae_stru_bwd_workspace_elems floats, contents on entry are arbitrary; F <= 768.
  * ggad_adae_attr_bwd_f32: dxhat rows `rows` = *gloss (0.5 / n_rows) (xhat - x) / attr (other rows untouched). */
 int ggad_adae_gat_alpha_f32(const float *y, const float *a_s, const float *a_d, int32_t n, int32_t F, float *als, float *ald,
                             ggad_stream_t stream);
@@ -259,7 +265,8 @@ int ggad_adae_attr_bwd_f32(const float *x, const float *xhat, const int64_t *row
  *   int64 num_batches_tracked are updated in place (each may be NULL: not updated).  Output rows k = rows[k] of the concatenation
  *   (rows NULL: k < n_out <= M): y (row stride ldy) when w2 is NULL, else the head p[k] = sigmoid(y . w2 + b2) without y.
  *   M < 2 -> GGAD_E_INVALID (torch: more than 1 value per channel); C != ggad_aegis_bn_channels() -> GGAD_E_UNSUPPORTED, nothing
- *   launched.  Rows are 16-byte aligned (strides multiples of 4).  ws = ggad_aegis_bn_workspace_elems(M, C) floats; ticket = one
+ *   launched.  Rows are 16-byte aligned (strides multiples of 4).  ws = ggad_aegis_bn_workspace_elems(M, C) floats, contents on entry
+ *   are arbitrary (here, at ggad_aegis_bn_bwd_f32 and at ggad_aegis_loss_fwd_f32); ticket = one
  *   int32.  Two launches.
  *   TICKET WORDS, here and at every `ticket` / `tickets` parameter of this header: int32 in device memory that count the workgroups
  *   of a launch as they finish (csrc/handoff.h).  They must be ZERO before the first call; every launch leaves them zero, so they
@@ -298,7 +305,7 @@ int ggad_aegis_loss_bwd_f32(const float *p, int64_t n, const float *gloss_g, flo
  * each with its columns j ascending where (normalize_adj(A) + I)[i, j] > 0.  emb and z are N x C, row-major, 16-byte aligned.
  * ggad_gaan_edge_fwd_f32: a_e = sigmoid(<emb_i, emb_j>) (written to a_out, m floats, for the backward), a'_e = sigmoid(<z_i, z_j>);
  *   loss[1] = mean_e -max(log1p(-a'_e), -100) (BCE against 0), loss[2] = mean_e -max(log(a_e), -100) (BCE against 1),
- *   loss[0] = (loss[1] + loss[2]) / 2.  ws = ggad_gaan_edge_fwd_workspace_elems(m) floats.  Two launches.
+ *   loss[0] = (loss[1] + loss[2]) / 2.  ws = ggad_gaan_edge_fwd_workspace_elems(m) floats, contents on entry are arbitrary.  Two launches.
  * ggad_gaan_edge_bwd_f32: dE (N x C, every row written) = G emb + G^T emb with G_e = ((*gloss / 2 / m) (a_e - 1) /
  *   max((1 - a_e) a_e, 1e-12)) (1 - a_e) a_e on E.  pos[k] = position of node k in the row list (-1: absent), rptr (n_rows + 1) the
  *   row list's offsets into E; tptr (N + 1) / trow / tedge: the entries (i, k) of E grouped by k, trow = i, tedge = e, ascending e.
@@ -320,10 +327,12 @@ int ggad_gaan_edge_bwd_f32(const float *emb, int64_t n, int32_t C, const int32_t
  * ggad_dominant_ae_f32: one launch: loss[0] = mean of e over the train rows, score[k] = e of test row k, and the gradients at
  *   d loss = 1 (dW1 H x F, dB1 H, dW2 F x H, dB2 F; every element written).  Only the listed rows are evaluated.  (F, H) outside
  *   ggad_dominant_ae_supported -> GGAD_E_UNSUPPORTED, nothing launched.  ws = ggad_dominant_ae_workspace_elems(m, t_rows, F, H)
- *   floats; tickets = ggad_dominant_tickets() int32 (TICKET WORDS above).  Fixed-order sums, no float atomics.
+ *   floats, contents on entry are arbitrary; tickets = ggad_dominant_tickets() int32 (TICKET WORDS above).  Fixed-order sums, no
+ *   float atomics.
  * ggad_dominant_recon_f32: one launch from a computed x_ (xh, N x F): loss[0], score as above and dxh (N x F, every element
  *   written) = (xh - x) / (e m) on the train rows (pos[i] = position of node i in the train list, -1 off it), 0 elsewhere.
- *   ws = ggad_dominant_recon_workspace_elems(n, m, t_rows) floats; ticket = one int32 (TICKET WORDS above).
+ *   ws = ggad_dominant_recon_workspace_elems(n, m, t_rows) floats, contents on entry are arbitrary; ticket = one int32 (TICKET WORDS
+ *   above).
  * ggad_dominant_scale_f32: dst[i] = src[i] * g[0] for i < n (g in device memory).  One launch. */
 int32_t ggad_dominant_ae_supported(int32_t F, int32_t H);
 int32_t ggad_dominant_tickets(void);
@@ -558,7 +567,8 @@ int ggad_device_cu_count(int32_t device, int32_t *out);
 /* C[M x N] = epilogue(A * B), fp32 on the matrix cores (v_mfma_f32_32x32x2_f32, exact f32).
  * A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]: NN / NT / TN by strides.  Replaces nn.Linear /
  * torch.mm and their autograd (model.py:27,156,176-180).  bias[N] and relu are optional epilogues.
- * workspace: float[ggad_gemm_workspace_elems(M,N,K)] (0 = no split-K needed; may be NULL). */
+ * workspace: float[ggad_gemm_workspace_elems(M,N,K)] (0 = no split-K needed; may be NULL); contents on entry are arbitrary: every
+ * split stores its whole M x N slice before the reduction reads it, a split whose K range is empty (the ranges are rounded up to 32) zeros. */
 int64_t ggad_gemm_workspace_elems(int32_t M, int32_t N, int32_t K);
 int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N, int32_t K, int64_t sam, int64_t sak,
                   int64_t sbk, int64_t sbn, int64_t ldc, const float *bias, int32_t relu, float *workspace,
@@ -570,7 +580,8 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
  * seg_out[s] < 0: the partial sum goes to part[-seg_out[s] - 1][W] and the row is listed in multi_row / multi_first /
  * multi_count (output row, first slot, number of slots), summed in slot order by a second launch; part holds
  * n_seg x W floats, slots are unique and < n_seg.  The order of the segments in the tables is the launch order and is free.
- * The segment tables are built once per matrix (and per row subset) on the host.
+ * The segment tables are built once per matrix (and per row subset) on the host.  part: contents on entry are arbitrary (a slot is read
+ * only behind the store of its segment; an EMPTY segment -- a row without entries -- stores its zero sum like any other).
  * act = PReLU with slope *prelu_a if given; out_pre (optional) receives the pre-activation.  W % 4 == 0.
  * Replaces torch.bmm(adj, .) + bias + PReLU (model.py:31-35), adj[0, abn, :] @ emb (model.py:151-155),
  * the column sums of sim * raw_adj (run.py:182-188, as R^T e_hat) and every transposed product in backward. */
@@ -612,7 +623,7 @@ int ggad_prelu_bwd_ld_f32(const float *g, const float *z, const float *prelu_a, 
  * of every group of four adds the group's partial column sums, the last group reduces the group rows -- every sum in a fixed order.
  * `workspace`: ggad_prelu_bwd_one_workspace_elems(M, W) floats; `ticket`: ggad_prelu_bwd_one_tickets() int32 in device memory (TICKET
  * WORDS at ggad_aegis_bn_fwd_f32: zero before the first call, left zero, shared only by stream-ordered launches).  Shapes the vector kernel does not take run
- * the two launches. */
+ * the two launches.  workspace: contents on entry are arbitrary. */
 int64_t ggad_prelu_bwd_one_workspace_elems(int32_t M, int32_t W);
 int32_t ggad_prelu_bwd_one_tickets(void);
 int ggad_prelu_bwd_one_f32(const float *g, const float *z, const float *prelu_a, int32_t M, int32_t W, float *dz, int64_t ld_dz, float *db,
@@ -622,9 +633,11 @@ int ggad_prelu_bwd_one_f32(const float *g, const float *z, const float *prelu_a,
  * re-laid slice-major into xs_workspace (ggad_spmm_sliced_workspace_elems(n_src_rows, W) floats; column slices of 32 floats =
  * one cache line per row), then every workgroup gathers ONE slice, chosen by the XCD it runs on, 8 neighbours per load.  n_src_rows = rows of X.  Same
  * segment tables, epilogue and outputs as ggad_spmm_csr_f32; the summation order inside a segment differs (lane groups
- * take every 8th neighbour), so results agree to fp32 round-off, and are deterministic. */
+ * take every 8th neighbour), so results agree to fp32 round-off, and are deterministic.  xs_workspace and part: contents on entry are
+ * arbitrary, and the buffer may be larger than this call needs (one staging buffer serves products of every width and row count: the
+ * lanes of a last, partial slice beyond W are written as zeros and never reach an output; nothing behind n_src_rows rows per slice is read). */
 int64_t ggad_spmm_sliced_workspace_elems(int64_t n_src_rows, int32_t W);
-int ggad_spmm_sliced_seg_len(void); /* recommended segment length of ITS segment tables (any length is accepted; empty segments are not) */
+int ggad_spmm_sliced_seg_len(void); /* recommended segment length of ITS segment tables (any length is accepted, 0 too: a row without entries) */
 int ggad_spmm_sliced_f32(const int32_t *col, const float *val, const int32_t *seg_beg, const int32_t *seg_end,
                          const int32_t *seg_out, int32_t n_seg, const int32_t *multi_row, const int32_t *multi_first,
                          const int32_t *multi_count, int32_t n_multi, const float *X, int64_t ldx, int32_t W, int64_t n_src_rows,
@@ -640,7 +653,8 @@ int ggad_spmm_sliced_f32(const int32_t *col, const float *val, const int32_t *se
  * dir[(block * waves + wave) * n_chunks + chunk][8] = {first oct of the wave's tiles of that panel, 8 x 16-bit counts of the QUADS
  * (4 steps) walked per round: whole octs, then half of the last one}, stream = [oct][8 lane groups][8 steps] uint16, two
  * per uint32, + 8 spare octs, row_tab[(block * waves + wave) * rounds + round][8] = output row (| GGAD_SPMM_PANEL_WIDE) or -1.  xs_workspace as for ggad_spmm_sliced_f32.
- * Deterministic; agrees with the other two kernels to fp32 round-off (the scales are applied outside the sum). */
+ * Deterministic; agrees with the other two kernels to fp32 round-off (the scales are applied outside the sum).  xs_workspace: contents on
+ * entry are arbitrary; the rows of a last, partial panel behind n_src_rows are never indexed by the stream. */
 /* Host half of its plan (csrc/spmm_panel_build.cpp, host pointers, threads; n_threads <= 0: one per core, 32 at most):
  * round_rows[n_rounds][8] = the 8 rows of a round (-1: none); ggad_spmm_panel_count -> steps_rc[round][panel] = entries of the
  * round's longest row in that panel of panel_rows columns; ggad_spmm_panel_fill writes the entry stream: tile (round, panel)
@@ -679,7 +693,8 @@ int ggad_spmm_panel_f32(const int32_t *wg_tab, int32_t n_wg, const uint32_t *dir
  * idx = [super-block][2 halves][8 lane groups][2 quads][4 steps] uint16 (+ one spare super-block); ctl = one byte per quad:
  * bits 0..5 = 4 * accumulator slot (< ggad_spmm_ring_rounds()), bit 6 = last quad of its phase (every walker flags every phase);
  * row_tab[(block * walkers + wave) * rounds + slot][8] = output row (| GGAD_SPMM_PANEL_WIDE) or -1; n_phases = ceil(n_src_rows /
- * slot_rows).  Deterministic; agrees with the other SpMM kernels to fp32 round-off.
+ * slot_rows).  Deterministic; agrees with the other SpMM kernels to fp32 round-off.  xs_workspace: as for ggad_spmm_panel_f32 (contents on
+ * entry are arbitrary; the last phase stages a partial slot).
  * Host half (csrc/spmm_ring_build.cpp, host pointers, threads): ggad_spmm_ring_count -> quads_rp[round][phase] = quads the round
  * walks in that phase under the flexible schedule (a lane group without open entry in the slot that is overwritten next walks
  * its next entries anywhere in the window); ggad_spmm_ring_fill writes idx given the absolute first quad of every (round, phase)
@@ -720,7 +735,8 @@ int ggad_mlp_score_fwd_f32(const float *X, int64_t ldx, int32_t R, int32_t H, in
 /* The three WEIGHT gradients of the scorer in one launch + one reduction (ABI 7; they were three split-K ggad_gemm_f32 calls):
  *   dW1 (H1 x H) = dz1^T x,  dW2 (H2 x H1) = dz2^T f1,  dW3 (1 x H2) = g3^T f2      over the same R rows.
  * x: R x H with row stride ldx; dz1, f1: R x H1; dz2, f2: R x H2; g3: R -- all contiguous but x.  Outputs contiguous.  workspace:
- * float[ggad_mlp_score_wgrad_workspace_elems(R, H, H1, H2)], 16-byte aligned (partials per row range, added in range order). */
+ * float[ggad_mlp_score_wgrad_workspace_elems(R, H, H1, H2)], 16-byte aligned (partials per row range, added in range order); contents on
+ * entry are arbitrary. */
 int64_t ggad_mlp_score_wgrad_workspace_elems(int32_t R, int32_t H, int32_t H1, int32_t H2);
 int ggad_mlp_score_wgrad_f32(const float *x, int64_t ldx, const float *dz1, const float *f1, const float *dz2, const float *f2, const float *g3,
                              int32_t R, int32_t H, int32_t H1, int32_t H2, float *dW1, float *dW2, float *dW3, float *workspace,
@@ -730,7 +746,7 @@ int ggad_mlp_score_dgrad_f32(const float *g3, int32_t R, int32_t H, int32_t H1, 
                              const float *dx_add, int64_t ld_add, ggad_stream_t stream);
 
 /* PReLU backward: dz = g * (z > 0 ? 1 : a); db[W] = column sums of dz; *da = sum g * z * [z <= 0].
- * workspace: float[2 * ggad_prelu_bwd_splits(M) * W].  db / da may be NULL. */
+ * workspace: float[2 * ggad_prelu_bwd_splits(M) * W], contents on entry are arbitrary.  db / da may be NULL. */
 int32_t ggad_prelu_bwd_splits(int32_t M);
 int ggad_prelu_bwd_f32(const float *g, const float *z, const float *prelu_a, int32_t M, int32_t W, float *dz, float *db,
                        float *da, float *workspace, ggad_stream_t stream);
@@ -785,7 +801,7 @@ int ggad_rows_scale_f32(const float *X, const int32_t *sel, const float *coef, i
 /* The scalar part of the loss block of run.py:165-210 and its gradients: logits[L], aff[L] (L = n_normal + n_out,
  * normal_idx entries first), emb_con / emb_abn (n_out x H).  losses4 = {total, margin, bce, rec};
  * d_logits[L]; g_aff[L] = d total / d aff; dD = d total / d (emb_con - emb_abn). */
-int64_t ggad_full_loss_workspace_elems(int32_t n_out, int32_t H);   /* floats of `workspace` (partial column sums of the recon term) */
+int64_t ggad_full_loss_workspace_elems(int32_t n_out, int32_t H);   /* floats of `workspace` (partial column sums of the recon term); contents on entry are arbitrary */
 int ggad_full_loss_f32(const float *logits, const float *aff, int32_t n_normal, int32_t n_out, const float *emb_con,
                        const float *emb_abn, int32_t H, float margin, float *losses4, float *d_logits, float *g_aff,
                        float *dD, float *workspace, ggad_stream_t stream);
@@ -799,7 +815,8 @@ int ggad_full_loss_bwd_scale_f32(const float *g_total, const float *g_aff, const
  * margin, recon, the four loss values and the coefficients (replaces ggad_rowdot_f32 + ggad_full_loss_f32: four launches);
  * backward: c, d logits, xc = c e_hat[J], d emb_con = g (con - abn) kcol, d emb_abnormal = -that (replaces ggad_full_loss_bwd_scale_f32 +
  * ggad_rows_scale_f32);  ggad_rownorm_bwd_add_f32 = ggad_rownorm_bwd_f32 with dXn[r] += c[q] S[q] for r = J[q] folded in (pos_n / pos_a:
- * position of row r in the normal / abnormal segment of J, or -1).  `ticket`: one int32 (TICKET WORDS at ggad_aegis_bn_fwd_f32). */
+ * position of row r in the normal / abnormal segment of J, or -1).  `ticket`: one int32 (TICKET WORDS at ggad_aegis_bn_fwd_f32);
+ * `workspace`: ggad_full_loss_fused_workspace_elems floats, contents on entry are arbitrary. */
 int64_t ggad_full_loss_fused_workspace_elems(int32_t n_out, int32_t H);
 int ggad_full_loss_fused_f32(const float *e_hat, const int32_t *J, const float *S, const float *r_inv_j, int32_t n_normal, int32_t n_out,
                              int32_t H, const float *logits, const float *emb_con, const float *emb_abn, float margin, float *aff,
@@ -884,7 +901,7 @@ int ggad_sage_sched_epoch(ggad_mt19937 *, int64_t *train, int64_t n_train, int64
  * n % 16 != 0 (torch redraws the last 16 outputs), and writes out[i] = normal_i * scale + shift, product and sum rounded
  * separately.  Values agree with the host's to float32 rounding of log / sin / cos, not bit for bit; the state is exact.  Everything
  * stays on the device: a captured launch draws fresh values at every replay.  `scratch`: ggad_mt_randn_scratch_elems(n) uint32
- * (the raw words).  n < 16 (a different algorithm in torch) or a null pointer -> GGAD_E_INVALID, nothing launched.
+ * (the raw words; contents on entry are arbitrary).  n < 16 (a different algorithm in torch) or a null pointer -> GGAD_E_INVALID, nothing launched.
  * ---------------------------------------------------------------------------------- */
 int32_t ggad_mt_state_words(void);
 int64_t ggad_mt_randn_scratch_elems(int64_t n);
