@@ -6,7 +6,8 @@ slice boundaries (the aggregation normalises per slice, quirk 2), never on the w
 `sigmoid(w . relu(W x1[i]))`, row by row (`k_score`, csrc/step.hip: one wave per row, a fixed fma order, nothing that depends on
 the launch size).  `ResidentSweep` therefore builds the plans ONCE, keeps the `(n, F)` rows, and a sweep is one `ggad_mb_score`
 launch over them: bit for bit what `score_nodes` returns.  The metrics come from the counting kernels of csrc/rank_metrics.hip
-(`metrics.rank_report`) instead of two device sorts.
+(`metrics.rank_report`) instead of two device sorts; above their 8,192 positives, with config key `rank_wide`, from those of
+csrc/rank_wide.hip (`metrics.rank_report_wide`).
 """
 from __future__ import annotations
 
@@ -28,8 +29,11 @@ class ResidentSweep:
     A caller that changes the feature table or the graph calls `invalidate()`; the rows are then rebuilt by the next `scores()`.
     The ids are copied at construction: a list mutated in place afterwards is NOT detected (build a new sweep for a new list)."""
 
-    def __init__(self, model, test_cases: Sequence[int], labels, batch_size: int, batches_per_launch: int = 2048):
+    def __init__(self, model, test_cases: Sequence[int], labels, batch_size: int, batches_per_launch: int = 2048,
+                 rank_wide: bool = False):
         self.model = model
+        self.rank_wide = bool(rank_wide)                         # config key `rank_wide`: see report()
+        self.n_pos = None                                        # with rank_wide: the label-1 entries, counted once on the host
         self.engine = model.enc.engine
         self.cases = np.array(test_cases, dtype=np.int64).reshape(-1)
         self.n = int(len(self.cases))
@@ -39,6 +43,8 @@ class ResidentSweep:
             if len(lab) != self.n:
                 raise ValueError("ResidentSweep: labels / test_cases length mismatch")
             self.labels = torch.from_numpy(lab.astype(np.uint8)).to(self.engine.dev)      # uploaded once
+            if self.rank_wide:
+                self.n_pos = int(np.count_nonzero(lab == 1))                              # (the labels never change)
         self.ids = torch.from_numpy(self.cases).to(self.engine.dev)                       # for top_k, uploaded once
         self.batch_size = int(batch_size)
         self.batches_per_launch = int(batches_per_launch)
@@ -89,11 +95,17 @@ class ResidentSweep:
 
     def report(self, thres: float, scores: torch.Tensor = None) -> Dict[str, float]:
         """The dict of `metrics.binary_report` for the current weights, from `metrics.rank_report` (the faster of the two metric blocks
-        at 1.74 M scores: profiles/eval_cache_time_line.json).  `scores`: a result of `scores()` the caller already holds."""
-        from .metrics import rank_report
+        at 1.74 M scores: profiles/eval_cache_time_line.json).  `scores`: a result of `scores()` the caller already holds.
+        A sweep built with `rank_wide=True` whose list holds more positives than `ggad_rank_metrics_max_pos()` reports through
+        `metrics.rank_report_wide` with `pos_cap` = its count of positives, where `rank_report` would fall back to `binary_report`;
+        a list at or under the cap takes `rank_report` either way."""
+        from .metrics import rank_report, rank_report_wide
         if self.labels is None:
             raise ValueError("ResidentSweep.report: this sweep was built without labels (an id list to rank: use top_k)")
-        return rank_report(self.scores() if scores is None else scores, self.labels, thres)
+        scores = self.scores() if scores is None else scores
+        if self.rank_wide and self.n_pos > int(self.engine.lib.ggad_rank_metrics_max_pos()):
+            return rank_report_wide(scores, self.labels, thres, pos_cap=min(self.n_pos, int(self.engine.lib.ggad_rank_wide_max_pos())))
+        return rank_report(scores, self.labels, thres)
 
     def top_k(self, k: int, scores: torch.Tensor = None):
         """`metrics.top_k` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) with the

@@ -10,7 +10,8 @@ sklearn.  Definitions follow scikit-learn's (the reference's metric library), in
 sklearn itself stays the checker in the tests (tests/test_metrics.py).
 
 `rank_report` returns the same dict from float32 scores and uint8 labels through the counting kernels of csrc/rank_metrics.hip:
-no full sort (only the positives are sorted), four launches and ONE read-back.
+no full sort (only the positives are sorted), four launches and ONE read-back.  `rank_report_wide` is the same for more than the
+8,192 positives one workgroup sorts, up to 1,048,576, through csrc/rank_wide.hip.
 
 `top_k` is the ranked list: the k highest scores in a FIXED order (score descending, equal scores by ascending position; the head
 of a saturated sigmoid ranking is full of exact ties, and `torch.topk` fixes neither which tied elements it returns nor their
@@ -96,6 +97,33 @@ def rank_report(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float) -> 
         ws = torch.empty(max(1, int(lib.ggad_rank_metrics_workspace_elems(n))), dtype=torch.int32, device=scores.device)
         out8 = torch.empty(8, dtype=torch.float64, device=scores.device)
         _lib.call("ggad_rank_metrics_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, float(thres), _lib.ptr(out8), _lib.ptr(ws))
+        return _report_from_out8(out8.cpu().tolist(), lambda: binary_report(scores, labels_u8, thres))
+
+
+def rank_report_wide(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float, pos_cap: Optional[int] = None) -> Dict[str, float]:
+    """`rank_report` for up to `ggad_rank_wide_max_pos()` = 1,048,576 positives, from `ggad_rank_wide_f32` (csrc/rank_wide.hip: the
+    positives sorted in runs of 2,048 and merged, the same formulas): same arguments, same checks, same dict, one read-back.
+    `pos_cap`: the caller's upper bound on the positives, which sizes the workspace and the launches (`None`: min(n, the cap); a
+    tight bound means fewer merge passes and less workspace).  More positives than `pos_cap`: the result of `binary_report`.
+    Timings against `binary_report` and `rank_report`: profiles/rank_wide_time_line.json."""
+    from . import _lib
+    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+        raise ValueError("rank_report takes float32 scores and uint8 labels of the same 1-D shape")
+    if scores.device.type != "cuda" or labels_u8.device != scores.device:
+        raise ValueError("rank_report takes scores and labels on the same GPU (there is no CPU path: use binary_report)")
+    lib = _lib.load()
+    n = scores.numel()
+    cap = int(lib.ggad_rank_wide_max_pos())
+    if pos_cap is None:
+        pos_cap = max(1, min(n, cap))
+    if int(pos_cap) != pos_cap or not 1 <= int(pos_cap) <= cap:
+        raise ValueError(f"rank_report_wide: pos_cap = {pos_cap} is outside 1..ggad_rank_wide_max_pos() = {cap}")
+    pos_cap = int(pos_cap)
+    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
+    with torch.cuda.device(scores.device):
+        ws = torch.empty(int(lib.ggad_rank_wide_workspace_elems(n, pos_cap)), dtype=torch.int32, device=scores.device)
+        out8 = torch.empty(8, dtype=torch.float64, device=scores.device)
+        _lib.call("ggad_rank_wide_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, pos_cap, float(thres), _lib.ptr(out8), _lib.ptr(ws))
         return _report_from_out8(out8.cpu().tolist(), lambda: binary_report(scores, labels_u8, thres))
 
 

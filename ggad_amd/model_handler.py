@@ -19,6 +19,8 @@ round-robin over the ranks and gradients are all-reduced once per step (SURVEY.m
 ``top_k: K`` / ``top_k_out`` (`model: 'GCN'`, one GPU): the K highest scores of the closing test sweep are ranked on the device in a
 fixed order (`metrics.top_k`, csrc/topk.hip), kept in `self.ranked`, reported in one line and written to an `.npz`;
 `ModelHandler(config).score(checkpoint)` does the sweep, the report and the ranking from a saved checkpoint without training.
+``rank_wide: true`` (with ``eval_cache: true``): a validation / test list with more than 8,192 positives is reported from the
+counting kernels of csrc/rank_wide.hip instead of `binary_report`'s two device sorts.
 
 The loader and split, the adjacency coercion, the checkpoint rule and the epoch loop of the labelled-batch models (`_train_sage`,
 `_train_sage_device`, `_train_pcgnn` build model, optimiser and containers and hand them to it) live in `handler_loop.py`; the GGAD
@@ -94,6 +96,9 @@ class ModelHandler(object):
             if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                 raise ValueError("config key `eval_cache` runs on one GPU: the resident sweep is not sharded over the ranks of a "
                                  "torch.distributed world yet")
+        if bool(getattr(args, "rank_wide", False)) and not bool(getattr(args, "eval_cache", False)):
+            raise ValueError("config key `rank_wide` needs `eval_cache: true`: it chooses the metric kernels of the resident sweep "
+                             "(without the sweep the metrics come from `binary_report`)")
         top_k, top_k_out = getattr(args, "top_k", 0) or 0, str(getattr(args, "top_k_out", "") or "")
         if top_k or top_k_out:
             if getattr(args, "model", None) != "GCN":
@@ -183,7 +188,7 @@ class ModelHandler(object):
         sweep = None
         if bool(getattr(args, "eval_cache", False)):
             from .eval_cache import ResidentSweep
-            sweep = ResidentSweep(gnn_model, ids, labels, args.batch_size)
+            sweep = ResidentSweep(gnn_model, ids, labels, args.batch_size, rank_wide=bool(getattr(args, "rank_wide", False)))
         self.eval_sweeps = (sweep, sweep)
         self.metrics, self.sweep_ap = None, []
         if labels is not None:
@@ -264,9 +269,10 @@ class ModelHandler(object):
         sweep_valid = sweep_test = None
         if bool(getattr(args, "eval_cache", False)):
             from .eval_cache import ResidentSweep
-            sweep_valid = ResidentSweep(gnn_model, idx_valid, y_valid, args.batch_size)
+            wide = bool(getattr(args, "rank_wide", False))       # config key `rank_wide`: lists above 8,192 positives keep the counting route
+            sweep_valid = ResidentSweep(gnn_model, idx_valid, y_valid, args.batch_size, rank_wide=wide)
             sweep_test = sweep_valid if (idx_test is idx_valid and y_test is y_valid) else \
-                ResidentSweep(gnn_model, idx_test, y_test, args.batch_size)
+                ResidentSweep(gnn_model, idx_test, y_test, args.batch_size, rank_wide=wide)
         self.eval_sweeps = (sweep_valid, sweep_test)
         trainer.start_stream(steps_per_epoch * args.num_epochs)        # sampler thread alive across the validation pauses
         total_time = 0.0

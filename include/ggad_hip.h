@@ -1170,6 +1170,24 @@ int64_t ggad_topk_workspace_elems(int64_t n, int32_t k);       /* int32 elements
 int ggad_topk_f32(const float *score, const uint8_t *label, int64_t n, int32_t k, int32_t *out_pos, float *out_score,
                   int32_t *out_cumpos, int64_t *out_meta, int32_t *workspace, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * The rank metrics of ggad_rank_metrics_f32 for up to ggad_rank_wide_max_pos() = 1,048,576 positives (rank_wide.hip): the same
+ * formulas, the same out8 and the same status codes.  The positives are sorted in runs of 2,048 (one workgroup each, in LDS) and
+ * merged in ceil(log2(runs)) passes; every negative is bucketed against the one tile of 8,192 sorted keys whose range holds it; the
+ * sums are made per tile and added in a fixed order.  `pos_cap` is the caller's upper bound on the positives (what k is to ggad_topk_f32): the
+ * workspace and every grid follow from (n, pos_cap) alone, so equal inputs give equal bits.  Status 2 = more positives than
+ * pos_cap (the counts are valid, auroc / ap NaN).
+ *
+ * 0 <= n <= INT32_MAX, 1 <= pos_cap <= ggad_rank_wide_max_pos(); outside: GGAD_E_INVALID and no launch.  5 + ceil(log2(ceil(
+ * min(pos_cap, n) / 2048))) launches on `stream`, no host synchronisation, integer atomics only, nothing that waits on another
+ * workgroup.  workspace: ggad_rank_wide_workspace_elems(n, pos_cap) int32 elements (0 = refused), 16-byte aligned, no preparation
+ * needed: every word a launch reads was written by an earlier launch of the same call, so the call is capturable and replayable.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_rank_wide_max_pos(void);
+int64_t ggad_rank_wide_workspace_elems(int64_t n, int64_t pos_cap);   /* int32 elements; 0 = refused */
+int ggad_rank_wide_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, double *out8,
+                       int32_t *workspace, ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

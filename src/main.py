@@ -128,6 +128,8 @@ if __name__ == "__main__":
                          "config's seed, print its report and, with top_k > 0, the ranked list")
     ap.add_argument("--top_k", type=int, default=None, help="override the config's top_k (rank the K highest test scores; 0 = off)")
     ap.add_argument("--top_k_out", type=str, default=None, help="override the config's top_k_out (.npz of the ranked list)")
+    ap.add_argument("--rank_wide", action="store_true", default=None,
+                    help="override the config's rank_wide (with eval_cache: exact rank metrics in HIP above 8,192 positives)")
     a = ap.parse_args()
     if a.score is not None and a.handler != "ggad":
         ap.error("--score serves --handler ggad only")
@@ -141,6 +143,8 @@ if __name__ == "__main__":
         cfg["top_k"] = a.top_k
     if a.top_k_out is not None:
         cfg["top_k_out"] = a.top_k_out
+    if a.rank_wide is not None:
+        cfg["rank_wide"] = a.rank_wide
     SCORE = a.score
     use_handler(a.handler)
     init_distributed()
