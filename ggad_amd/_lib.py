@@ -25,7 +25,18 @@ class GgadKernelError(RuntimeError):
     pass
 
 
-ABI_VERSION = 10   # what this binding was written against (include/ggad_hip.h, runtime.cpp); `load` refuses any other library
+# `enum ggad_gemm_route` of include/ggad_hip.h: what `ggad_gemm_last_route()` & 0xFF names; the variant is the rest (>> 8)
+GEMM_ROUTES = ("NONE", "SLAB", "BRES", "WGRAD_TN", "SMALL", "DMA", "DMA_SPLITK", "TILED", "TILED_SPLITK")
+
+
+def gemm_last_route():
+    """(route name, variant) of this thread's last `ggad_gemm_f32` / `ggad_linear_prelu_f32` call; the variant as the header's
+    GGAD_GEMM_VARIANT_* macros pack it."""
+    v = int(load().ggad_gemm_last_route())
+    return GEMM_ROUTES[v & 0xFF], v >> 8
+
+
+ABI_VERSION = 11   # what this binding was written against (include/ggad_hip.h, runtime.cpp); `load` refuses any other library
 _P = c_void_p      # device (or host) pointer
 EXCHANGE_CB = ctypes.CFUNCTYPE(c_int32, c_void_p)      # int exchange(void *user): the data-parallel all-reduce hook
 _I = c_int32
@@ -141,6 +152,7 @@ SIGNATURES = {
     "ggad_dominant_scale_f32": (c_int32, [_P, _L, _P, _P, _P]),
     "ggad_gemm_workspace_elems": (c_int64, [_I, _I, _I]),
     "ggad_gemm_f32": (c_int32, [_P, _P, _P, _I, _I, _I, _L, _L, _L, _L, _L, _P, _I, _P, _P]),
+    "ggad_gemm_last_route": (c_int32, []),
     "ggad_spmm_seg_len": (c_int32, []),
     "ggad_spmm_csr_f32": (c_int32, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _L, _I, _P, _P, _P, _L, _P, _P, _P]),
     "ggad_spmm_rowslice_group": (c_int32, []),

@@ -109,7 +109,8 @@ int ggad_int_gemm_slab(const float *A, const float *B, float *C, int M, int N, i
 
 // ---- mlp.hip: D (m x n) = P^T Q over R rows as row-range partials + ordered reduction (the weight gradients); 1 = launched, 0 = not taken
 int64_t ggad_int_wgrad_tn_ws(int R, int m, int n);
-int ggad_int_wgrad_tn(const float *P, int64_t ldp, const float *Q, int64_t ldq, int R, int m, int n, float *D, float *ws, hipStream_t st);
+int ggad_int_wgrad_tn(const float *P, int64_t ldp, const float *Q, int64_t ldq, int R, int m, int n, float *D, float *ws, hipStream_t st,
+                      int *vpq = nullptr);      // vpq: GGAD_GEMM_VARIANT_TN(vp, vq) of the launch, for ggad_gemm_last_route
 
 // ---- step_wide.hip: the layered step chain for 64 < D <= 256 (and chain 3 at any D <= 256); arguments and buffer contracts of the
 // ggad_mb_* entry points of the same names (step.hip forwards to these)

@@ -651,9 +651,16 @@ static int pick_tm(int M, int N) {
   (void)M; (void)N;
   return forced == 128 ? 128 : 64;
 }
+
+// which kernel the last ggad_gemm_f32 / ggad_linear_prelu_f32 call of this thread chose (ggad_gemm_last_route, include/ggad_hip.h): a
+// host-side store made when the call is made -- no synchronisation, no part in the dispatch
+thread_local int32_t g_gemm_route = GGAD_GEMM_ROUTE_NONE;
+inline void gemm_note_route(int route, int variant) { g_gemm_route = GGAD_GEMM_ROUTE_PACK(route, variant); }
 }  // namespace
 
 extern "C" {
+
+int32_t ggad_gemm_last_route(void) { return g_gemm_route; }
 
 // split-K factor of the tiled kernels for an M x N x K product (1 = no split); the ONE place that decides it -- the workspace query sizes
 // for it, the launches below use it (they used to divide the workspace size, which is the max() with the row-range kernel's: ADVICE round 5)
@@ -685,6 +692,7 @@ int64_t ggad_gemm_workspace_elems(int32_t M, int32_t N, int32_t K) {
 int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N, int32_t K, int64_t sam, int64_t sak,
                   int64_t sbk, int64_t sbn, int64_t ldc, const float *bias, int32_t relu, float *workspace,
                   ggad_stream_t stream) {
+  gemm_note_route(GGAD_GEMM_ROUTE_NONE, 0);
   GGAD_REQUIRE(A && B && C && M >= 0 && N >= 0 && K >= 0 && ldc >= N);
   // 32-bit element offsets inside a tile row range (BM rows x K) / (K x BN): every stride times its extent must fit
   GGAD_REQUIRE((sam == 1 || sak == 1) && (sbk == 1 || sbn == 1));
@@ -705,7 +713,7 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
   if (a_kfast && ws_elems == 0) {
     const int r = ggad_int_gemm_slab(A, B, C, (int)M, (int)N, (int)K, sam, sbk, sbn, ldc, bias, (int)relu, st);
     if (r < 0) { ggad_set_error(hipErrorLaunchFailure, "gemm_f32 (slab)"); return GGAD_E_LAUNCH; }
-    if (r > 0) return GGAD_OK;
+    if (r > 0) { gemm_note_route(GGAD_GEMM_ROUTE_SLAB, (K + 15) / 16); return GGAD_OK; }
   }
   static const int bres = [] { const char *e = getenv("GGAD_GEMM_BRES"); return e ? atoi(e) : 1; }();
   // (measured, scripts/gemm_bres_ab.py: 39,357 rows 105-108 -> 92-97 us; at 7,500-12,000 rows -7 ... +5 %, inside the box-to-box noise --
@@ -726,14 +734,16 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
       default: GGAD_BRES(20); break;
     }
 #undef GGAD_BRES
+    gemm_note_route(GGAD_GEMM_ROUTE_BRES, KSn < 20 ? KSn : 20);
     GGAD_CHECK_LAUNCH("gemm_f32 (resident operand)");
     return GGAD_OK;
   }
   // weight gradients (op(A) = A^T with A: K x M row-major, B: K x N row-major, K long): row ranges + ordered reduction (mlp.hip)
   if (ws_elems > 0 && sam == 1 && sbn == 1 && ldc == N && !bias && !relu && ws_elems >= ggad_int_wgrad_tn_ws(K, M, N) && ggad_int_wgrad_tn_ws(K, M, N) > 0) {
-    const int r = ggad_int_wgrad_tn(A, sak, B, sbk, (int)K, (int)M, (int)N, C, workspace, st);
+    int vpq = 0;
+    const int r = ggad_int_wgrad_tn(A, sak, B, sbk, (int)K, (int)M, (int)N, C, workspace, st, &vpq);
     if (r < 0) { ggad_set_error(hipErrorLaunchFailure, "gemm_f32 (wgrad tn)"); return GGAD_E_LAUNCH; }
-    if (r > 0) return GGAD_OK;
+    if (r > 0) { gemm_note_route(GGAD_GEMM_ROUTE_WGRAD_TN, vpq); return GGAD_OK; }
   }
   // small products: both operand panels of a 32 x 32 tile in LDS for the whole K (one round trip), GGAD_GEMM_SMALL=0 turns it off
   static const bool no_small = [] { const char *e = getenv("GGAD_GEMM_SMALL"); return e && e[0] == '0'; }();
@@ -759,6 +769,7 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
     if (ok) {
       k_gemm_small<<<dim3((N + SM_T - 1) / SM_T, (M + SM_T - 1) / SM_T), dim3(256), lds, st>>>(A, B, C, (int)M, (int)N, (int)K, sam, sak, sbk, sbn, ldc,
                                                                                                   bias, (int)relu, KP);
+      gemm_note_route(GGAD_GEMM_ROUTE_SMALL, 0);
       GGAD_CHECK_LAUNCH("gemm_f32 (small)");
       return GGAD_OK;
     }
@@ -793,10 +804,12 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
       const int64_t tot = (int64_t)M * N;
       k_splitk_reduce<<<dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st>>>(workspace, splits, (int64_t)M * N, C, M, N, ldc, bias, relu);
     }
+    gemm_note_route(splits > 1 ? GGAD_GEMM_ROUTE_DMA_SPLITK : GGAD_GEMM_ROUTE_DMA, GGAD_GEMM_VARIANT_DMA(splits, nbuf == 2 ? 2 : 3));
     GGAD_CHECK_LAUNCH("gemm_f32 (dma)");
     return GGAD_OK;
   }
   if (ws_elems == 0) {
+    gemm_note_route(GGAD_GEMM_ROUTE_TILED, GGAD_GEMM_VARIANT_TILED(1, vec, tm));
     if (tm == 128)
       launch_gemm<128>(vec, a_kfast, b_nfast, dim3(gx, gy, 1), st, A, B, C, (int)M, (int)N, (int)K, (int)sam, (int)sak, (int)sbk, (int)sbn,
                        ldc, bias, (int)relu, K > 0 ? (int)K : 1, (int64_t)0);
@@ -805,6 +818,7 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
                       ldc, bias, (int)relu, K > 0 ? (int)K : 1, (int64_t)0);
   } else {
     const int splits = gemm_splits(M, N, K);
+    gemm_note_route(GGAD_GEMM_ROUTE_TILED_SPLITK, GGAD_GEMM_VARIANT_TILED(splits, vec, tm));
     int kps = (K + splits - 1) / splits;
     kps = (kps + BK - 1) / BK * BK;
     if (tm == 128)
@@ -828,10 +842,12 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
  * W: N x K (rows ldw apart), z / out: M x N (rows ldz / ldo apart). */
 int ggad_linear_prelu_f32(const float *A, int64_t lda, const float *W, int64_t ldw, const float *bias, const float *prelu_a, int32_t M,
                           int32_t N, int32_t K, float *z, int64_t ldz, float *out, int64_t ldo, ggad_stream_t stream) {
+  gemm_note_route(GGAD_GEMM_ROUTE_NONE, 0);
   GGAD_REQUIRE(A && W && prelu_a && z && out && M >= 0 && N >= 1 && K >= 1 && lda >= K && ldw >= K && ldz >= N && ldo >= N);
   if (M == 0) return GGAD_OK;
   const int r = ggad_int_gemm_slab(A, W, z, (int)M, (int)N, (int)K, lda, 1, ldw, ldz, bias, 0, as_stream(stream), prelu_a, out, ldo);
   if (r < 0) { ggad_set_error(hipErrorLaunchFailure, "linear_prelu_f32 (slab)"); return GGAD_E_LAUNCH; }
+  if (r > 0) gemm_note_route(GGAD_GEMM_ROUTE_SLAB, (K + 15) / 16);
   return r > 0 ? GGAD_OK : GGAD_E_UNSUPPORTED;
 }
 

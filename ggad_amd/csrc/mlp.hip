@@ -502,7 +502,8 @@ int64_t ggad_int_wgrad_tn_ws(int R, int m, int n) {
   if (m < 1 || n < 1 || m > 512 || n > 512 || R < 1024 || std::min(m, n) > 32) return 0;
   return (int64_t)std::min(std::max(1, R / 64), 64) * m * n + 16;
 }
-int ggad_int_wgrad_tn(const float *P, int64_t ldp, const float *Q, int64_t ldq, int R, int m, int n, float *D, float *ws, hipStream_t st) {
+int ggad_int_wgrad_tn(const float *P, int64_t ldp, const float *Q, int64_t ldq, int R, int m, int n, float *D, float *ws, hipStream_t st,
+                      int *vpq) {
   static const bool off = [] { const char *e = getenv("GGAD_GEMM_WGRAD_TN"); return e && e[0] == '0'; }();
   if (off || ggad_int_wgrad_tn_ws(R, m, n) == 0 || ((uintptr_t)ws & 15) != 0) return 0;
   WgArgs A;
@@ -513,6 +514,7 @@ int ggad_int_wgrad_tn(const float *P, int64_t ldp, const float *Q, int64_t ldq, 
   if (!((W.vp == 2 && W.vq == 4) || (W.vp == 1 && W.vq == 2) || (W.vp == 1 && W.vq == 4) || (W.vp == 2 && W.vq == 2))) { W.vp = 1; W.vq = 1; }
   W.tiles_m = (m + 16 * W.vp - 1) / (16 * W.vp);
   W.tiles_n = (n + 16 * W.vq - 1) / (16 * W.vq);
+  if (vpq) *vpq = GGAD_GEMM_VARIANT_TN(W.vp, W.vq);
   W.splits = wg_splits(R, 0, 0);
   W.task0 = 0; W.part0 = 0;
   A.n_tasks = W.tiles_m * W.tiles_n * W.splits;

@@ -574,6 +574,33 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
                   int64_t sbk, int64_t sbn, int64_t ldc, const float *bias, int32_t relu, float *workspace,
                   ggad_stream_t stream);
 
+/* Which kernel the last ggad_gemm_f32 / ggad_linear_prelu_f32 call of the CALLING THREAD chose (ABI 11): route | variant << 8.  A
+ * host-side record written when the call is made (no synchronisation; it says what was launched, not that it has finished); NONE
+ * after a call that launched nothing (M or N zero, invalid arguments, GGAD_E_UNSUPPORTED); after GGAD_E_LAUNCH it names the kernel
+ * whose launch failed, or NONE.  Variant:
+ *   SLAB / BRES            the template instance: K-steps of 16, (K + 15) / 16
+ *   WGRAD_TN               GGAD_GEMM_VARIANT_TN(vp, vq): columns per lane of the two operands
+ *   DMA / DMA_SPLITK       GGAD_GEMM_VARIANT_DMA(splits, LDS buffers): splits = 1 without split-K
+ *   TILED / TILED_SPLITK   GGAD_GEMM_VARIANT_TILED(splits, vec, tm): vec 0 per-float loads, 1 float4 loads, 2 float4 loads with the
+ *                          per-float path at the edges; tm = rows of a workgroup tile (64 or 128)
+ *   SMALL, NONE            0 */
+enum ggad_gemm_route {
+  GGAD_GEMM_ROUTE_NONE = 0,
+  GGAD_GEMM_ROUTE_SLAB = 1,            /* k_gemm_slab<KSn> */
+  GGAD_GEMM_ROUTE_BRES = 2,            /* k_gemm_bres<KSn> */
+  GGAD_GEMM_ROUTE_WGRAD_TN = 3,        /* k_mlp_wgrad + k_mlp_wgrad_reduce */
+  GGAD_GEMM_ROUTE_SMALL = 4,           /* k_gemm_small */
+  GGAD_GEMM_ROUTE_DMA = 5,             /* k_gemm_dma */
+  GGAD_GEMM_ROUTE_DMA_SPLITK = 6,      /* k_gemm_dma into the workspace + k_splitk_reduce */
+  GGAD_GEMM_ROUTE_TILED = 7,           /* k_gemm_f32 */
+  GGAD_GEMM_ROUTE_TILED_SPLITK = 8     /* k_gemm_f32 into the workspace + k_splitk_reduce */
+};
+#define GGAD_GEMM_ROUTE_PACK(route, variant) ((int32_t)(route) | (int32_t)(variant) << 8)
+#define GGAD_GEMM_VARIANT_TN(vp, vq) ((vp) << 4 | (vq))
+#define GGAD_GEMM_VARIANT_DMA(splits, bufs) ((splits) | (bufs) << 8)
+#define GGAD_GEMM_VARIANT_TILED(splits, vec, tm) ((splits) | (vec) << 8 | (tm) << 10)
+int32_t ggad_gemm_last_route(void);
+
 /* out[r] = act( sum_e val[e] * X[col[e]] + bias ) over CSR rows cut into SEGMENTS of <= ggad_spmm_seg_len()
  * consecutive entries [seg_beg, seg_end): one wave per segment, so a hub row never serialises the launch.
  * seg_out[s] >= 0: the row consists of this one segment and is finished in place (output row seg_out[s]);

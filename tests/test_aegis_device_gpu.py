@@ -85,7 +85,7 @@ def yardsticks():
 
 def test_the_library_takes_what_the_tests_assume():
     lib = load()
-    assert lib.ggad_abi_version() == 10 and lib.ggad_aegis_mb_max_rows() == MAX_ROWS >= 256
+    assert lib.ggad_abi_version() == 11 and lib.ggad_aegis_mb_max_rows() == MAX_ROWS >= 256
     assert lib.ggad_aegis_mb_supported(1, 64, 2) and lib.ggad_aegis_mb_supported(64, 64, MAX_ROWS)
     for bad in ((0, 64, 2), (65, 64, 2), (17, 32, 2), (17, 64, 1), (17, 64, MAX_ROWS + 1)):
         assert not lib.ggad_aegis_mb_supported(*bad), bad

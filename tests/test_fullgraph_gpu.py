@@ -39,10 +39,13 @@ def _adj(g):
 def test_gemm_f32_all_layouts(shape, dma, monkeypatch):
     """C = op(A) op(B) (+ bias, ReLU) on the exact-f32 matrix cores for every layout and for shapes with ragged edges, split-K
     (weight gradients: K = number of nodes), the tall products with a small second operand (M >= 4096, 244 <= K <= 320, N a sum of
-    5- and 4-tile slabs: k_gemm_slab, round 5 -- 80-column slabs of op(B) resident in LDS, both memory layouts of B, 16-byte and scalar
-    stores; M >= 2048, 128 <= K <= 320 otherwise: k_gemm_bres) and the aligned K = 300 products of the path, which take the LDS-DMA kernel (k_gemm_dma;
-    dma = "0" is decided when the library first reads GGAD_GEMM_DMA, so that run only re-checks the register-staged kernel when it is
-    the first in the process), against numpy in float64."""
+    5- and 4-tile slabs: k_gemm_slab<16>, <19>, <20>, round 5 -- 80-column slabs of op(B) resident in LDS, both memory layouts of B,
+    16-byte and scalar stores), the products of <= 1024 rows with K <= 512 (k_gemm_small), the skinny "TN" weight gradient 300 x 10 x 5000
+    (k_mlp_wgrad) and the aligned products the slab kernel does not take, which run on the LDS-DMA kernel (k_gemm_dma), the unaligned ones
+    on k_gemm_f32, against numpy in float64.  What this list does NOT reach: k_gemm_bres (M >= 16384 since round 4: the only such shape
+    here, 39357 x 300 x 300, is the slab kernel's), k_gemm_slab<2>, <4>, <17>, <18>, split-K with an empty split, and anything the
+    read-once switches select -- GGAD_GEMM_DMA is read when the library makes its first product, so dma = "0" repeats dma = "1" unless
+    it is the first GEMM of the process.  tests/test_gemm_routes_gpu.py names the kernel of every product and covers those."""
     monkeypatch.setenv("GGAD_GEMM_DMA", dma)
     m, n, k = shape
     rng = np.random.default_rng(m + n + k)

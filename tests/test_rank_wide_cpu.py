@@ -26,7 +26,7 @@ def test_the_binding_holds_the_three_entry_points():
     lib = _lib.load()
     assert int(lib.ggad_rank_wide_max_pos()) == 1 << 20
     assert int(lib.ggad_rank_metrics_max_pos()) == 8192                       # (the narrow cap stays where it is)
-    assert _lib.ABI_VERSION == 10
+    assert _lib.ABI_VERSION == 11
 
 
 def test_workspace_elems():

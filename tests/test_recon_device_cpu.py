@@ -56,7 +56,7 @@ def test_dead_column_has_a_finite_float64_gradient():
 
 def test_entry_points_refuse_bad_arguments_without_a_launch():
     lib = _lib.load()
-    assert lib.ggad_abi_version() == 10
+    assert lib.ggad_abi_version() == 11
     assert lib.ggad_recon_mb_max_rows(17) >= 256 and lib.ggad_recon_mb_max_rows(32) >= 256 and lib.ggad_recon_mb_max_rows(64) >= 150
     assert lib.ggad_recon_mb_max_rows(0) == 0 and lib.ggad_recon_mb_max_rows(65) == 0
     assert lib.ggad_recon_mb_supported(1, 64, 1) and lib.ggad_recon_mb_supported(64, 64, lib.ggad_recon_mb_max_rows(64))

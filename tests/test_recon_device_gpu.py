@@ -129,7 +129,7 @@ def _judge(tag, got, yard, want, keys, capsys, finite_yard=None, masks=None):
 
 def test_the_library_takes_what_the_tests_assume():
     lib = load()
-    assert lib.ggad_abi_version() == 10
+    assert lib.ggad_abi_version() == 11
     assert _max_rows(17) >= 256 and _max_rows(32) >= 256 and _max_rows(64) >= 150
     assert lib.ggad_recon_mb_supported(1, 64, 1) and lib.ggad_recon_mb_supported(64, 64, _max_rows(64))
     assert not lib.ggad_recon_mb_supported(64, 64, _max_rows(64) + 1) and not lib.ggad_recon_mb_supported(17, 32, 48)
