@@ -233,7 +233,7 @@ class BatchChunk:
                 self.stage_host = self.stage_host.pin_memory()
             self.stage = _i32(self.stage_cap, d)
         if self.train and self.hop2 == "ldsw":
-            if pairs > self.pair_cap:
+            if pairs > self.pair_cap or self.pc is None:      # (a chunk of isolated nodes has no pair, and still hands pc[] over)
                 self.pair_cap = int(pairs * 1.25) + 1024
                 self.pc = torch.empty(self.pair_cap, dtype=torch.int16, device=d)      # uint16 per-pair counts (raw storage)
             if items > self.item_cap:

@@ -15,6 +15,7 @@ import torch
 
 from ggad_amd import synth
 from oracle import ggad_oracle as O
+import plan_counts_ref
 import step_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +89,16 @@ def test_sampled_batches_of_the_full_size_chunk_against_the_oracle(full):
         ref = np.concatenate([t.grad.numpy().reshape(-1) for t in p.tensors()])
         np.testing.assert_allclose(eng.grads.cpu().numpy(), ref, atol=5e-6, rtol=5e-5)
         np.testing.assert_allclose(eng.losses(slot + 1)[slot], [tot.item(), cls.item(), mar.item(), rec.item()], atol=2e-5)
+
+
+def test_plan_integers_of_the_full_size_chunk_are_exact(full):
+    """pc (the 2-hop counts c'_k), own_deg, own_rp and seg_t of the sampled batches 0, 61 and 149 and the counters of the whole
+    150-batch chunk, exact (tests/plan_counts_ref.py).  n_tiles + 1 = 114 here: the only place where the second 64-tile half of
+    a k_seg_transpose slab runs."""
+    ch = full["ch"]
+    assert plan_counts_ref.n_tiles_of(N) + 1 == 114 and ch.last_hop2 == "ldsw"
+    plan_counts_ref.assert_plan_integers_exact(ch, full["rowptr"], full["col"], full["batches"], plan_counts_ref.effective_range_deg(0),
+                                               only_batches=(0, 61, 149))
 
 
 def test_resident_kernel_on_sampled_full_size_batches_against_float64(full):

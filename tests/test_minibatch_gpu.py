@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import plan_counts_ref
 from conftest import load_golden
 from ggad_amd import synth
 
@@ -43,8 +44,10 @@ def test_exclusive_scan(n):
     assert np.array_equal(out.cpu().numpy().astype(np.int64), ref)
 
 
-def _check_plan_against_oracle(g, ch, batches, feat_np, atol=2e-6):
+def _check_plan_against_oracle(g, ch, batches, feat_np, atol=2e-6, range_option=0):
     rp, ci = g["rowptr"], g["col"]
+    if ch.last_hop2 == "ldsw":      # the integers behind x2, exact (range_option: what ggad_mb_set_gather_options had at the build)
+        plan_counts_ref.assert_plan_integers_exact(ch, rp, ci, batches, plan_counts_ref.effective_range_deg(range_option))
     ent_ptr = ch.ent_ptr[:ch.n_rows + 1].cpu().numpy()
     etot = int(ent_ptr[-1])
     assert np.array_equal(ent_ptr, ch.ent_ptr_host)          # host-side exact entry offsets == device scan
@@ -541,7 +544,7 @@ def test_ldsw_node_major_gather_against_per_owner_kernel(stride, mfma, ranges):
         outs.append((ch.ent_col[own].clone(), torch.div(own, 1, rounding_mode="floor"), ch.x2.view(-1, 17)[own].clone()))
         if nm:
             assert int(ch.node_head.abs().sum()) == 0
-            _check_plan_against_oracle(g, ch, batches, feat, atol=5e-6)
+            _check_plan_against_oracle(g, ch, batches, feat, atol=5e-6, range_option=256 if ranges else 0)
     # owner election is a race between duplicate entries, so compare per (batch, node): sort owners by (entry range, column)
     def keyed(cols, ents, x, chunk):
         b = torch.bucketize(ents, torch.as_tensor(chunk.ent_ptr_host[chunk.batch_ptr_host][1:], device=DEV), right=True)
