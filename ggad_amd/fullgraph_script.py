@@ -72,6 +72,102 @@ def parse_with_defaults(p, argv, lr, epochs, fallback=None):
     return a
 
 
+def add_select_options(p):
+    """`--select` / `--save` / `--score` / `--top_k` / `--top_k_out`: keep the epoch with the best validation metric (ggad_amd.select),
+    write a checkpoint, score a graph from one and rank its test nodes.  All off by default, and an option that is not given leaves NO
+    attribute behind (`argparse.SUPPRESS`): the namespace of a command line without them is the one the script had before they existed
+    (tests/test_fullgraph_script_cpu.py pins it), and a caller's hand-made namespace needs none of them.  Read them with
+    `select_options`; `check_select_options` after parsing."""
+    off = argparse.SUPPRESS
+    p.add_argument("--select", choices=["auroc", "ap"], default=off,
+                   help="validate every epoch on idx_val inside the (captured) epoch and keep the weights of the epoch with the best "
+                        "AUROC / AP on the device; the training trajectory is unchanged")
+    p.add_argument("--save", type=str, default=off, metavar="PATH",
+                   help="write the weights to PATH (torch.save): the best epoch's with --select, else the last epoch's")
+    p.add_argument("--score", type=str, default=off, metavar="CKPT",
+                   help="no training: load the weights of CKPT (written by --save), score the graph and report on idx_test")
+    p.add_argument("--top_k", type=int, default=off, help="with --score: rank the K highest-scoring test nodes (precision / recall @ K)")
+    p.add_argument("--top_k_out", type=str, default=off, metavar="F.npz", help="with --score --top_k K: write the ranked list to F.npz")
+    return p
+
+
+def select_options(a):
+    """(select, save, score, top_k, top_k_out) of a namespace, with what "not given" means: None, None, None, 0, ""."""
+    return (getattr(a, "select", None), getattr(a, "save", None), getattr(a, "score", None), int(getattr(a, "top_k", 0) or 0),
+            str(getattr(a, "top_k_out", "") or ""))
+
+
+def check_select_options(p, a):
+    select, save, score, top_k, top_k_out = select_options(a)
+    if score and select:
+        p.error("--score does no training: it cannot be combined with --select")
+    if score and save:
+        p.error("--score does no training: there is nothing for --save to write")
+    if (top_k or top_k_out) and not score:
+        p.error("--top_k / --top_k_out rank the scores of --score CKPT")
+    if top_k < 0 or (top_k_out and not top_k):
+        p.error("--top_k_out needs --top_k K with K > 0")
+    return a
+
+
+# ------------------------------------------------------------------------------------------------ checkpoints
+def save_checkpoint(path, state_dict, args, n_in, nodes, epoch, value=None):
+    """`torch.save({"state_dict", "meta"})`: the model's own state_dict (host copies; for `run.py` the reference's key names, so the
+    reference's `Model` loads it) and what a later `--score` checks or reports.  `epoch`: the epoch the weights are from; `value`: the
+    validation metric `--select` chose them by (None without)."""
+    meta = {"dataset": args.dataset, "n_in": int(n_in), "embedding_dim": int(args.embedding_dim), "nodes": int(nodes), "seed": int(args.seed),
+            "epoch": int(epoch), "select": getattr(args, "select", None), "value": None if value is None else float(value)}
+    torch.save({"state_dict": type(state_dict)((k, v.detach().cpu().clone()) for k, v in state_dict.items()), "meta": meta}, path)
+    return meta
+
+
+def load_checkpoint(path, n_in, embedding_dim):
+    """The dict `save_checkpoint` wrote (tensors on the host).  Weights made for another `n_in` or `embedding_dim`: `ValueError` naming
+    both values of each."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ck, dict) or "state_dict" not in ck or "meta" not in ck:
+        raise ValueError("{}: not a checkpoint written by --save (no 'state_dict' / 'meta')".format(path))
+    meta = ck["meta"]
+    if int(meta["n_in"]) != int(n_in) or int(meta["embedding_dim"]) != int(embedding_dim):
+        raise ValueError("{}: the checkpoint was written for n_in = {}, embedding_dim = {}; this graph and command line give n_in = {}, "
+                         "embedding_dim = {}".format(path, meta["n_in"], meta["embedding_dim"], int(n_in), int(embedding_dim)))
+    return ck
+
+
+def score_from_checkpoint(args, model, score_fn, n_in, idx_test, ano_label, dev):
+    """`--score CKPT [--top_k K] [--top_k_out F.npz]`: load CKPT into `model` (strict), `score_fn()` -> the (N,) float32 device scores
+    of all nodes (no training, no noise draw), the reference's two evaluation lines on `idx_test`, and -- with `--top_k` -- the K
+    highest-scoring test nodes through `metrics.top_k`: precision / recall @ K printed, the list written by `write_ranked`.  Returns
+    (scores, auc, ap, ranked or None)."""
+    from .metrics import check_k, precision_recall_at, top_k, write_ranked
+    _, _, path, k, k_out = select_options(args)
+    if k:
+        check_k(k, "--top_k")                                                   # before anything is loaded or scored
+    ck = load_checkpoint(path, n_in, args.embedding_dim)
+    model.load_state_dict(ck["state_dict"], strict=True)
+    model.eval()
+    meta = ck["meta"]
+    print("scoring with {} (dataset {}, epoch {}, select {}, value {})".format(path, meta["dataset"], meta["epoch"], meta["select"],
+                                                                               meta["value"]))
+    scores = score_fn()
+    idx = np.asarray(idx_test, dtype=np.int64)
+    idx_dev = torch.as_tensor(idx, device=dev)
+    y = np.asarray(ano_label).reshape(-1)[idx]
+    test_scores = scores.index_select(0, idx_dev)
+    auc, ap = print_eval(args.dataset, test_scores, torch.as_tensor(y.astype(np.int64), device=dev))
+    ranked = None
+    if k:
+        y8 = y.astype(np.uint8)
+        ranked = top_k(test_scores, k, torch.from_numpy(y8).to(dev), idx_dev)
+        prec, rec = precision_recall_at(ranked, ranked.m)
+        print("top {} of {} test nodes: precision@{} {:.4f} recall@{} {:.4f} ({} positives among the test nodes, {} tied with the last "
+              "rank left out)".format(ranked.m, idx.size, ranked.m, prec, ranked.m, rec, ranked.n_pos, ranked.tied_left_out))
+        if k_out:
+            write_ranked(k_out, ranked, y8)
+            print("ranked list written to", k_out)
+    return scores, auc, ap, ranked
+
+
 # ------------------------------------------------------------------------------------------------ data
 class Graph(NamedTuple):
     """What the reference's `load_mat` returns, less what no script reads."""
@@ -228,12 +324,13 @@ def print_captured():
     print("training epoch captured as a hipGraph", flush=True)
 
 
-def print_eval(dataset, scores, y):
-    """The reference's two evaluation lines (= sklearn's roc_auc_score / average_precision_score); returns (auc, ap)."""
+def print_eval(dataset, scores, y, prefix=""):
+    """The reference's two evaluation lines (= sklearn's roc_auc_score / average_precision_score); returns (auc, ap).  `prefix`: put
+    in front of both, for evaluations the reference does not make (so that they cannot be mistaken for its lines)."""
     auc = roc_auc(scores, y)
-    print("Testing {} AUC:{:.4f}".format(dataset, auc))
+    print("{}Testing {} AUC:{:.4f}".format(prefix, dataset, auc))
     ap = average_precision(scores, y)
-    print("Testing AP:", ap)
+    print("{}Testing AP:".format(prefix), ap)
     return auc, ap
 
 

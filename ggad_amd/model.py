@@ -148,6 +148,18 @@ class Model(nn.Module):
         f = LinearFn.apply(f, self.fc2.weight, True)                       # fc2 + relu     :178-179
         return LinearFn.apply(f, self.fc3.weight, False)                   # fc3            :180
 
+    def score(self, seq1, adj):
+        """(N,) float32 logits of all nodes: the two GCN layers and the scorer of `forward(..., train_flag=False)`, the same kernels in
+        the same order, so bit for bit that call's `f_3[0, :, 0]` -- without its noise draw, which in evaluation mode only reaches
+        `emb_abnormal` and never the scores: neither the CPU generator nor a `DeviceMT` moves.  No autograd graph."""
+        dev = self.fc1.weight.device
+        with torch.no_grad():
+            fa = as_full_adj(adj, dev)
+            x = seq1.reshape(-1, seq1.shape[-1]).to(dev)
+            h_1 = GcnLayerFn.apply(x, self.gcn1.fc.weight, self.gcn1.bias, self.gcn1.act.weight, fa)
+            emb = GcnLayerFn.apply(h_1, self.gcn2.fc.weight, self.gcn2.bias, self.gcn2.act.weight, fa)
+            return self._score(emb).reshape(-1)
+
     def forward(self, seq1, adj, sample_abnormal_idx, normal_idx, train_flag, args, sparse=False):
         dev = self.fc1.weight.device
         fa = as_full_adj(adj, dev)

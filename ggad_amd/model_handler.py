@@ -41,6 +41,7 @@ import torch.nn as nn
 from .graph import DeviceGraph
 from .graphsage import GCN, Encoder, FeatureTable, GCNAggregator, GCNEncoder, GraphSage, MeanAggregator
 from .handler_loop import BestCheckpoint, device_graph, load_and_split, sweep_report, train_labelled
+from .metrics import write_ranked  # noqa: F401  (it lives beside `top_k`; re-exported: callers import it from here)
 from .sage_utils import score_nodes, test_sage
 from .sampler import PyCompatRandom
 from .trainer import BatchSchedule, DGraphTrainer
@@ -57,23 +58,6 @@ def _autograd_step(gnn_model, optimizer):
         optimizer.step()
         return out
     return step
-
-
-def write_ranked(path, ranked, labels=None):
-    """The `.npz` of config key `top_k_out`: `node` int64, `score` float32, `label` uint8, `cum_positives` int32 (both empty without
-    labels), `n_pos`, `tied_left_out`.  `labels`: the labels of the scored list, indexed by `ranked.pos`.  Entries are stored with a
-    fixed date, so equal rankings give equal files byte for byte."""
-    import zipfile
-    pos = ranked.pos.cpu().numpy()
-    has = labels is not None and ranked.cum_pos is not None
-    arrays = {"node": ranked.ids.cpu().numpy().astype(np.int64), "score": ranked.scores.cpu().numpy().astype(np.float32),
-              "label": np.asarray(labels).reshape(-1)[pos].astype(np.uint8) if has else np.zeros(0, dtype=np.uint8),
-              "cum_positives": ranked.cum_pos.cpu().numpy().astype(np.int32) if has else np.zeros(0, dtype=np.int32),
-              "n_pos": np.int64(ranked.n_pos), "tied_left_out": np.int64(ranked.tied_left_out)}
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
-        for name, a in arrays.items():
-            with z.open(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w", force_zip64=True) as fh:
-                np.lib.format.write_array(fh, np.asanyarray(a), allow_pickle=False)
 
 
 def _report_sage(epoch, means, epoch_time):

@@ -1215,6 +1215,27 @@ int64_t ggad_rank_wide_workspace_elems(int64_t n, int64_t pos_cap);   /* int32 e
 int ggad_rank_wide_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, double *out8,
                        int32_t *workspace, ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Keep the best epoch's weights on the device (select.hip): the hand-off "if this epoch's validation metric is the best so far,
+ * snapshot the parameters" without a host round trip.  Neither call takes a workspace; each reads only words the host or an earlier
+ * launch wrote, so both are capturable and replayable behind ggad_rank_metrics_f32 / ggad_rank_wide_f32 in a captured epoch.
+ *
+ * ggad_select_decide_f64: one tiny launch.  out8 = what the rank metrics wrote; which = 0 AUROC, 1 AP (anything else: GGAD_E_INVALID,
+ *   no launch); state4 (device, 4 doubles) = {best_value, best_epoch, epoch, taken}, initialised by the host to {NaN, -1, 0, 0}.  With
+ *   e = epoch: if curve != NULL and e < curve_cap, curve[3e .. 3e+2] = {auroc, ap, status}; taken = (status == 0 && value == value &&
+ *   (best_epoch < 0 || value > best_value)) -- strict > in double, an equal later epoch never displaces an earlier one --; if taken,
+ *   best_value = value and best_epoch = e; epoch = e + 1.
+ * ggad_select_copy_f32: copies src[i] -> dst[i] (numel[i] floats each, i < n) in full if and only if state4[3] == 1, and writes nothing
+ *   otherwise.  src / dst / numel are HOST arrays (as in ggad_adam_multi_f32), 1 <= n <= ggad_select_max_tensors() (16), every pointer
+ *   4-byte aligned; outside: GGAD_E_INVALID and no launch.  16-byte accesses where source and destination share their offset within a
+ *   16-byte line (the first and last 0..3 floats apart), 4-byte accesses otherwise; dst is never read.  It is a launch of its own so
+ *   that no workgroup reads a word another one writes: a model of more than 16 tensors is copied in groups after ONE decide.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_select_max_tensors(void);
+int ggad_select_decide_f64(const double *out8, int32_t which, double *state4, double *curve, int64_t curve_cap, ggad_stream_t stream);
+int ggad_select_copy_f32(int32_t n, const float *const *src, float *const *dst, const int64_t *numel, const double *state4,
+                         ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

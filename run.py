@@ -9,6 +9,10 @@ reconstruction loss, backward, Adam -- runs in the HIP kernels of libggad_hip.so
 instead of the reference's dense N x N tensors).  Extra flags: `--synthetic` (no dataset ships with this repo:
 builds a graph of the dataset's published size from the seed), `--device`, `--device_noise` (opt-in: the N(mean, var)
 noise is drawn on the device from torch's own CPU stream, `ggad_amd/rng.py`; the draw opens the captured epoch).
+`--select auroc|ap` (opt-in): every epoch ends with a noise-free scoring forward, the validation AUROC / AP on idx_val and a
+conditional snapshot of the weights, all on the device and inside the captured epoch (`ggad_amd/select.py`); the trajectory and
+the CPU generator are untouched.  `--save PATH` writes the weights (the best epoch's with `--select`, else the last epoch's),
+`--score PATH [--top_k K] [--top_k_out F.npz]` scores the graph from such a file without training and ranks its test nodes.
 """
 import os
 import sys
@@ -19,8 +23,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ggad_amd.fullgraph import FlatAdam, ggad_loss  # noqa: E402
-from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, init_process, load_graph, make_parser, parse_with_defaults,  # noqa: E402,F401
-                                       prepare, print_captured, print_eval, print_median)
+from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, add_select_options, check_select_options, init_process, load_graph,  # noqa: E402,F401
+                                       make_parser, parse_with_defaults, prepare, print_captured, print_eval, print_median,
+                                       save_checkpoint, score_from_checkpoint, select_options)
 from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
 from ggad_amd.model import Model  # noqa: E402
 
@@ -35,7 +40,8 @@ def parse(argv=None):
                                       "becomes the first node of the captured epoch; values agree with the host's to float32 rounding")
     p.add_argument("--mean", type=float, default=0.0)
     p.add_argument("--var", type=float, default=0.0)
-    a = parse_with_defaults(p, argv, {}, EPOCHS, fallback=(1e-3, 100))
+    add_select_options(p)
+    a = check_select_options(p, parse_with_defaults(p, argv, {}, EPOCHS, fallback=(1e-3, 100)))
     a.mean, a.var = (0.02, 0.01) if a.dataset in ["reddit", "photo"] else (0.0, 0.0)      # run.py:61-66 (CLI values overwritten)
     return a
 
@@ -45,18 +51,25 @@ def load(args):
     return g.adj, g.feat, g.ano_label, g.idx_test, g.normal_idx, g.abn_idx
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    """Train (returns None) or, with `--score`, score from a checkpoint (returns the (N,) float32 scores of all nodes)."""
+    args = parse(argv)
     print("Dataset: ", args.dataset)
     dev = init_process(args, "run.py", why="the GGAD hot path has no CPU fallback")
-    adj, features, ano_label, idx_test, normal_label_idx, abnormal_label_idx = load(args)
-    print(adj.sum())
-    full, feats, ft_size = prepare(args, adj, features, dev)
+    g = load_graph(args)
+    print(g.adj.sum())
+    full, feats, ft_size = prepare(args, g.adj, g.feat, dev)
     model = Model(ft_size, args.embedding_dim, "prelu", args.negsamp_ratio, args.readout).to(dev)
-    fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label)
+    if select_options(args)[2]:
+        try:
+            scores = score_from_checkpoint(args, model, lambda: model.score(feats, full), ft_size, g.idx_test, g.ano_label, dev)[0]
+        except ValueError as exc:
+            sys.exit("run.py --score: {}".format(exc))
+        return scores.cpu().numpy()
+    fit(args, dev, full, feats, model, g.normal_idx, g.abn_idx, g.idx_test, g.ano_label, idx_val=g.idx_val)
 
 
-def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history=None):
+def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history=None, idx_val=None):
     """`_fit`, on the host's noise (the default) or -- `args.device_noise`, or GGAD_DEVICE_NOISE=1 where `args` does not say -- with the
     CPU generator continued on the device (ggad_amd.rng): snapshotted before the first epoch, handed back when the loop ends, also
     on an exception."""
@@ -64,25 +77,42 @@ def fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx
     if device_noise is None:
         device_noise = os.environ.get("GGAD_DEVICE_NOISE", "0") == "1"
     if not device_noise:
-        return _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history)
+        return _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history, idx_val=idx_val)
     from ggad_amd.rng import DeviceMT
     mt = DeviceMT.from_host(dev)
     model.device_noise = mt
     if history is not None:
         history["noise"] = "device"
     try:
-        return _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history, mt)
+        return _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history, mt, idx_val=idx_val)
     finally:
         model.device_noise = model.noise_override = None
         mt.to_host()
 
 
-def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history=None, device_mt=None):
+def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, idx_test, ano_label, history=None, device_mt=None,
+         idx_val=None):
     """The training loop of the reference's script (`run.py:137-240`): Adam, `num_epoch` epochs, an evaluation forward (which draws
     noise too, quirk 5) every 10th epoch.  `history` (a dict, tests / the end-of-training parity report): filled with the four loss
     terms of every epoch, the AUROC / AP of every evaluation, and -- one extra evaluation after the last epoch, which the reference
-    does not run -- the final scores of all nodes."""
+    does not run -- the final scores of all nodes.
+
+    `args.select` ("auroc" / "ap"; needs `idx_val`): every epoch ends, after the optimiser step and inside the captured epoch, with
+    `Model.score` (no noise draw) and `BestKeeper.step` -- validation AUROC / AP on `idx_val` as exact counts, the decision and the
+    conditional snapshot of the weights, launches only.  Nothing of the training reads what they write, so losses, weights and the CPU
+    generator are those of a run without it.  After the loop (and after everything a run without it does) the best epoch is printed,
+    its weights are loaded into `model` and evaluated on `idx_test`; `history` gains `val_curve` ((epochs, 3): AUROC, AP, status),
+    `best_epoch`, `best_value`, `best_scores` (all N logits under the best weights), `best_auc` / `best_ap` (on `idx_test`) and
+    `last_params` (the last epoch's weights, which `model` no longer holds).  `args.save`: the weights `model` ends with are written."""
     nb_nodes = feats.shape[1]
+    select, save = select_options(args)[:2]
+    keeper = None
+    if select:
+        if idx_val is None:
+            raise ValueError("--select validates on idx_val: pass fit(..., idx_val=...)")
+        from ggad_amd.select import BestKeeper
+        rows = np.asarray(idx_val, dtype=np.int64)
+        keeper = BestKeeper(list(model.parameters()), args.num_epoch, select, labels_u8=np.asarray(ano_label).reshape(-1)[rows], rows=rows)
     optimiser = FlatAdam(model.parameters(), lr=args.lr, weight_decay=args.weight_decay)
     ls = full.loss_structs(normal_label_idx, abnormal_label_idx)
     idx_test_dev = torch.as_tensor(np.asarray(idx_test, dtype=np.int64), device=dev)
@@ -109,6 +139,8 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
         out = ggad_loss(emb, logits, emb_con, emb_abnormal, full, ls, 0.7)
         out[0].backward(gradient=one)            # (d loss / d loss = 1 from a kept tensor: autograd would fill a new one every epoch)
         optimiser.step()
+        if keeper is not None:                   # the last launches of the epoch: score, validate, keep the weights if they are the best
+            keeper.step(model.score(feats, full))
         return tuple(t.detach() for t in out)
 
     def before_capture():
@@ -172,6 +204,27 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
         history["captured"] = cap.captured
     print("nodes/s (training window, run.py:146->214): {:.1f}".format(nb_nodes * args.num_epoch / total_time))
     print_median(epoch_times, nb_nodes, "one-off plan building / module load")
+    best_epoch, best_value = args.num_epoch - 1, None
+    if keeper is not None:
+        curve, best_epoch, best_value = keeper.curve(), keeper.best_epoch, keeper.best_value
+        if history is not None:
+            history["val_curve"], history["best_epoch"], history["best_value"] = curve, best_epoch, best_value
+            history["last_params"] = [p.detach().cpu().clone() for p in model.parameters()]
+        if best_epoch < 0:
+            raise RuntimeError("--select {}: no epoch had a defined validation metric (statuses {}): is one class missing from idx_val?"
+                               .format(select, sorted(set(curve[:, 2].tolist()))))
+        print("[select] best epoch {:04d} by validation {}: validation AUC:{:.4f} AP: {}".format(
+            best_epoch, select, curve[best_epoch, 0], curve[best_epoch, 1]))
+        keeper.load_into(model)
+        model.eval()
+        best_scores = model.score(feats, full)
+        auc, ap = print_eval(args.dataset, best_scores.index_select(0, idx_test_dev), y_test_dev, prefix="[select] best epoch: ")
+        if history is not None:
+            history["best_scores"], history["best_auc"], history["best_ap"] = best_scores.cpu().numpy(), auc, ap
+    if save:
+        state = keeper.state_dict(model) if keeper is not None else model.state_dict()
+        save_checkpoint(save, state, args, feats.shape[2], nb_nodes, best_epoch, best_value)
+        print("weights of epoch {:04d} written to {}".format(best_epoch, save))
 
 
 if __name__ == "__main__":
