@@ -280,6 +280,9 @@ SIGNATURES = {
     "ggad_topk_max_k": (c_int32, []),
     "ggad_topk_workspace_elems": (c_int64, [_L, _I]),
     "ggad_topk_f32": (c_int32, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
+    "ggad_topk_wide_max_k": (c_int32, []),
+    "ggad_topk_wide_workspace_elems": (c_int64, [_L, _I]),
+    "ggad_topk_wide_f32": (c_int32, [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P]),
     "ggad_rank_wide_max_pos": (c_int32, []),
     "ggad_rank_wide_workspace_elems": (c_int64, [_L, _L]),
     "ggad_rank_wide_f32": (c_int32, [_P, _P, _L, _L, _F, _P, _P, _P]),

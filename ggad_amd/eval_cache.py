@@ -107,8 +107,9 @@ class ResidentSweep:
             return rank_report_wide(scores, self.labels, thres, pos_cap=min(self.n_pos, int(self.engine.lib.ggad_rank_wide_max_pos())))
         return rank_report(scores, self.labels, thres)
 
-    def top_k(self, k: int, scores: torch.Tensor = None):
+    def top_k(self, k: int, scores: torch.Tensor = None, wide: bool = False):
         """`metrics.top_k` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) with the
-        sweep's ids and resident labels: the `Ranked` head of the list, `ids` = node ids.  Nothing is uploaded and no plan is built."""
+        sweep's ids and resident labels: the `Ranked` head of the list, `ids` = node ids.  Nothing is uploaded and no plan is built.
+        `wide`: `metrics.top_k(..., wide=True)`, k above 16,384 up to a full ranking of the list."""
         from .metrics import top_k
-        return top_k(self.scores() if scores is None else scores, k, self.labels, self.ids)
+        return top_k(self.scores() if scores is None else scores, k, self.labels, self.ids, wide=wide)

@@ -73,7 +73,7 @@ def parse_with_defaults(p, argv, lr, epochs, fallback=None):
 
 
 def add_select_options(p):
-    """`--select` / `--save` / `--score` / `--top_k` / `--top_k_out`: keep the epoch with the best validation metric (ggad_amd.select),
+    """`--select` / `--save` / `--score` / `--top_k` / `--top_k_out` / `--top_k_wide`: keep the epoch with the best validation metric (ggad_amd.select),
     write a checkpoint, score a graph from one and rank its test nodes.  All off by default, and an option that is not given leaves NO
     attribute behind (`argparse.SUPPRESS`): the namespace of a command line without them is the one the script had before they existed
     (tests/test_fullgraph_script_cpu.py pins it), and a caller's hand-made namespace needs none of them.  Read them with
@@ -88,6 +88,8 @@ def add_select_options(p):
                    help="no training: load the weights of CKPT (written by --save), score the graph and report on idx_test")
     p.add_argument("--top_k", type=int, default=off, help="with --score: rank the K highest-scoring test nodes (precision / recall @ K)")
     p.add_argument("--top_k_out", type=str, default=off, metavar="F.npz", help="with --score --top_k K: write the ranked list to F.npz")
+    p.add_argument("--top_k_wide", action="store_true", default=off,
+                   help="with --score --top_k K: rank through csrc/topk_wide.hip, K above 16384 up to 4194304 (a whole test split)")
     return p
 
 
@@ -97,8 +99,15 @@ def select_options(a):
             str(getattr(a, "top_k_out", "") or ""))
 
 
+def top_k_wide_option(a):
+    """`--top_k_wide` of a namespace (False when not given); apart from `select_options`, whose five values callers unpack."""
+    return bool(getattr(a, "top_k_wide", False))
+
+
 def check_select_options(p, a):
     select, save, score, top_k, top_k_out = select_options(a)
+    if top_k_wide_option(a) and not top_k:
+        p.error("--top_k_wide chooses the kernels of --top_k K: it needs --top_k K with K > 0")
     if score and select:
         p.error("--score does no training: it cannot be combined with --select")
     if score and save:
@@ -135,14 +144,15 @@ def load_checkpoint(path, n_in, embedding_dim):
 
 
 def score_from_checkpoint(args, model, score_fn, n_in, idx_test, ano_label, dev):
-    """`--score CKPT [--top_k K] [--top_k_out F.npz]`: load CKPT into `model` (strict), `score_fn()` -> the (N,) float32 device scores
+    """`--score CKPT [--top_k K] [--top_k_out F.npz] [--top_k_wide]`: load CKPT into `model` (strict), `score_fn()` -> the (N,) float32 device scores
     of all nodes (no training, no noise draw), the reference's two evaluation lines on `idx_test`, and -- with `--top_k` -- the K
     highest-scoring test nodes through `metrics.top_k`: precision / recall @ K printed, the list written by `write_ranked`.  Returns
     (scores, auc, ap, ranked or None)."""
     from .metrics import check_k, precision_recall_at, top_k, write_ranked
     _, _, path, k, k_out = select_options(args)
+    wide = top_k_wide_option(args)
     if k:
-        check_k(k, "--top_k")                                                   # before anything is loaded or scored
+        check_k(k, "--top_k", wide=wide)                                        # before anything is loaded or scored
     ck = load_checkpoint(path, n_in, args.embedding_dim)
     model.load_state_dict(ck["state_dict"], strict=True)
     model.eval()
@@ -158,7 +168,7 @@ def score_from_checkpoint(args, model, score_fn, n_in, idx_test, ano_label, dev)
     ranked = None
     if k:
         y8 = y.astype(np.uint8)
-        ranked = top_k(test_scores, k, torch.from_numpy(y8).to(dev), idx_dev)
+        ranked = top_k(test_scores, k, torch.from_numpy(y8).to(dev), idx_dev, wide=wide)
         prec, rec = precision_recall_at(ranked, ranked.m)
         print("top {} of {} test nodes: precision@{} {:.4f} recall@{} {:.4f} ({} positives among the test nodes, {} tied with the last "
               "rank left out)".format(ranked.m, idx.size, ranked.m, prec, ranked.m, rec, ranked.n_pos, ranked.tied_left_out))

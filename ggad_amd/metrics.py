@@ -15,7 +15,8 @@ no full sort (only the positives are sorted), four launches and ONE read-back.  
 
 `top_k` is the ranked list: the k highest scores in a FIXED order (score descending, equal scores by ascending position; the head
 of a saturated sigmoid ranking is full of exact ties, and `torch.topk` fixes neither which tied elements it returns nor their
-order), with the running count of positives beside it, from `ggad_topk_f32` (csrc/topk.hip): six launches and ONE read-back."""
+order), with the running count of positives beside it, from `ggad_topk_f32` (csrc/topk.hip): six launches and ONE read-back.  `top_k(..., wide=True)` is the same list for more than the
+16,384 ranks one workgroup sorts, up to 4,194,304, through `ggad_topk_wide_f32` (csrc/topk_wide.hip)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -166,11 +167,14 @@ class Ranked:
     tied_left_out: int
 
 
-def top_k(scores: torch.Tensor, k: int, labels_u8: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None) -> Ranked:
+def top_k(scores: torch.Tensor, k: int, labels_u8: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None,
+          wide: bool = False) -> Ranked:
     """The `min(k, n)` highest of float32 device `scores`, ranked by score descending and, among equal scores, by ascending position
     (-0.0 ties with +0.0): one `ggad_topk_f32` call and one read-back of its four meta words.  `labels_u8` (uint8, same shape):
     `cum_pos` and `n_pos` are filled.  `ids` (int64, same shape): `Ranked.ids = ids[pos]`.  A NaN score, a label other than 0/1 or a
-    `k` outside 1..ggad_topk_max_k(): `ValueError`."""
+    `k` outside 1..ggad_topk_max_k(): `ValueError`.  `wide=True`: `ggad_topk_wide_f32` (csrc/topk_wide.hip: the candidates sorted in
+    runs of 2,048 and merged), k up to ggad_topk_wide_max_k() = 4,194,304; the same list, and the same bits where both routes serve.
+    Timings of both against a torch sort: profiles/topk_wide_time_line.json."""
     from . import _lib
     if scores.dtype != torch.float32 or scores.dim() != 1:
         raise ValueError("top_k takes float32 scores of a 1-D shape")
@@ -181,19 +185,20 @@ def top_k(scores: torch.Tensor, k: int, labels_u8: Optional[torch.Tensor] = None
     if ids is not None and (ids.shape != scores.shape or ids.device != scores.device):
         raise ValueError("top_k takes ids of the scores' shape on the same GPU")
     lib = _lib.load()
-    check_k(k, "top_k", lib)
+    check_k(k, "top_k", lib, wide)
     k = int(k)
+    entry = "ggad_topk_wide" if wide else "ggad_topk"
     n = scores.numel()
     scores = scores.contiguous()
     labels_u8 = labels_u8.contiguous() if labels_u8 is not None else None
     dev = scores.device
     with torch.cuda.device(dev):
-        ws = torch.empty(int(lib.ggad_topk_workspace_elems(n, k)), dtype=torch.int32, device=dev)
+        ws = torch.empty(int(getattr(lib, entry + "_workspace_elems")(n, k)), dtype=torch.int32, device=dev)
         pos = torch.empty(k, dtype=torch.int32, device=dev)
         val = torch.empty(k, dtype=torch.float32, device=dev)
         cum = torch.empty(k, dtype=torch.int32, device=dev) if labels_u8 is not None else None
         meta = torch.empty(4, dtype=torch.int64, device=dev)
-        _lib.call("ggad_topk_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, k, _lib.ptr(pos), _lib.ptr(val), _lib.ptr(cum),
+        _lib.call(entry + "_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, k, _lib.ptr(pos), _lib.ptr(val), _lib.ptr(cum),
                   _lib.ptr(meta), _lib.ptr(ws))
         m, status, n_pos, left = (int(v) for v in meta.cpu().tolist())
     if status == 3:
@@ -201,15 +206,21 @@ def top_k(scores: torch.Tensor, k: int, labels_u8: Optional[torch.Tensor] = None
     if status == 4:
         raise ValueError("top_k: a label is neither 0 nor 1")
     pos = pos[:m]
-    wide = pos.long()
-    return Ranked(pos=pos, ids=ids.long()[wide] if ids is not None else wide, scores=val[:m], cum_pos=cum[:m] if cum is not None else None,
+    pos64 = pos.long()
+    return Ranked(pos=pos, ids=ids.long()[pos64] if ids is not None else pos64, scores=val[:m], cum_pos=cum[:m] if cum is not None else None,
                   m=m, n_pos=n_pos, tied_left_out=left)
 
 
-def check_k(k, who: str, lib=None) -> None:
-    """`ValueError` unless 1 <= k <= ggad_topk_max_k() (asked of the library: no GPU needed)."""
+def check_k(k, who: str, lib=None, wide: bool = False) -> None:
+    """`ValueError` unless 1 <= k <= ggad_topk_max_k() -- `wide`: ggad_topk_wide_max_k() -- (asked of the library: no GPU needed)."""
     from . import _lib
-    cap = int((lib or _lib.load()).ggad_topk_max_k())
+    lib = lib or _lib.load()
+    if wide:
+        cap = int(lib.ggad_topk_wide_max_k())
+        if int(k) != k or not 1 <= int(k) <= cap:
+            raise ValueError(f"{who}: k = {k} is outside 1..ggad_topk_wide_max_k() = {cap}")
+        return
+    cap = int(lib.ggad_topk_max_k())
     if int(k) != k or not 1 <= int(k) <= cap:
         raise ValueError(f"{who}: k = {k} is outside 1..ggad_topk_max_k() = {cap} (the pairs one workgroup sorts in LDS)")
 

@@ -19,6 +19,7 @@ round-robin over the ranks and gradients are all-reduced once per step (SURVEY.m
 ``top_k: K`` / ``top_k_out`` (`model: 'GCN'`, one GPU): the K highest scores of the closing test sweep are ranked on the device in a
 fixed order (`metrics.top_k`, csrc/topk.hip), kept in `self.ranked`, reported in one line and written to an `.npz`;
 `ModelHandler(config).score(checkpoint)` does the sweep, the report and the ranking from a saved checkpoint without training.
+``top_k_wide: true`` (with ``top_k`` > 0): the list is ranked by csrc/topk_wide.hip, K up to 4,194,304 instead of 16,384.
 ``rank_wide: true`` (with ``eval_cache: true``): a validation / test list with more than 8,192 positives is reported from the
 counting kernels of csrc/rank_wide.hip instead of `binary_report`'s two device sorts.
 
@@ -84,6 +85,10 @@ class ModelHandler(object):
             raise ValueError("config key `rank_wide` needs `eval_cache: true`: it chooses the metric kernels of the resident sweep "
                              "(without the sweep the metrics come from `binary_report`)")
         top_k, top_k_out = getattr(args, "top_k", 0) or 0, str(getattr(args, "top_k_out", "") or "")
+        top_k_wide = bool(getattr(args, "top_k_wide", False))
+        if top_k_wide and not top_k:
+            raise ValueError("config key `top_k_wide` needs `top_k: K` with K > 0: it chooses the kernels that rank the K highest scores "
+                             "(there is no ranking while `top_k` is 0)")
         if top_k or top_k_out:
             if getattr(args, "model", None) != "GCN":
                 raise ValueError("config keys `top_k` / `top_k_out` need `model: 'GCN'`: the ranked list is made from the scores of the "
@@ -91,7 +96,7 @@ class ModelHandler(object):
             if not top_k:
                 raise ValueError("config key `top_k_out` needs `top_k: K` with K > 0: there is no ranking to write while `top_k` is 0")
             from .metrics import check_k
-            check_k(top_k, "config key `top_k`")
+            check_k(top_k, "config key `top_k`", wide=top_k_wide)
             if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                 raise ValueError("config keys `top_k` / `top_k_out` run on one GPU: the ranking is not made under a torch.distributed "
                                  "world of several ranks yet")
@@ -127,13 +132,15 @@ class ModelHandler(object):
 
     def _rank(self, scores, ids, labels, sweep, k, verbose=True):
         """Config key `top_k` / `score(k=)`: the `Ranked` head of `scores` (the device scores of a sweep over `ids`, already made: nothing
-        is scored again), kept in `self.ranked`; one printed line; the `.npz` of config key `top_k_out`."""
+        is scored again), kept in `self.ranked`; one printed line; the `.npz` of config key `top_k_out`.  Config key `top_k_wide`: ranked
+        by `ggad_topk_wide_f32` (K above 16,384)."""
         from .metrics import precision_recall_at, top_k
+        wide = bool(getattr(self.args, "top_k_wide", False))
         if sweep is not None:
-            ranked = sweep.top_k(k, scores=scores)
+            ranked = sweep.top_k(k, scores=scores, wide=wide)
         else:
             lab = None if labels is None else torch.from_numpy(np.asarray(labels).reshape(-1).astype(np.uint8)).to(scores.device)
-            ranked = top_k(scores, k, lab, torch.from_numpy(np.asarray(ids, dtype=np.int64).reshape(-1)).to(scores.device))
+            ranked = top_k(scores, k, lab, torch.from_numpy(np.asarray(ids, dtype=np.int64).reshape(-1)).to(scores.device), wide=wide)
         self.ranked = ranked
         if verbose:
             if ranked.cum_pos is not None and ranked.m:
@@ -162,7 +169,7 @@ class ModelHandler(object):
         k = int(getattr(args, "top_k", 0) or 0) if k is None else int(k)
         if k:
             from .metrics import check_k
-            check_k(k, "ModelHandler.score")
+            check_k(k, "ModelHandler.score", wide=bool(getattr(args, "top_k_wide", False)))
         _, _, _, gnn_model, engine = self._build_gcn()
         self.model = gnn_model
         gnn_model.load_state_dict(torch.load(checkpoint))

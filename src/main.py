@@ -62,13 +62,17 @@ def use_handler(name):
 
 
 SCORE = None          # --score CKPT: score from this checkpoint instead of training
+SCORE_IDS = None      # --score_ids FILE.npy: the int64 ids --score sweeps and ranks (no labels) instead of the test split
 
 
 def run_once(config):
     set_random_seed(config["seed"])
     if SCORE is not None:
         handler = HANDLER(config)
-        handler.score(SCORE)
+        if SCORE_IDS is not None:
+            handler.score(SCORE, ids=np.asarray(np.load(SCORE_IDS), dtype=np.int64).reshape(-1))
+        else:
+            handler.score(SCORE)
         return handler.metrics
     return HANDLER(config).train()
 
@@ -130,7 +134,14 @@ if __name__ == "__main__":
     ap.add_argument("--top_k_out", type=str, default=None, help="override the config's top_k_out (.npz of the ranked list)")
     ap.add_argument("--rank_wide", action="store_true", default=None,
                     help="override the config's rank_wide (with eval_cache: exact rank metrics in HIP above 8,192 positives)")
+    ap.add_argument("--top_k_wide", action="store_true", default=None,
+                    help="override the config's top_k_wide (with top_k: rank through csrc/topk_wide.hip, K above 16384 up to 4194304)")
+    ap.add_argument("--score_ids", type=str, default=None, metavar="FILE.npy",
+                    help="with --score: sweep and rank this int64 id list (np.save) instead of the test split; no labels, so no report: "
+                         "with top_k it is the ranked list of these ids (every node of the graph, for instance)")
     a = ap.parse_args()
+    if a.score_ids is not None and a.score is None:
+        ap.error("--score_ids names the ids --score CKPT sweeps: it needs --score")
     if a.score is not None and a.handler != "ggad":
         ap.error("--score serves --handler ggad only")
     if a.score is not None and a.multi_run:
@@ -145,7 +156,9 @@ if __name__ == "__main__":
         cfg["top_k_out"] = a.top_k_out
     if a.rank_wide is not None:
         cfg["rank_wide"] = a.rank_wide
-    SCORE = a.score
+    if a.top_k_wide is not None:
+        cfg["top_k_wide"] = a.top_k_wide
+    SCORE, SCORE_IDS = a.score, a.score_ids
     use_handler(a.handler)
     init_distributed()
     torch.set_num_threads(min(8, os.cpu_count() or 1))        # host tensors are tiny here; 128 intra-op threads only add jitter
