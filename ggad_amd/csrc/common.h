@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
 #include "../../include/ggad_hip.h"
 
 #define GGAD_WAVE 64
@@ -25,6 +26,26 @@ void ggad_set_error(hipError_t e, const char *where);
   } while (0)
 
 static inline hipStream_t as_stream(ggad_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// More than 64 KB of dynamic LDS is a per-DEVICE attribute of a kernel: set -- and its result checked -- once per device of the
+// process, under the mutex of the site (one static ggad_lds_optin per site).  `kernels` all get `bytes`.  1 = ready, -1 = this device
+// refused (remembered), 0 = no usable current device; each site reacts in its own way.
+struct ggad_lds_optin {
+  std::mutex mu;
+  int state[64] = {};
+};
+template <typename... K>
+static inline int ggad_lds_opt_in(ggad_lds_optin &S, int bytes, K... kernels) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  std::lock_guard<std::mutex> lock(S.mu);
+  if (S.state[dev] == 0) {
+    const bool ok = ((hipFuncSetAttribute((const void *)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) && ...);
+    (void)hipGetLastError();
+    S.state[dev] = ok ? 1 : -1;
+  }
+  return S.state[dev];
+}
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (GGAD_WAVE - 1); }
 

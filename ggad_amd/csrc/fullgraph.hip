@@ -12,7 +12,6 @@
 // One wave per output row; a row of W floats is read as float4 (W % 4 == 0, W <= 1024: W = 300 -> 75 float4,
 // 2 load instructions per neighbour); neighbour ids / values are fetched 64 at a time and broadcast by
 // v_readlane.  Summation order is fixed (CSR order) -> deterministic.
-#include <mutex>
 
 #include "common.h"
 #include "handoff.h"
@@ -1957,23 +1956,11 @@ int ggad_spmm_sliced_f32(const int32_t *col, const float *val, const int32_t *se
 }
 
 // k_spmm_panel needs PAN_LDS (159 KB) of dynamic LDS per workgroup: the attribute is set -- and its result checked -- once per DEVICE
-// (0 unknown, 1 ready, -1 not available), under a mutex
+// (ggad_lds_opt_in of common.h; the device's reported LDS limit is the default one on some stacks, so the authoritative answer is
+// whether the opt-in succeeds)
 static bool panel_lds_ready() {
-  static std::mutex mu;
-  static int state[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (state[dev] == 0) {
-    int max_lds = 0;
-    bool ok = hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess;
-    (void)hipGetLastError();
-    // (the attribute reports the default limit on some stacks; the authoritative answer is whether the opt-in succeeds)
-    ok = hipFuncSetAttribute((const void *)k_spmm_panel, hipFuncAttributeMaxDynamicSharedMemorySize, PAN_LDS) == hipSuccess;
-    (void)hipGetLastError();
-    state[dev] = ok ? 1 : -1;
-  }
-  return state[dev] == 1;
+  static ggad_lds_optin lds_optin;
+  return ggad_lds_opt_in(lds_optin, PAN_LDS, k_spmm_panel) == 1;
 }
 int32_t ggad_spmm_panel_available(void) { return panel_lds_ready() ? 1 : 0; }
 
@@ -2003,20 +1990,10 @@ int ggad_spmm_panel_f32(const int32_t *wg_tab, int32_t n_wg, const uint32_t *dir
   return GGAD_OK;
 }
 
-// k_spmm_ring: the same opt-in for its RING_LDS bytes (per device, under a mutex)
+// k_spmm_ring: the same opt-in for its RING_LDS bytes, both instances
 static bool ring_lds_ready() {
-  static std::mutex mu;
-  static int state[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (state[dev] == 0) {
-    const bool ok = hipFuncSetAttribute((const void *)k_spmm_ring<RING_WALK>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS) == hipSuccess &&
-                    hipFuncSetAttribute((const void *)k_spmm_ring<RING_WALK_SUBSET>, hipFuncAttributeMaxDynamicSharedMemorySize, RING_LDS) == hipSuccess;
-    (void)hipGetLastError();
-    state[dev] = ok ? 1 : -1;
-  }
-  return state[dev] == 1;
+  static ggad_lds_optin lds_optin;
+  return ggad_lds_opt_in(lds_optin, RING_LDS, k_spmm_ring<RING_WALK>, k_spmm_ring<RING_WALK_SUBSET>) == 1;
 }
 int32_t ggad_spmm_ring_available(void) { return ring_lds_ready() ? 1 : 0; }
 int32_t ggad_spmm_ring_slot_rows(void) { return RING_RS; }

@@ -15,7 +15,6 @@
 // Long-K / few-tile shapes (weight gradients: K = number of nodes) are split along K over gridDim.z into
 // a workspace and summed by a second kernel in a fixed order (deterministic, no float atomics).
 #include <cstdlib>
-#include <mutex>
 
 #include "common.h"
 
@@ -754,19 +753,8 @@ int ggad_gemm_f32(const float *A, const float *B, float *C, int32_t M, int32_t N
     const int KP = sm_kp((K + 15) & ~15);
     const size_t lds = (size_t)2 * SM_T * KP * sizeof(float);
     // the opt-in for > 64 KB of dynamic LDS is recorded per DEVICE (0 unknown, 1 ready, -1 refused: the tiled kernels take the product)
-    static std::mutex mu;
-    static int state[64] = {};
-    int dev = 0;
-    bool ok = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
-    if (ok) {
-      std::lock_guard<std::mutex> lock(mu);
-      if (state[dev] == 0) {
-        state[dev] = hipFuncSetAttribute((const void *)k_gemm_small, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SM_T * 520 * 4 + 1024) == hipSuccess ? 1 : -1;
-        (void)hipGetLastError();
-      }
-      ok = state[dev] == 1;
-    }
-    if (ok) {
+    static ggad_lds_optin lds_optin;
+    if (ggad_lds_opt_in(lds_optin, 2 * SM_T * 520 * 4 + 1024, k_gemm_small) == 1) {
       k_gemm_small<<<dim3((N + SM_T - 1) / SM_T, (M + SM_T - 1) / SM_T), dim3(256), lds, st>>>(A, B, C, (int)M, (int)N, (int)K, sam, sak, sbk, sbn, ldc,
                                                                                                   bias, (int)relu, KP);
       gemm_note_route(GGAD_GEMM_ROUTE_SMALL, 0);

@@ -5,37 +5,78 @@
 //     L_k = negatives with score <  pos[k]        E_k = negatives with score == pos[k]        G_k = positives with score >= pos[k]
 //     AUROC = sum_k (2 L_k + E_k) / (2 P Nn)      (the numerator an exact int64: ONE float64 division)
 //     AP    = (1 / P) sum_k G_k / (G_k + Nn - L_k)    (float64 terms, summed in a fixed order)
-// Only the positives are sorted (one workgroup, bitonic network in LDS); every negative is bucketed against them by binary search.
+// Only the positives are sorted; every negative is bucketed against them by binary search.  No launch reads a word that an earlier
+// launch of the same call did not write, so the workspace needs no preparation and a call can be captured and replayed.  Two chains
+// share the pieces of this file and of rank_common.h (the key, the bounds, the bitonic network, the workgroup scan):
 //
-// Four launches on one stream:
-//   k_rm_scan    all n elements, RM_G workgroups over contiguous ranges: confusion counts and flags per workgroup (plain stores),
+// ggad_rank_metrics_f32, at most RM_CAP = 8,192 positives: four launches
+//   k_rm_scan    all n elements, <= 256 workgroups over contiguous ranges: confusion counts and flags per workgroup (plain stores),
 //                the keys of the positives appended to the workgroup's own segment; clears the two histograms of k_rm_bucket
-//   k_rm_sort    one workgroup: totals, status, the segments gathered and sorted
+//   k_rm_sort    one workgroup: totals, status, the segments gathered and sorted with the bitonic network in LDS
 //   k_rm_bucket  the sorted keys in LDS; per negative a lower- and an upper-bound search, +1 in two LDS histograms of P + 1 bins,
 //                flushed with integer atomics (integers: the result does not depend on the order)
-//   k_rm_finish  one workgroup: prefix sums, the two formulas, out8
-// Everything a launch reads was written by an earlier launch of the same call, so the workspace needs no preparation and the call
-// can be captured and replayed.
-#include "common.h"
-
-#include <mutex>
+//   k_rm_finish  one workgroup: prefix sums, the two formulas (8 consecutive positives per thread, then a halving tree), out8
+//
+// ggad_rank_wide_f32, at most RW_MAX = 1,048,576 positives.  `pos_cap` is the caller's bound on the positives; grids and workspace
+// follow from (n, pos_cap) alone.  With pc = min(pos_cap, max(n, 1)), TILE = 8,192, Tc = ceil(pc / TILE) and Sc = ceil(pc / 2,048):
+//   k_rw_scan    k_rm_scan's range scan (the one rm_scan_range); the segment capacity is min(per_block, pc); it clears nothing
+//   k_rw_sort    Sc workgroups.  Each sums the <= 256 headers (totals, status, segment offsets: one thread per header, a scan and a
+//                tree in LDS); workgroup 0 stores the summary.  Workgroup r gathers keys [2,048 r, min(P, 2,048 (r + 1))) from the
+//                segments, sorts them with the bitonic network and clears the histogram bins of its range; runs beyond P return
+//   k_rw_merge   ceil(log2(Sc)) passes, ping-pong between two key buffers, one thread per key: the key's place in the merged pair of
+//                runs is its index in its own run plus its rank in the partner run (lower bound from the left run, upper bound from
+//                the right one: equal keys keep distinct places).  An unpaired last run -- and a run that already covers P -- is
+//                copied through, so the sorted keys always end in the buffer the pass count names
+//   k_rw_bucket  a (Tc x rows) grid.  Column t holds tile t of the sorted keys and two histograms in LDS and walks the n elements; a
+//                negative belongs to the ONE tile with first key of t <= key < first key of t + 1 (open ends), where its upper bound
+//                ub is t TILE + the local one.  +1 in histU[ub], and, when the key at ub - 1 equals it, +1 in histE[ub - 1]: ties
+//                are counted at the END of a run, so a run that crosses a tile edge needs no look into another tile.  Flushed with
+//                integer atomics
+//   k_rw_terms   workgroup b owns positives [b TILE, (b + 1) TILE): sum of histU before them, a scan inside, per positive k the start s
+//                and end e of its run (neighbours first, binary search only inside a run); L_k = prefix of histU through k,
+//                E_k = histE[e], G_k = P - s.  Partial int64 numerator and float64 AP sum per workgroup, in k_rm_finish's order
+//   k_rw_final   the partials in a halving tree over the tiles, out8 (the one rm_write_out8)
+// Why runs of 2,048 and a merge by rank: head of rank_common.h.  Why the narrow chain stays although the wide one is twice as fast at
+// DGraph-Fin's size: inside a captured training epoch (run.py --select) a validation list of 3,935 nodes costs the wide chain six
+// launches against four, and the epoch is 21 us longer (profiles/rank_one_chain_time_line.json).
+#include "rank_common.h"
 
 namespace {
 
-constexpr int RM_CAP = 8192;              // positives one call takes: keys (32 KB) + two histograms (2 x 32 KB) in the 160 KB LDS
-constexpr int RM_T = 1024;                // threads of every workgroup
-constexpr int RM_G = 256;                 // workgroups of k_rm_scan at most (one segment of keys each)
+constexpr int RW_TILE = 8192;             // keys of one tile: keys (32 KB) + two histograms (2 x 32 KB) in the 160 KB LDS
+constexpr int RM_CAP = 8192;              // positives the narrow chain takes: keys (32 KB) + two histograms (2 x 32 KB) in LDS
 constexpr int RM_GB = 64;                 // workgroups of k_rm_bucket at most
-constexpr int RM_HDR = 8;                 // ints per workgroup of k_rm_scan: tp, fp, fn, tn, positives, flags
-constexpr int RM_META = 16;               // ints of k_rm_sort's summary: tp, fp, fn, tn, P, status
-constexpr int RM_BUCKET_LDS = RM_CAP * 4 + 2 * (RM_CAP + 1) * 4;
+constexpr int RW_STILE = RK_RUN;          // keys one workgroup sorts
+constexpr int RW_MAX = 1 << 20;           // positives one call takes: 128 tiles, 512 sorted runs, 9 merge passes
+constexpr int RW_TMAX = RW_MAX / RW_TILE;
+constexpr int RW_T = RK_T;                // threads of every workgroup
+constexpr int RW_G = 256;                 // workgroups of k_rw_scan at most (one segment of keys each)
+constexpr int RW_ROWS = 128;              // rows of k_rw_bucket's grid at most
+constexpr int RW_HDR = 8;                 // ints per workgroup of k_rw_scan: tp, fp, fn, tn, positives, flags
+constexpr int RW_META = 16;               // ints of the summary: tp, fp, fn, tn, P, status, tiles
+constexpr int RW_BUCKET_LDS = RW_TILE * 4 + 2 * (RW_TILE + 1) * 4;
 
-struct RmLayout {                         // int32 offsets into the workspace
+static_assert(RM_CAP == RW_TILE, "k_rm_bucket and k_rw_bucket take the same RW_BUCKET_LDS bytes");
+static_assert((RW_G * RW_HDR + RW_META + 4 * RW_TMAX) % 4 == 0 && RW_TILE % 4 == 0, "o_part, o_keys and o_hist stay 16-byte aligned");
+
+struct RwLayout {                         // int32 offsets into the workspace (o_part: 8-byte aligned; o_hist: 16-byte aligned)
+  int64_t per_block, seg_cap, pc;
+  int g, tc, st, passes, rows;
+  int64_t o_hdr() const { return 0; }
+  int64_t o_meta() const { return (int64_t)RW_G * RW_HDR; }
+  int64_t o_part() const { return o_meta() + RW_META; }                   // double ap[RW_TMAX] then int64 num[RW_TMAX]
+  int64_t o_keys() const { return o_part() + 4 * RW_TMAX; }               // two buffers of tc tiles
+  int64_t o_hist() const { return o_keys() + 2 * (int64_t)tc * RW_TILE; } // histU[pc + 1] then histE[pc + 1]
+  int64_t o_seg() const { return o_hist() + 2 * (pc + 1); }
+  int64_t total() const { return o_seg() + (int64_t)g * seg_cap; }
+};
+
+struct RmLayout {                         // the narrow chain's int32 offsets into the workspace
   int64_t per_block, seg_cap;
   int g;
   int64_t o_hdr() const { return 0; }
-  int64_t o_meta() const { return (int64_t)RM_G * RM_HDR; }
-  int64_t o_keys() const { return o_meta() + RM_META; }
+  int64_t o_meta() const { return (int64_t)RW_G * RW_HDR; }
+  int64_t o_keys() const { return o_meta() + RW_META; }
   int64_t o_hist() const { return o_keys() + RM_CAP; }                    // histU[RM_CAP + 1] then histE[RM_CAP + 1]
   int64_t o_seg() const { return o_hist() + 2 * (RM_CAP + 1); }
   int64_t total() const { return o_seg() + (int64_t)g * seg_cap; }
@@ -43,25 +84,37 @@ struct RmLayout {                         // int32 offsets into the workspace
 
 RmLayout rm_layout(int64_t n) {
   RmLayout L;
-  int64_t g = (n + RM_T - 1) / RM_T;
-  L.g = (int)(g < 1 ? 1 : (g > RM_G ? RM_G : g));
+  int64_t g = (n + RW_T - 1) / RW_T;
+  L.g = (int)(g < 1 ? 1 : (g > RW_G ? RW_G : g));
   L.per_block = (n + L.g - 1) / L.g;
   L.seg_cap = L.per_block < RM_CAP ? L.per_block : RM_CAP;
   if (L.seg_cap < 1) L.seg_cap = 1;
   return L;
 }
 
-// order-preserving image of a float (not NaN): a < b <=> key(a) < key(b), and -0.0 ties with +0.0
-__device__ __forceinline__ uint32_t rm_key(float s) {
-  const uint32_t b = s == 0.0f ? 0u : __float_as_uint(s);
-  return (b >> 31) ? ~b : (b | 0x80000000u);
+RwLayout rw_layout(int64_t n, int64_t pos_cap) {
+  RwLayout L;
+  int64_t g = (n + RW_T - 1) / RW_T;
+  L.g = (int)(g < 1 ? 1 : (g > RW_G ? RW_G : g));
+  L.per_block = (n + L.g - 1) / L.g;
+  L.pc = pos_cap < (n > 1 ? n : 1) ? pos_cap : (n > 1 ? n : 1);           // more positives than elements cannot be
+  L.seg_cap = L.per_block < L.pc ? L.per_block : L.pc;
+  if (L.seg_cap < 1) L.seg_cap = 1;
+  L.tc = (int)((L.pc + RW_TILE - 1) / RW_TILE);
+  L.st = (int)((L.pc + RW_STILE - 1) / RW_STILE);
+  L.passes = 0;
+  while ((1 << L.passes) < L.st) ++L.passes;
+  int64_t rows = (n + 16 * RW_T - 1) / (16 * RW_T);
+  const int64_t most = 256 / L.tc > RW_ROWS ? RW_ROWS : (256 / L.tc < 1 ? 1 : 256 / L.tc);
+  L.rows = (int)(rows < 1 ? 1 : (rows > most ? most : rows));
+  return L;
 }
 
-__global__ void __launch_bounds__(RM_T) k_rm_scan(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n,
-                                                  float thres, int64_t per_block, int seg_cap, int32_t *__restrict__ hdr,
-                                                  uint32_t *__restrict__ seg, int32_t *__restrict__ hist) {
+// The scan of both chains: workgroup b takes elements [b per_block, ...): confusion counts, flags and the number of positives to its
+// header by plain stores, the keys of the positives appended to its own segment.
+__device__ __forceinline__ void rm_scan_range(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n, float thres,
+                                              int64_t per_block, int seg_cap, int32_t *__restrict__ hdr, uint32_t *__restrict__ seg) {
   __shared__ int s_cnt[6];
-  for (int i = blockIdx.x * RM_T + threadIdx.x; i < 2 * (RM_CAP + 1); i += gridDim.x * RM_T) hist[i] = 0;
   if (threadIdx.x < 6) s_cnt[threadIdx.x] = 0;
   __syncthreads();
   const int64_t lo = (int64_t)blockIdx.x * per_block;
@@ -69,7 +122,7 @@ __global__ void __launch_bounds__(RM_T) k_rm_scan(const float *__restrict__ scor
   uint32_t *my = seg + (int64_t)blockIdx.x * seg_cap;
   const int lane = lane_id();
   int tp = 0, fp = 0, fn = 0, tn = 0, flags = 0;
-  for (int64_t base = lo + (threadIdx.x - lane); base < hi; base += RM_T) {        // (whole waves: the ballot below needs every lane)
+  for (int64_t base = lo + (threadIdx.x - lane); base < hi; base += RW_T) {        // (whole waves: the ballot below needs every lane)
     const int64_t i = base + lane;
     bool is_pos = false;
     uint32_t key = 0;
@@ -81,7 +134,7 @@ __global__ void __launch_bounds__(RM_T) k_rm_scan(const float *__restrict__ scor
       const bool pred = s >= thres;
       is_pos = y == 1;
       tp += pred && is_pos;  fp += pred && !is_pos;  fn += !pred && is_pos;  tn += !pred && !is_pos;
-      key = rm_key(s);
+      key = rk_key(s);
     }
     const unsigned long long m = __ballot(is_pos);
     if (m) {                                                                       // one LDS atomic per wave that holds positives
@@ -99,20 +152,34 @@ __global__ void __launch_bounds__(RM_T) k_rm_scan(const float *__restrict__ scor
   }
   if (flags) atomicOr(&s_cnt[5], flags);
   __syncthreads();
-  if (threadIdx.x < 6) hdr[blockIdx.x * RM_HDR + threadIdx.x] = s_cnt[threadIdx.x];
+  if (threadIdx.x < 6) hdr[blockIdx.x * RW_HDR + threadIdx.x] = s_cnt[threadIdx.x];
 }
 
-__global__ void __launch_bounds__(RM_T) k_rm_sort(const int32_t *__restrict__ hdr, int g, int seg_cap, const uint32_t *__restrict__ seg,
+__global__ void __launch_bounds__(RW_T) k_rw_scan(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n,
+                                                  float thres, int64_t per_block, int seg_cap, int32_t *__restrict__ hdr,
+                                                  uint32_t *__restrict__ seg) {
+  rm_scan_range(score, label, n, thres, per_block, seg_cap, hdr, seg);
+}
+
+// ---- the narrow chain (head of the file): four launches for at most RM_CAP positives
+__global__ void __launch_bounds__(RW_T) k_rm_scan(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n,
+                                                  float thres, int64_t per_block, int seg_cap, int32_t *__restrict__ hdr,
+                                                  uint32_t *__restrict__ seg, int32_t *__restrict__ hist) {
+  for (int i = blockIdx.x * RW_T + threadIdx.x; i < 2 * (RM_CAP + 1); i += gridDim.x * RW_T) hist[i] = 0;     // k_rm_bucket's histograms
+  rm_scan_range(score, label, n, thres, per_block, seg_cap, hdr, seg);
+}
+
+__global__ void __launch_bounds__(RW_T) k_rm_sort(const int32_t *__restrict__ hdr, int g, int seg_cap, const uint32_t *__restrict__ seg,
                                                   int32_t *__restrict__ meta, uint32_t *__restrict__ keys_out) {
   __shared__ uint32_t keys[RM_CAP];
-  __shared__ int32_t off[RM_G + 1];
+  __shared__ int32_t off[RW_G + 1];
   __shared__ int64_t tot[6];
   const int t = threadIdx.x;
   if (t == 0) {                                                   // <= 256 workgroups: a serial pass over their headers
     int64_t a[4] = {0, 0, 0, 0}, p = 0;
     int flags = 0;
     for (int b = 0; b < g; ++b) {
-      const int32_t *h = hdr + b * RM_HDR;
+      const int32_t *h = hdr + b * RW_HDR;
       for (int j = 0; j < 4; ++j) a[j] += h[j];
       off[b] = (int32_t)(p < RM_CAP + 1 ? p : RM_CAP + 1);
       p += h[4];
@@ -135,7 +202,7 @@ __global__ void __launch_bounds__(RM_T) k_rm_sort(const int32_t *__restrict__ hd
   const int P = (int)tot[4];
   int M = 64;
   while (M < P) M <<= 1;
-  for (int i = t; i < M; i += RM_T) {
+  for (int i = t; i < M; i += RW_T) {
     uint32_t k = 0xFFFFFFFFu;                                     // padding: above every key (NaN scores never get here)
     if (i < P) {
       int lo = 0, hi = g;                                         // the segment that holds the i-th positive: last b with off[b] <= i
@@ -144,22 +211,11 @@ __global__ void __launch_bounds__(RM_T) k_rm_sort(const int32_t *__restrict__ hd
     }
     keys[i] = k;
   }
-  __syncthreads();
-  for (int size = 2; size <= M; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = t; i < (M >> 1); i += RM_T) {
-        const int a = 2 * i - (i & (stride - 1)), b = a + stride;
-        const bool up = (a & size) == 0;
-        const uint32_t x = keys[a], y = keys[b];
-        if ((x > y) == up) { keys[a] = y; keys[b] = x; }
-      }
-      __syncthreads();
-    }
-  }
-  for (int i = t; i < P; i += RM_T) keys_out[i] = keys[i];
+  rk_bitonic(keys, M);
+  for (int i = t; i < P; i += RW_T) keys_out[i] = keys[i];
 }
 
-__global__ void __launch_bounds__(RM_T) k_rm_bucket(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n,
+__global__ void __launch_bounds__(RW_T) k_rm_bucket(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n,
                                                     const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys_in,
                                                     int32_t *__restrict__ hist) {
   extern __shared__ __attribute__((aligned(16))) uint32_t rm_lds[];
@@ -167,42 +223,55 @@ __global__ void __launch_bounds__(RM_T) k_rm_bucket(const float *__restrict__ sc
   const int P = meta[4];
   uint32_t *keys = rm_lds;
   int *hu = reinterpret_cast<int *>(rm_lds + RM_CAP), *he = hu + (RM_CAP + 1);
-  for (int i = threadIdx.x; i < P; i += RM_T) keys[i] = keys_in[i];
-  for (int i = threadIdx.x; i <= P; i += RM_T) { hu[i] = 0; he[i] = 0; }
+  for (int i = threadIdx.x; i < P; i += RW_T) keys[i] = keys_in[i];
+  for (int i = threadIdx.x; i <= P; i += RW_T) { hu[i] = 0; he[i] = 0; }
   __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * RM_T + threadIdx.x; i < n; i += (int64_t)gridDim.x * RM_T) {
+  for (int64_t i = (int64_t)blockIdx.x * RW_T + threadIdx.x; i < n; i += (int64_t)gridDim.x * RW_T) {
     if (label[i] != 0) continue;
-    const uint32_t key = rm_key(score[i]);
-    int lo = 0, hi = P;                                           // lb = positives below this score = first index of its run, if any
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
-    const int lb = lo;
-    hi = P;                                                       // ub = positives at or below it
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] <= key) lo = mid + 1; else hi = mid; }
-    atomicAdd(&hu[lo], 1);
-    if (lo > lb) atomicAdd(&he[lb], 1);
+    const uint32_t key = rk_key(score[i]);
+    const int lb = rk_lower(keys, 0, P, key);                     // positives below this score = first index of its run, if any
+    const int ub = rk_upper(keys, lb, P, key);                    // positives at or below it
+    atomicAdd(&hu[ub], 1);
+    if (ub > lb) atomicAdd(&he[lb], 1);
   }
   __syncthreads();
   int32_t *gu = hist, *ge = hist + (RM_CAP + 1);
-  for (int i = threadIdx.x; i <= P; i += RM_T) {
+  for (int i = threadIdx.x; i <= P; i += RW_T) {
     if (hu[i]) atomicAdd(&gu[i], hu[i]);
     if (he[i]) atomicAdd(&ge[i], he[i]);
   }
 }
 
-__global__ void __launch_bounds__(RM_T) k_rm_finish(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys_in,
-                                                    const int32_t *__restrict__ hist, double *__restrict__ out8) {
-  constexpr int CH = RM_CAP / RM_T;                               // consecutive positives of one thread
-  __shared__ uint32_t keys[RM_CAP];
-  __shared__ int32_t scan[2][RM_T];                              // (every prefix is a count of negatives: n <= INT32_MAX)
-  __shared__ double red[RM_T];
-  __shared__ int64_t redi[RM_T];
-  const int t = threadIdx.x;
+// out8 of both chains from the summary words, the exact numerator and the AP sum: ONE float64 division each
+__device__ __forceinline__ void rm_write_out8(const int32_t *__restrict__ meta, int64_t num, double ap_sum, double *__restrict__ out8) {
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  const int64_t tp = meta[0], fp = meta[1], fn = meta[2], tn = meta[3], n_pos = meta[4];
   const int status = meta[5];
-  const int64_t tp = meta[0], fp = meta[1], fn = meta[2], tn = meta[3];
-  const int P = status == 0 ? meta[4] : 0;
   const int64_t Nn = fp + tn;
+  double auroc = nan, avp = nan;
+  if (status == 0) {
+    auroc = (double)num / (double)(2 * n_pos * Nn);
+    avp = ap_sum / (double)n_pos;
+  } else if (status == 1) {
+    avp = n_pos == 0 ? 0.0 : 1.0;                                 // no positives: 0.0; positives only: every precision is 1
+  }
+  out8[0] = auroc;  out8[1] = avp;
+  out8[2] = (double)tp;  out8[3] = (double)fp;  out8[4] = (double)fn;  out8[5] = (double)tn;
+  out8[6] = (double)n_pos;  out8[7] = (double)status;
+}
+
+__global__ void __launch_bounds__(RW_T) k_rm_finish(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys_in,
+                                                    const int32_t *__restrict__ hist, double *__restrict__ out8) {
+  constexpr int CH = RM_CAP / RW_T;                               // consecutive positives of one thread
+  __shared__ uint32_t keys[RM_CAP];
+  __shared__ RkScan S;                                            // (every prefix is a count of negatives: n <= INT32_MAX)
+  __shared__ double red[RW_T];
+  __shared__ int64_t redi[RW_T];
+  const int t = threadIdx.x;
+  const int P = meta[5] == 0 ? meta[4] : 0;
+  const int64_t Nn = (int64_t)meta[1] + meta[3];
   const int32_t *hu = hist, *he = hist + (RM_CAP + 1);
-  for (int i = t; i < P; i += RM_T) keys[i] = keys_in[i];
+  for (int i = t; i < P; i += RW_T) keys[i] = keys_in[i];
   int64_t loc[CH];
   int64_t run = 0;
 #pragma unroll
@@ -211,25 +280,15 @@ __global__ void __launch_bounds__(RM_T) k_rm_finish(const int32_t *__restrict__ 
     if (k < P) run += hu[k];
     loc[j] = run;
   }
-  scan[0][t] = (int32_t)run;
-  __syncthreads();
-  int cur = 0;
-  for (int d = 1; d < RM_T; d <<= 1) {                            // inclusive scan of the threads' totals
-    scan[cur ^ 1][t] = scan[cur][t] + (t >= d ? scan[cur][t - d] : 0);
-    cur ^= 1;
-    __syncthreads();
-  }
-  const int64_t before = t > 0 ? scan[cur][t - 1] : 0;
-  double ap = 0.0;
+  const int64_t before = rk_block_scan(S, (int32_t)run, nullptr) - (int32_t)run;    // scan of the threads' totals (its barriers also
+  double ap = 0.0;                                                                   // publish keys[])
   int64_t num = 0;
 #pragma unroll
   for (int j = 0; j < CH; ++j) {
     const int k = t * CH + j;
     if (k >= P) continue;
     const int64_t L = before + loc[j];
-    const uint32_t key = keys[k];
-    int lo = 0, hi = k;                                           // first index of the run of equal keys that holds k
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
+    const int lo = rk_lower(keys, 0, k, keys[k]);                 // first index of the run of equal keys that holds k
     const int64_t G = P - lo;
     num += 2 * L + he[lo];
     ap += (double)G / (double)(G + Nn - L);
@@ -237,67 +296,272 @@ __global__ void __launch_bounds__(RM_T) k_rm_finish(const int32_t *__restrict__ 
   red[t] = ap;
   redi[t] = num;
   __syncthreads();
-  for (int d = RM_T / 2; d > 0; d >>= 1) {
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
     if (t < d) { red[t] += red[t + d]; redi[t] += redi[t + d]; }
     __syncthreads();
   }
-  if (t == 0) {
-    const double nan = __longlong_as_double(0x7FF8000000000000ll);
-    const int64_t n_pos = meta[4];
-    double auroc = nan, avp = nan;
-    if (status == 0) {
-      auroc = (double)redi[0] / (double)(2 * (int64_t)P * Nn);
-      avp = red[0] / (double)P;
-    } else if (status == 1) {
-      avp = n_pos == 0 ? 0.0 : 1.0;                               // no positives: 0.0; positives only: every precision is 1
+  if (t == 0) rm_write_out8(meta, redi[0], red[0], out8);
+}
+
+// ---- the run-merge chain
+
+__global__ void __launch_bounds__(RW_T) k_rw_sort(const int32_t *__restrict__ hdr, int g, int seg_cap, int pc,
+                                                  const uint32_t *__restrict__ seg, int32_t *__restrict__ meta,
+                                                  uint32_t *__restrict__ keys_out, int32_t *__restrict__ hist) {
+  __shared__ uint32_t keys[RW_STILE];
+  __shared__ int32_t off[RW_G + 1];
+  __shared__ int32_t hs[6][RW_G];                                 // the headers, one thread each (a serial pass over 256 of them
+  __shared__ RkScan S;                                            // is ~100 us of dependent loads); every sum is <= n <= INT32_MAX
+  __shared__ int32_t tot[2];
+  const int t = threadIdx.x;
+  if (t < RW_G) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) hs[j][t] = t < g ? hdr[t * RW_HDR + j] : 0;
+  }
+  const int upto = rk_block_scan(S, t < g ? hdr[t * RW_HDR + 4] : 0, nullptr);    // inclusive scan of the segments' counts
+  if (t < RW_G) off[t + 1] = upto;                                // (segments past g hold nothing: off[b] = P for b >= g)
+  if (t == 0) off[0] = 0;
+  for (int d = RW_G / 2; d > 0; d >>= 1) {                        // totals (integers: any order) and the flags
+    if (t < d) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) hs[j][t] += hs[j][t + d];
+      hs[5][t] |= hs[5][t + d];
     }
-    out8[0] = auroc;  out8[1] = avp;
-    out8[2] = (double)tp;  out8[3] = (double)fp;  out8[4] = (double)fn;  out8[5] = (double)tn;
-    out8[6] = (double)n_pos;  out8[7] = (double)status;
+    __syncthreads();
+  }
+  if (t == 0) {
+    const int p = off[RW_G], flags = hs[5][0];
+    const int64_t nn = (int64_t)hs[1][0] + hs[3][0];
+    int status = 0;
+    if (flags & 2) status = 4;
+    else if (flags & 1) status = 3;
+    else if (p > pc) status = 2;
+    else if (p == 0 || nn == 0) status = 1;
+    if (blockIdx.x == 0) {
+      for (int j = 0; j < 4; ++j) meta[j] = hs[j][0];
+      meta[4] = p;
+      meta[5] = status;
+      meta[6] = (int32_t)(((int64_t)p + RW_TILE - 1) / RW_TILE);
+    }
+    tot[0] = p;  tot[1] = status;
+  }
+  __syncthreads();
+  if (tot[1] != 0) return;
+  const int P = tot[0];
+  const int base = blockIdx.x * RW_STILE;
+  if (base >= P) return;
+  const int len = P - base < RW_STILE ? P - base : RW_STILE;
+  int32_t *gu = hist, *ge = hist + (pc + 1);
+  for (int i = t; i <= len; i += RW_T) { gu[base + i] = 0; ge[base + i] = 0; }    // bins base .. base + len <= P <= pc (the next run
+                                                                                  // clears bin base + len again: the same zero)
+  int M = 64;
+  while (M < len) M <<= 1;
+  for (int i = t; i < M; i += RW_T) {
+    uint32_t k = 0xFFFFFFFFu;                                     // padding: above every key (NaN scores never get here)
+    if (i < len) {
+      const int q = base + i;
+      int lo = 0, hi = g;                                         // the segment that holds the q-th positive: last b with off[b] <= q
+      while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= q) lo = mid; else hi = mid; }
+      k = seg[(int64_t)lo * seg_cap + (q - off[lo])];
+    }
+    keys[i] = k;
+  }
+  rk_bitonic(keys, M);
+  for (int i = t; i < len; i += RW_T) keys_out[base + i] = keys[i];
+}
+
+// one pass: runs of `width` keys of src[0, P) merged in pairs into dst[0, P)
+__global__ void __launch_bounds__(RW_T) k_rw_merge(const int32_t *__restrict__ meta, const uint32_t *__restrict__ src,
+                                                   uint32_t *__restrict__ dst, int width) {
+  if (meta[5] != 0) return;
+  const int P = meta[4];
+  const int i = blockIdx.x * RW_T + threadIdx.x;
+  if (i >= P) return;
+  const uint32_t key = src[i];
+  const int base = (i / (2 * width)) * (2 * width);               // (2 * width <= 2^20)
+  const int mid = base + width;
+  if (mid >= P) { dst[i] = key; return; }                         // an unpaired run: carried through
+  const int end = mid + width < P ? mid + width : P;
+  const int at = i < mid ? (i - base) + (rk_lower(src, mid, end, key) - mid) : (i - mid) + (rk_upper(src, base, mid, key) - base);
+  dst[base + at] = key;
+}
+
+__global__ void __launch_bounds__(RW_T) k_rw_bucket(const float *__restrict__ score, const uint8_t *__restrict__ label, int64_t n,
+                                                    const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys_in, int pc,
+                                                    int32_t *__restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t rw_lds[];
+  if (meta[5] != 0) return;
+  const int P = meta[4], T = meta[6];
+  const int tile = blockIdx.x;
+  if (tile >= T) return;
+  const int base = tile * RW_TILE;
+  const int len = P - base < RW_TILE ? P - base : RW_TILE;
+  uint32_t *keys = rw_lds;
+  int *hu = reinterpret_cast<int *>(rw_lds + RW_TILE), *he = hu + (RW_TILE + 1);
+  for (int i = threadIdx.x; i < len; i += RW_T) keys[i] = keys_in[base + i];
+  for (int i = threadIdx.x; i <= len; i += RW_T) { hu[i] = 0; he[i] = 0; }
+  const bool open_lo = tile == 0, open_hi = tile == T - 1;
+  const uint32_t first = keys_in[base], next = open_hi ? 0u : keys_in[base + RW_TILE];
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.y * RW_T + threadIdx.x; i < n; i += (int64_t)gridDim.y * RW_T) {
+    if (label[i] != 0) continue;
+    const uint32_t key = rk_key(score[i]);
+    if (!((open_lo || key >= first) && (open_hi || key < next))) continue;        // another tile's negative
+    const int ub = rk_upper(keys, 0, len, key);                   // positives of this tile at or below it (>= 1 unless tile 0)
+    atomicAdd(&hu[ub], 1);
+    if (ub > 0 && keys[ub - 1] == key) atomicAdd(&he[ub - 1], 1);
+  }
+  __syncthreads();
+  int32_t *gu = hist + base, *ge = hist + (pc + 1) + base;
+  for (int i = threadIdx.x; i <= len; i += RW_T) {
+    if (hu[i]) atomicAdd(&gu[i], hu[i]);
+    if (i < len && he[i]) atomicAdd(&ge[i], he[i]);
   }
 }
+
+__global__ void __launch_bounds__(RW_T) k_rw_terms(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                                   const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                                   int64_t *__restrict__ part_num) {
+  constexpr int CH = RW_TILE / RW_T;                              // consecutive positives of one thread
+  __shared__ RkScan S;                                            // (every prefix is a count of negatives: n <= INT32_MAX)
+  __shared__ double red[RW_T];
+  __shared__ int64_t redi[RW_T];
+  if (meta[5] != 0) return;
+  const int t = threadIdx.x;
+  const int P = meta[4];
+  const int base = blockIdx.x * RW_TILE;
+  if (base >= P) return;
+  const int64_t Nn = (int64_t)meta[1] + meta[3];
+  const int32_t *hu = hist, *he = hist + (pc + 1);
+  int32_t mine = 0;                                               // negatives binned before this workgroup's positives
+  const int4 *hu4 = reinterpret_cast<const int4 *>(hu);          // (histU starts on a 16-byte boundary, base is a multiple of 8,192)
+  for (int i = t; i < base / 4; i += RW_T) { const int4 v = hu4[i]; mine += v.x + v.y + v.z + v.w; }
+  const int64_t before_all = rk_block_sum(S.wsum, mine);
+  int64_t loc[CH];
+  int64_t run = 0;
+#pragma unroll
+  for (int j = 0; j < CH; ++j) {
+    const int k = base + t * CH + j;
+    if (k < P) run += hu[k];
+    loc[j] = run;
+  }
+  const int64_t before = before_all + (rk_block_scan(S, (int32_t)run, nullptr) - (int32_t)run);    // scan of the threads' totals
+  double ap = 0.0;
+  int64_t num = 0;
+#pragma unroll
+  for (int j = 0; j < CH; ++j) {
+    const int k = base + t * CH + j;
+    if (k >= P) continue;
+    const int64_t L = before + loc[j];
+    const uint32_t key = keys[k];
+    int s = k, e = k;                                             // the run of equal keys that holds k: [s, e]
+    if (k > 0 && keys[k - 1] == key) s = rk_lower(keys, 0, k - 1, key);
+    if (k + 1 < P && keys[k + 1] == key) e = rk_upper(keys, k + 2, P, key) - 1;
+    const int64_t G = P - s;
+    num += 2 * L + he[e];
+    ap += (double)G / (double)(G + Nn - L);
+  }
+  red[t] = ap;
+  redi[t] = num;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) { red[t] += red[t + d]; redi[t] += redi[t + d]; }
+    __syncthreads();
+  }
+  if (t == 0) { part_ap[blockIdx.x] = red[0]; part_num[blockIdx.x] = redi[0]; }
+}
+
+__global__ void __launch_bounds__(RW_TMAX) k_rw_final(const int32_t *__restrict__ meta, const double *__restrict__ part_ap,
+                                                      const int64_t *__restrict__ part_num, double *__restrict__ out8) {
+  __shared__ double red[RW_TMAX];
+  __shared__ int64_t redi[RW_TMAX];
+  const int t = threadIdx.x;
+  const int status = meta[5];
+  const int T = status == 0 ? meta[6] : 0;
+  red[t] = t < T ? part_ap[t] : 0.0;
+  redi[t] = t < T ? part_num[t] : 0;
+  __syncthreads();
+  for (int d = RW_TMAX / 2; d > 0; d >>= 1) {
+    if (t < d) { red[t] += red[t + d]; redi[t] += redi[t + d]; }
+    __syncthreads();
+  }
+  if (t == 0) rm_write_out8(meta, redi[0], red[0], out8);
+}
+
+bool rw_args_ok(int64_t n, int64_t pos_cap) { return n >= 0 && n <= INT32_MAX && pos_cap >= 1 && pos_cap <= RW_MAX; }
 
 }  // namespace
 
 extern "C" {
 
 int32_t ggad_rank_metrics_max_pos(void) { return RM_CAP; }
+int32_t ggad_rank_wide_max_pos(void) { return RW_MAX; }
 
 int64_t ggad_rank_metrics_workspace_elems(int64_t n) {
   if (n < 0 || n > INT32_MAX) return 0;
   return rm_layout(n).total();
 }
 
+int64_t ggad_rank_wide_workspace_elems(int64_t n, int64_t pos_cap) {
+  if (!rw_args_ok(n, pos_cap)) return 0;
+  return rw_layout(n, pos_cap).total();
+}
+
 int ggad_rank_metrics_f32(const float *score, const uint8_t *label, int64_t n, float thres, double *out8, int32_t *workspace,
                           ggad_stream_t stream) {
   GGAD_REQUIRE(out8 && workspace && n >= 0 && n <= INT32_MAX && (n == 0 || (score && label)));
   const RmLayout L = rm_layout(n);
-  {  // more than 64 KB of dynamic LDS is a per-DEVICE attribute of the kernel: set (and checked) once per device of the process
-    static std::mutex mu;
-    static int state[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GGAD_E_INVALID;
-    std::lock_guard<std::mutex> lock(mu);
-    if (state[dev] == 0) {
-      const bool ok = hipFuncSetAttribute((const void *)k_rm_bucket, hipFuncAttributeMaxDynamicSharedMemorySize, RM_BUCKET_LDS) == hipSuccess;
-      (void)hipGetLastError();
-      state[dev] = ok ? 1 : -1;
-    }
-    if (state[dev] != 1) { ggad_set_error(hipErrorInvalidValue, "rank_metrics: this device cannot give k_rm_bucket its LDS"); return GGAD_E_LAUNCH; }
-  }
+  static ggad_lds_optin lds;
+  const int ready = ggad_lds_opt_in(lds, RW_BUCKET_LDS, k_rm_bucket);
+  if (ready == 0) return GGAD_E_INVALID;
+  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "rank_metrics: this device cannot give k_rm_bucket its LDS"); return GGAD_E_LAUNCH; }
   hipStream_t st = as_stream(stream);
   int32_t *hdr = workspace + L.o_hdr(), *meta = workspace + L.o_meta(), *hist = workspace + L.o_hist();
   uint32_t *keys = reinterpret_cast<uint32_t *>(workspace + L.o_keys()), *seg = reinterpret_cast<uint32_t *>(workspace + L.o_seg());
-  k_rm_scan<<<dim3(L.g), dim3(RM_T), 0, st>>>(score, label, n, thres, L.per_block, (int)L.seg_cap, hdr, seg, hist);
+  k_rm_scan<<<dim3(L.g), dim3(RW_T), 0, st>>>(score, label, n, thres, L.per_block, (int)L.seg_cap, hdr, seg, hist);
   GGAD_CHECK_LAUNCH("rank_metrics scan");
-  k_rm_sort<<<dim3(1), dim3(RM_T), 0, st>>>(hdr, L.g, (int)L.seg_cap, seg, meta, keys);
+  k_rm_sort<<<dim3(1), dim3(RW_T), 0, st>>>(hdr, L.g, (int)L.seg_cap, seg, meta, keys);
   GGAD_CHECK_LAUNCH("rank_metrics sort");
-  int64_t gb = (n + 16 * RM_T - 1) / (16 * RM_T);
+  int64_t gb = (n + 16 * RW_T - 1) / (16 * RW_T);
   gb = gb < 1 ? 1 : (gb > RM_GB ? RM_GB : gb);
-  k_rm_bucket<<<dim3((unsigned)gb), dim3(RM_T), RM_BUCKET_LDS, st>>>(score, label, n, meta, keys, hist);
+  k_rm_bucket<<<dim3((unsigned)gb), dim3(RW_T), RW_BUCKET_LDS, st>>>(score, label, n, meta, keys, hist);
   GGAD_CHECK_LAUNCH("rank_metrics bucket");
-  k_rm_finish<<<dim3(1), dim3(RM_T), 0, st>>>(meta, keys, hist, out8);
+  k_rm_finish<<<dim3(1), dim3(RW_T), 0, st>>>(meta, keys, hist, out8);
   GGAD_CHECK_LAUNCH("rank_metrics finish");
+  return GGAD_OK;
+}
+
+int ggad_rank_wide_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, double *out8,
+                       int32_t *workspace, ggad_stream_t stream) {
+  GGAD_REQUIRE(out8 && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) && (n == 0 || (score && label)));
+  const RwLayout L = rw_layout(n, pos_cap);
+  static ggad_lds_optin lds;
+  const int ready = ggad_lds_opt_in(lds, RW_BUCKET_LDS, k_rw_bucket);
+  if (ready == 0) return GGAD_E_INVALID;
+  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "rank_wide: this device cannot give k_rw_bucket its LDS"); return GGAD_E_LAUNCH; }
+  hipStream_t st = as_stream(stream);
+  const int pc = (int)L.pc;
+  int32_t *hdr = workspace + L.o_hdr(), *meta = workspace + L.o_meta(), *hist = workspace + L.o_hist();
+  double *part_ap = reinterpret_cast<double *>(workspace + L.o_part());
+  int64_t *part_num = reinterpret_cast<int64_t *>(part_ap + RW_TMAX);
+  uint32_t *buf[2] = {reinterpret_cast<uint32_t *>(workspace + L.o_keys()),
+                      reinterpret_cast<uint32_t *>(workspace + L.o_keys() + (int64_t)L.tc * RW_TILE)};
+  uint32_t *seg = reinterpret_cast<uint32_t *>(workspace + L.o_seg());
+  k_rw_scan<<<dim3(L.g), dim3(RW_T), 0, st>>>(score, label, n, thres, L.per_block, (int)L.seg_cap, hdr, seg);
+  GGAD_CHECK_LAUNCH("rank_wide scan");
+  k_rw_sort<<<dim3(L.st), dim3(RW_T), 0, st>>>(hdr, L.g, (int)L.seg_cap, pc, seg, meta, buf[0], hist);
+  GGAD_CHECK_LAUNCH("rank_wide sort");
+  for (int p = 0; p < L.passes; ++p) {
+    k_rw_merge<<<dim3((unsigned)((L.pc + RW_T - 1) / RW_T)), dim3(RW_T), 0, st>>>(meta, buf[p & 1], buf[(p & 1) ^ 1], RW_STILE << p);
+    GGAD_CHECK_LAUNCH("rank_wide merge");
+  }
+  const uint32_t *keys = buf[L.passes & 1];
+  k_rw_bucket<<<dim3(L.tc, L.rows), dim3(RW_T), RW_BUCKET_LDS, st>>>(score, label, n, meta, keys, pc, hist);
+  GGAD_CHECK_LAUNCH("rank_wide bucket");
+  k_rw_terms<<<dim3(L.tc), dim3(RW_T), 0, st>>>(meta, keys, pc, hist, part_ap, part_num);
+  GGAD_CHECK_LAUNCH("rank_wide terms");
+  k_rw_final<<<dim3(1), dim3(RW_TMAX), 0, st>>>(meta, part_ap, part_num, out8);
+  GGAD_CHECK_LAUNCH("rank_wide final");
   return GGAD_OK;
 }
 

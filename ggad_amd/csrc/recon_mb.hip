@@ -26,7 +26,6 @@
 //
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage):  k_rm_steps  124 VGPRs, no scratch, dynamic LDS (the size of
 // rm_lds_floats, at most 160 KiB - 512 B);  k_rm_scores  62 VGPRs, no scratch, 33,024 bytes of LDS.
-#include <mutex>
 
 #include "common.h"
 
@@ -323,19 +322,10 @@ int ggad_recon_mb_steps_f32(const float *x1, const float *target, const int32_t 
   GGAD_REQUIRE((int64_t)total_rows * feat_dim < (1ll << 31));
   const size_t lds = (size_t)rm_lds_floats(feat_dim, max_rows) * sizeof(float);
   GGAD_REQUIRE(lds <= (size_t)RM_LDS_BYTES);
-  {  // the opt-in for more than 64 KB of dynamic LDS is a per-DEVICE attribute of the kernel: set (and checked) once per device
-    static std::mutex mu;
-    static int state[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return GGAD_E_INVALID;
-    std::lock_guard<std::mutex> lock(mu);
-    if (state[dev] == 0) {
-      const bool ok = hipFuncSetAttribute((const void *)k_rm_steps, hipFuncAttributeMaxDynamicSharedMemorySize, RM_LDS_BYTES) == hipSuccess;
-      (void)hipGetLastError();
-      state[dev] = ok ? 1 : -1;
-    }
-    if (state[dev] != 1) { ggad_set_error(hipErrorInvalidValue, "recon_mb_steps: this device cannot give k_rm_steps its LDS"); return GGAD_E_LAUNCH; }
-  }
+  static ggad_lds_optin lds_optin;
+  const int ready = ggad_lds_opt_in(lds_optin, RM_LDS_BYTES, k_rm_steps);
+  if (ready == 0) return GGAD_E_INVALID;
+  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "recon_mb_steps: this device cannot give k_rm_steps its LDS"); return GGAD_E_LAUNCH; }
   for (int32_t s0 = 0; s0 < n_steps; s0 += RM_SC_STEPS) {      // an epoch of the handlers (150 or 50 steps) is one launch
     const int32_t n = n_steps - s0 < RM_SC_STEPS ? n_steps - s0 : RM_SC_STEPS;
     const bool tail = s0 + n == n_steps;

@@ -7,7 +7,7 @@ slice boundaries (the aggregation normalises per slice, quirk 2), never on the w
 the launch size).  `ResidentSweep` therefore builds the plans ONCE, keeps the `(n, F)` rows, and a sweep is one `ggad_mb_score`
 launch over them: bit for bit what `score_nodes` returns.  The metrics come from the counting kernels of csrc/rank_metrics.hip
 (`metrics.rank_report`) instead of two device sorts; above their 8,192 positives, with config key `rank_wide`, from those of
-csrc/rank_wide.hip (`metrics.rank_report_wide`).
+csrc/rank_metrics.hip (`metrics.rank_report_wide`).
 """
 from __future__ import annotations
 

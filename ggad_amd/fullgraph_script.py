@@ -89,7 +89,7 @@ def add_select_options(p):
     p.add_argument("--top_k", type=int, default=off, help="with --score: rank the K highest-scoring test nodes (precision / recall @ K)")
     p.add_argument("--top_k_out", type=str, default=off, metavar="F.npz", help="with --score --top_k K: write the ranked list to F.npz")
     p.add_argument("--top_k_wide", action="store_true", default=off,
-                   help="with --score --top_k K: rank through csrc/topk_wide.hip, K above 16384 up to 4194304 (a whole test split)")
+                   help="with --score --top_k K: rank through csrc/topk.hip, K above 16384 up to 4194304 (a whole test split)")
     return p
 
 

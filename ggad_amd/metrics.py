@@ -11,12 +11,13 @@ sklearn itself stays the checker in the tests (tests/test_metrics.py).
 
 `rank_report` returns the same dict from float32 scores and uint8 labels through the counting kernels of csrc/rank_metrics.hip:
 no full sort (only the positives are sorted), four launches and ONE read-back.  `rank_report_wide` is the same for more than the
-8,192 positives one workgroup sorts, up to 1,048,576, through csrc/rank_wide.hip.
+8,192 positives one workgroup sorts, up to 1,048,576, through the run-merge chain of the same file.
 
 `top_k` is the ranked list: the k highest scores in a FIXED order (score descending, equal scores by ascending position; the head
 of a saturated sigmoid ranking is full of exact ties, and `torch.topk` fixes neither which tied elements it returns nor their
-order), with the running count of positives beside it, from `ggad_topk_f32` (csrc/topk.hip): six launches and ONE read-back.  `top_k(..., wide=True)` is the same list for more than the
-16,384 ranks one workgroup sorts, up to 4,194,304, through `ggad_topk_wide_f32` (csrc/topk_wide.hip)."""
+order), with the running count of positives beside it, from `ggad_topk_f32` (csrc/topk.hip): six launches and ONE read-back.
+`top_k(..., wide=True)` is the same list for more than the 16,384 ranks one workgroup sorts, up to 4,194,304, through
+`ggad_topk_wide_f32` of the same file."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -58,6 +59,17 @@ def average_precision(scores: torch.Tensor, labels: torch.Tensor) -> float:
     return float(((recall - prev) * precision).sum())
 
 
+def _confusion_scores(tp: int, fp: int, fn: int, tn: int) -> Dict[str, float]:
+    """F1 of class 1 and of class 0, macro-F1 and G-mean of a confusion matrix, and its four counts."""
+    def f1(t, f_p, f_n):
+        d = 2 * t + f_p + f_n
+        return 2.0 * t / d if d else 0.0
+
+    f1_1, f1_0 = f1(tp, fp, fn), f1(tn, fn, fp)
+    gmean = float((tp * tn / ((tp + fn) * (tn + fp))) ** 0.5) if (tp + fn) and (tn + fp) else float("nan")
+    return {"f1_1": f1_1, "f1_0": f1_0, "f1_macro": 0.5 * (f1_1 + f1_0), "gmean": gmean, "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+
+
 def binary_report(scores: torch.Tensor, labels: torch.Tensor, thres: float) -> Dict[str, float]:
     """Everything `test_sage` prints and returns, one host read-back of a handful of scalars."""
     labels = labels.to(scores.device)
@@ -67,18 +79,36 @@ def binary_report(scores: torch.Tensor, labels: torch.Tensor, thres: float) -> D
     fp = int((pred & ~pos).sum())
     fn = int((~pred & pos).sum())
     tn = int((~pred & ~pos).sum())
-
-    def f1(t, f_p, f_n):
-        d = 2 * t + f_p + f_n
-        return 2.0 * t / d if d else 0.0
-
-    f1_1, f1_0 = f1(tp, fp, fn), f1(tn, fn, fp)
-    gmean = float((tp * tn / ((tp + fn) * (tn + fp))) ** 0.5) if (tp + fn) and (tn + fp) else float("nan")
-    return {"auc": roc_auc(scores, labels), "ap": average_precision(scores, labels), "f1_1": f1_1, "f1_0": f1_0,
-            "f1_macro": 0.5 * (f1_1 + f1_0), "gmean": gmean, "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+    return {"auc": roc_auc(scores, labels), "ap": average_precision(scores, labels), **_confusion_scores(tp, fp, fn, tn)}
 
 
 _ONE_CLASS = "Only one class present in y_true. ROC AUC score is not defined in that case."
+
+
+def _rank_call(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float, pos_cap: Optional[int], wide: bool) -> Dict[str, float]:
+    """The body of `rank_report` and `rank_report_wide`: the checks, the workspace, one call and one read-back of eight doubles."""
+    from . import _lib
+    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+        raise ValueError("rank_report takes float32 scores and uint8 labels of the same 1-D shape")
+    if scores.device.type != "cuda" or labels_u8.device != scores.device:
+        raise ValueError("rank_report takes scores and labels on the same GPU (there is no CPU path: use binary_report)")
+    lib = _lib.load()
+    n = scores.numel()
+    if wide:
+        cap = int(lib.ggad_rank_wide_max_pos())
+        if pos_cap is None:
+            pos_cap = max(1, min(n, cap))
+        if int(pos_cap) != pos_cap or not 1 <= int(pos_cap) <= cap:
+            raise ValueError(f"rank_report_wide: pos_cap = {pos_cap} is outside 1..ggad_rank_wide_max_pos() = {cap}")
+        entry, sized = "ggad_rank_wide", (n, int(pos_cap))
+    else:
+        entry, sized = "ggad_rank_metrics", (n,)
+    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
+    with torch.cuda.device(scores.device):
+        ws = torch.empty(max(1, int(getattr(lib, entry + "_workspace_elems")(*sized))), dtype=torch.int32, device=scores.device)
+        out8 = torch.empty(8, dtype=torch.float64, device=scores.device)
+        _lib.call(entry + "_f32", _lib.ptr(scores), _lib.ptr(labels_u8), *sized, float(thres), _lib.ptr(out8), _lib.ptr(ws))
+        return _report_from_out8(out8.cpu().tolist(), lambda: binary_report(scores, labels_u8, thres))
 
 
 def rank_report(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float) -> Dict[str, float]:
@@ -86,46 +116,16 @@ def rank_report(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float) -> 
     float64 division of exact integer counts, AP as a fixed-order float64 sum, the confusion counts as integers; one read-back of
     eight doubles.  One class only: the `ValueError` of `binary_report`.  More positives than `ggad_rank_metrics_max_pos()`: the
     result of `binary_report` (its two device sorts).  A NaN score or a label other than 0/1: `ValueError`."""
-    from . import _lib
-    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
-        raise ValueError("rank_report takes float32 scores and uint8 labels of the same 1-D shape")
-    if scores.device.type != "cuda" or labels_u8.device != scores.device:
-        raise ValueError("rank_report takes scores and labels on the same GPU (there is no CPU path: use binary_report)")
-    lib = _lib.load()
-    n = scores.numel()
-    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
-    with torch.cuda.device(scores.device):
-        ws = torch.empty(max(1, int(lib.ggad_rank_metrics_workspace_elems(n))), dtype=torch.int32, device=scores.device)
-        out8 = torch.empty(8, dtype=torch.float64, device=scores.device)
-        _lib.call("ggad_rank_metrics_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, float(thres), _lib.ptr(out8), _lib.ptr(ws))
-        return _report_from_out8(out8.cpu().tolist(), lambda: binary_report(scores, labels_u8, thres))
+    return _rank_call(scores, labels_u8, thres, None, False)
 
 
 def rank_report_wide(scores: torch.Tensor, labels_u8: torch.Tensor, thres: float, pos_cap: Optional[int] = None) -> Dict[str, float]:
-    """`rank_report` for up to `ggad_rank_wide_max_pos()` = 1,048,576 positives, from `ggad_rank_wide_f32` (csrc/rank_wide.hip: the
+    """`rank_report` for up to `ggad_rank_wide_max_pos()` = 1,048,576 positives, from `ggad_rank_wide_f32` (csrc/rank_metrics.hip: the
     positives sorted in runs of 2,048 and merged, the same formulas): same arguments, same checks, same dict, one read-back.
     `pos_cap`: the caller's upper bound on the positives, which sizes the workspace and the launches (`None`: min(n, the cap); a
     tight bound means fewer merge passes and less workspace).  More positives than `pos_cap`: the result of `binary_report`.
     Timings against `binary_report` and `rank_report`: profiles/rank_wide_time_line.json."""
-    from . import _lib
-    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
-        raise ValueError("rank_report takes float32 scores and uint8 labels of the same 1-D shape")
-    if scores.device.type != "cuda" or labels_u8.device != scores.device:
-        raise ValueError("rank_report takes scores and labels on the same GPU (there is no CPU path: use binary_report)")
-    lib = _lib.load()
-    n = scores.numel()
-    cap = int(lib.ggad_rank_wide_max_pos())
-    if pos_cap is None:
-        pos_cap = max(1, min(n, cap))
-    if int(pos_cap) != pos_cap or not 1 <= int(pos_cap) <= cap:
-        raise ValueError(f"rank_report_wide: pos_cap = {pos_cap} is outside 1..ggad_rank_wide_max_pos() = {cap}")
-    pos_cap = int(pos_cap)
-    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
-    with torch.cuda.device(scores.device):
-        ws = torch.empty(int(lib.ggad_rank_wide_workspace_elems(n, pos_cap)), dtype=torch.int32, device=scores.device)
-        out8 = torch.empty(8, dtype=torch.float64, device=scores.device)
-        _lib.call("ggad_rank_wide_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, pos_cap, float(thres), _lib.ptr(out8), _lib.ptr(ws))
-        return _report_from_out8(out8.cpu().tolist(), lambda: binary_report(scores, labels_u8, thres))
+    return _rank_call(scores, labels_u8, thres, pos_cap, True)
 
 
 def _report_from_out8(o, fallback) -> Dict[str, float]:
@@ -139,16 +139,7 @@ def _report_from_out8(o, fallback) -> Dict[str, float]:
         return fallback()
     if status == 1:
         raise ValueError(_ONE_CLASS)
-    tp, fp, fn, tn = (int(v) for v in o[2:6])
-
-    def f1(t, f_p, f_n):
-        d = 2 * t + f_p + f_n
-        return 2.0 * t / d if d else 0.0
-
-    f1_1, f1_0 = f1(tp, fp, fn), f1(tn, fn, fp)
-    gmean = float((tp * tn / ((tp + fn) * (tn + fp))) ** 0.5) if (tp + fn) and (tn + fp) else float("nan")
-    return {"auc": float(o[0]), "ap": float(o[1]), "f1_1": f1_1, "f1_0": f1_0, "f1_macro": 0.5 * (f1_1 + f1_0), "gmean": gmean,
-            "tp": tp, "fp": fp, "fn": fn, "tn": tn}
+    return {"auc": float(o[0]), "ap": float(o[1]), **_confusion_scores(*(int(v) for v in o[2:6]))}
 
 
 @dataclass
@@ -172,7 +163,7 @@ def top_k(scores: torch.Tensor, k: int, labels_u8: Optional[torch.Tensor] = None
     """The `min(k, n)` highest of float32 device `scores`, ranked by score descending and, among equal scores, by ascending position
     (-0.0 ties with +0.0): one `ggad_topk_f32` call and one read-back of its four meta words.  `labels_u8` (uint8, same shape):
     `cum_pos` and `n_pos` are filled.  `ids` (int64, same shape): `Ranked.ids = ids[pos]`.  A NaN score, a label other than 0/1 or a
-    `k` outside 1..ggad_topk_max_k(): `ValueError`.  `wide=True`: `ggad_topk_wide_f32` (csrc/topk_wide.hip: the candidates sorted in
+    `k` outside 1..ggad_topk_max_k(): `ValueError`.  `wide=True`: `ggad_topk_wide_f32` (csrc/topk.hip: the candidates sorted in
     runs of 2,048 and merged), k up to ggad_topk_wide_max_k() = 4,194,304; the same list, and the same bits where both routes serve.
     Timings of both against a torch sort: profiles/topk_wide_time_line.json."""
     from . import _lib

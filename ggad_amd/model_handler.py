@@ -19,9 +19,9 @@ round-robin over the ranks and gradients are all-reduced once per step (SURVEY.m
 ``top_k: K`` / ``top_k_out`` (`model: 'GCN'`, one GPU): the K highest scores of the closing test sweep are ranked on the device in a
 fixed order (`metrics.top_k`, csrc/topk.hip), kept in `self.ranked`, reported in one line and written to an `.npz`;
 `ModelHandler(config).score(checkpoint)` does the sweep, the report and the ranking from a saved checkpoint without training.
-``top_k_wide: true`` (with ``top_k`` > 0): the list is ranked by csrc/topk_wide.hip, K up to 4,194,304 instead of 16,384.
+``top_k_wide: true`` (with ``top_k`` > 0): the list is ranked by csrc/topk.hip, K up to 4,194,304 instead of 16,384.
 ``rank_wide: true`` (with ``eval_cache: true``): a validation / test list with more than 8,192 positives is reported from the
-counting kernels of csrc/rank_wide.hip instead of `binary_report`'s two device sorts.
+counting kernels of csrc/rank_metrics.hip instead of `binary_report`'s two device sorts.
 
 The loader and split, the adjacency coercion, the checkpoint rule and the epoch loop of the labelled-batch models (`_train_sage`,
 `_train_sage_device`, `_train_pcgnn` build model, optimiser and containers and hand them to it) live in `handler_loop.py`; the GGAD

@@ -1199,10 +1199,10 @@ int ggad_topk_f32(const float *score, const uint8_t *label, int64_t n, int32_t k
 
 /* ------------------------------------------------------------------------------------
  * ggad_topk_f32 above 16,384 ranks, up to ggad_topk_wide_max_k() = 4,194,304 (2^22: one call ranks every node of DGraph-Fin)
- * (topk_wide.hip).  Same arguments and same outputs: out_pos int32[k], out_score float32[k], out_cumpos int32[k] or NULL, out_meta
+ * (topk.hip, behind the same select stage).  Same arguments and same outputs: out_pos int32[k], out_score float32[k], out_cumpos int32[k] or NULL, out_meta
  * int64[4] with the same four words and status codes; entries m..k) are padded as the narrow call pads them (pos -1, score 0, cumpos of
  * the last rank).  The ranking is the same one, and for every k <= ggad_topk_max_k() every output holds the same bits as
- * ggad_topk_f32's.  The select stage is the narrow call's (topk_common.h); the m candidates are then sorted in runs of 2,048 64-bit
+ * ggad_topk_f32's.  The select stage is the narrow call's (five launches); the m candidates are then sorted in runs of 2,048 64-bit
  * words (one workgroup each, 16 KB of static LDS), merged by rank in ceil(log2(ceil(m / 2048))) passes between two word buffers,
  * emitted one thread per output slot, and the labels along the ranking are prefix-summed per block of 1,024 ranks behind a fixed-order
  * sum of the blocks before.
@@ -1219,7 +1219,7 @@ int ggad_topk_wide_f32(const float *score, const uint8_t *label, int64_t n, int3
                        int32_t *out_cumpos, int64_t *out_meta, int32_t *workspace, ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
- * The rank metrics of ggad_rank_metrics_f32 for up to ggad_rank_wide_max_pos() = 1,048,576 positives (rank_wide.hip): the same
+ * The rank metrics of ggad_rank_metrics_f32 for up to ggad_rank_wide_max_pos() = 1,048,576 positives (rank_metrics.hip): the same
  * formulas, the same out8 and the same status codes.  The positives are sorted in runs of 2,048 (one workgroup each, in LDS) and
  * merged in ceil(log2(runs)) passes; every negative is bucketed against the one tile of 8,192 sorted keys whose range holds it; the
  * sums are made per tile and added in a fixed order.  `pos_cap` is the caller's upper bound on the positives (what k is to ggad_topk_f32): the

@@ -13,7 +13,7 @@ noise is drawn on the device from torch's own CPU stream, `ggad_amd/rng.py`; the
 conditional snapshot of the weights, all on the device and inside the captured epoch (`ggad_amd/select.py`); the trajectory and
 the CPU generator are untouched.  `--save PATH` writes the weights (the best epoch's with `--select`, else the last epoch's),
 `--score PATH [--top_k K] [--top_k_out F.npz]` scores the graph from such a file without training and ranks its test nodes;
-`--top_k_wide` ranks through csrc/topk_wide.hip, K above 16,384 up to 4,194,304 (the whole test split of T-Finance or Elliptic).
+`--top_k_wide` ranks through csrc/topk.hip, K above 16,384 up to 4,194,304 (the whole test split of T-Finance or Elliptic).
 """
 import os
 import sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the rank metrics cost above the 8,192 positives of csrc/rank_metrics.hip: `metrics.rank_report_wide` (csrc/rank_wide.hip)
+"""What the rank metrics cost above the 8,192 positives of csrc/rank_metrics.hip: `metrics.rank_report_wide` (csrc/rank_metrics.hip)
 against what runs today.
 
     python scripts/rank_wide_time.py [--n 1736598] [--positives 8313,7427,65536,1048576] [--warmup 2] [--reps 7]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the ranked list costs above 16,384 ranks: `ggad_topk_wide_f32` (csrc/topk_wide.hip) against `ggad_topk_f32` where both serve
+"""What the ranked list costs above 16,384 ranks: `ggad_topk_wide_f32` (csrc/topk.hip) against `ggad_topk_f32` where both serve
 and against torch at every depth.
 
     python scripts/topk_wide_time.py [--scores 1736598] [--all 3700550] [--reps 7] [--warmup 3] [--profile-k K]

@@ -135,7 +135,7 @@ if __name__ == "__main__":
     ap.add_argument("--rank_wide", action="store_true", default=None,
                     help="override the config's rank_wide (with eval_cache: exact rank metrics in HIP above 8,192 positives)")
     ap.add_argument("--top_k_wide", action="store_true", default=None,
-                    help="override the config's top_k_wide (with top_k: rank through csrc/topk_wide.hip, K above 16384 up to 4194304)")
+                    help="override the config's top_k_wide (with top_k: rank through csrc/topk.hip, K above 16384 up to 4194304)")
     ap.add_argument("--score_ids", type=str, default=None, metavar="FILE.npy",
                     help="with --score: sweep and rank this int64 id list (np.save) instead of the test split; no labels, so no report: "
                          "with top_k it is the ranked list of these ids (every node of the graph, for instance)")

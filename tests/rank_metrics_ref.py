@@ -90,4 +90,10 @@ def cases(cap: int):
     s[::7] = np.inf
     s[3::11] = -np.inf
     out.append(("infinity", s, y, 0.5))
+    # the edges of the sorted runs of 2,048 keys (appended last: the cases above keep their draws from the one generator): one short
+    # run, one full run, a second run of one key, three runs (an unpaired run in the first merge pass), four runs (two passes)
+    for p in (2047, 2048, 2049, 4097, 6145):
+        out.append((f"p{p}", *rand(p + 900, p), 0.5))
+    s, y = rand(5000, 4100)
+    out.append(("ties_across_runs", (np.floor(s * 3) / 3).astype(np.float32), y, 0.4))   # runs of equal keys longer than a sorted run
     return out

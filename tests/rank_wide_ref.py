@@ -1,4 +1,4 @@
-"""The cases of `ggad_rank_wide_f32` (csrc/rank_wide.hip): the smallest inputs at which each branch of the tiled kernels can go wrong.
+"""The cases of `ggad_rank_wide_f32` (csrc/rank_metrics.hip): the smallest inputs at which each branch of the tiled kernels can go wrong.
 The formulas are those of tests/rank_metrics_ref.py, imported: this file holds cases only.  Each case is (name, scores float32,
 labels uint8, thres), seeded.  tests/test_rank_wide_cpu.py holds the list against scikit-learn; tests/test_rank_wide_gpu.py holds the
 kernels against the formulas on it."""

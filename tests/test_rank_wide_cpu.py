@@ -1,4 +1,4 @@
-"""Exact rank metrics above 8,192 positives (csrc/rank_wide.hip, `metrics.rank_report_wide`, config key `rank_wide`), without a GPU.
+"""Exact rank metrics above 8,192 positives (csrc/rank_metrics.hip, `metrics.rank_report_wide`, config key `rank_wide`), without a GPU.
 
   1. the binding holds the three entry points; the cap is 2^20; `ggad_rank_wide_workspace_elems` is 0 for every refused argument,
      positive and non-decreasing in `n` and in `pos_cap` otherwise, and a function of the two alone; out-of-bounds calls are refused
@@ -111,9 +111,11 @@ def test_the_case_list():
     by = {c[0]: c for c in cs}
     want_p = dict(p8193=8193, p16384=16384, p16385=16385, p24581=3 * 8192 + 5, five_tiles=40000, lone_negative_wide=20000,
                   heavy_ties_wide=20000, all_tied_wide=9000, quantised=20000, boundary_run=16390, signed_zero_wide=9000,
-                  infinity_wide=9000, dgraph_like=8313, at_wide_cap=1 << 20, at_cap=8192)
+                  infinity_wide=9000, dgraph_like=8313, at_wide_cap=1 << 20, at_cap=8192,
+                  p2047=2047, p2048=2048, p2049=2049, p4097=4097, p6145=6145, ties_across_runs=4100)
     want_n = dict(five_tiles=70000, lone_negative_wide=20001, heavy_ties_wide=30000, all_tied_wide=12000, quantised=40000,
-                  dgraph_like=1736598, at_wide_cap=(1 << 20) + 3000, p8193=8193 + 3000)
+                  dgraph_like=1736598, at_wide_cap=(1 << 20) + 3000, p8193=8193 + 3000,
+                  p2047=2047 + 900, p2048=2048 + 900, p2049=2049 + 900, p4097=4097 + 900, p6145=6145 + 900, ties_across_runs=5000)
     for name, p in want_p.items():
         assert int(by[name][2].sum()) == p, name
     for name, n in want_n.items():

@@ -1,4 +1,4 @@
-"""Exact rank metrics above 8,192 positives on the device: csrc/rank_wide.hip, `metrics.rank_report_wide`, `ResidentSweep(rank_wide=True)`
+"""Exact rank metrics above 8,192 positives on the device: csrc/rank_metrics.hip, `metrics.rank_report_wide`, `ResidentSweep(rank_wide=True)`
 and config key `rank_wide`.
 
   1. every case of tests/rank_wide_ref.py through `ggad_rank_wide_f32` with `pos_cap` = P exactly and a workspace full of -1, against

@@ -1,4 +1,4 @@
-"""Top-k above 16,384 ranks (csrc/topk_wide.hip, `metrics.top_k(wide=True)`, config key `top_k_wide`), the parts that need no GPU:
+"""Top-k above 16,384 ranks (csrc/topk.hip, `metrics.top_k(wide=True)`, config key `top_k_wide`), the parts that need no GPU:
 
   1. the wide cases of tests/topk_wide_ref.py of at most 5,000 elements against a brute-force python sort by (-score, position), and
      the shape of the case list;

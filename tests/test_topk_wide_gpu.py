@@ -1,4 +1,4 @@
-"""Top-k above 16,384 ranks on the device: `ggad_topk_wide_f32` (csrc/topk_wide.hip), `metrics.top_k(wide=True)`,
+"""Top-k above 16,384 ranks on the device: `ggad_topk_wide_f32` (csrc/topk.hip), `metrics.top_k(wide=True)`,
 `ResidentSweep.top_k(wide=True)`, config key `top_k_wide`, `score_from_checkpoint` with `--top_k_wide`.  Everything is exact: integers
 compared with ==, floats bit for bit.
 

@@ -1,4 +1,4 @@
-"""The cases of `ggad_topk_wide_f32` (csrc/topk_wide.hip): the ranking is the one tests/topk_ref.py states (`reference`, `padded`); this
+"""The cases of `ggad_topk_wide_f32` (csrc/topk.hip): the ranking is the one tests/topk_ref.py states (`reference`, `padded`); this
 module adds the smallest inputs at which each branch the wide route adds can go wrong.  The candidates are sorted in runs of 2,048
 (one workgroup each) and merged in ceil(log2(runs)) passes, an unpaired last run copied through; the running positives are scanned
 per block of 1,024 ranks.  tests/test_topk_wide_cpu.py holds the small ones against a brute-force python sort,
