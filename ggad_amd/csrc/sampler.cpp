@@ -447,7 +447,7 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
           const int64_t s_old = (it.ord - POOL_RING) / SEG;
           const int64_t seg_last_item = pool_idx[(size_t)(s_old * SEG + SEG - 1)];
           wait_until([&] { return done_items.load(std::memory_order_acquire) > seg_last_item; });
-          wait_until([&] { return mat_done.load(std::memory_order_acquire) > s_old; });
+          if (n_pool >= 2) wait_until([&] { return mat_done.load(std::memory_order_acquire) > s_old; });      // (no composers below that)
         } else {
           wait_until([&] { return done_items.load(std::memory_order_acquire) > it.free_after; });
         }
@@ -511,7 +511,8 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
   auto perm_of = [&](int64_t q) -> const int32_t * { return pool_p + (size_t)items[(size_t)pool_idx[(size_t)q]].slot * pstride; };
   // positions [p0, p1) of X_s[P_first[ ... P_last[p]]].  Level by level over blocks of positions (each level a plain gather: independent
   // loads; following one position through all levels at a time is a chain of dependent cache misses: 43 against 32 us per batch)
-  auto compose = [&](const int32_t *X, int32_t *out, int64_t first, int64_t last, int64_t p0, int64_t p1) {
+  // out[0] stands for position out0 (a caller with a short buffer passes it as it is: `buffer - out0` would be a pointer outside the array)
+  auto compose = [&](const int32_t *X, int32_t *out, int64_t out0, int64_t first, int64_t last, int64_t p0, int64_t p1) {
     const int n_chain = (int)(last - first + 1);
     const int32_t *chain[SEG];
     for (int k = 0; k < n_chain; ++k) chain[k] = perm_of(last - k);          // applied last-to-first
@@ -524,7 +525,7 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
         const int32_t *c = chain[k];
         for (int j = 0; j < nb; ++j) idx[j] = c[idx[j]];
       }
-      for (int j = 0; j < nb; ++j) out[b0 + j] = X[idx[j]];
+      for (int j = 0; j < nb; ++j) out[b0 - out0 + j] = X[idx[j]];
     }
   };
   static const int env_m = [] { const char *e = getenv("GGAD_SCHED_M"); return e ? atoi(e) : 0; }();
@@ -541,7 +542,7 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
           if (sg >= 1)                                           // the buffer to write still serves the batches of segment sg - 1
             wait_until([&] { return done_items.load(std::memory_order_acquire) > pool_idx[(size_t)(first - 1)]; });
           const int64_t p0 = n_pool * m / NM, p1 = n_pool * (m + 1) / NM;
-          compose(Xb[sg & 1], Xb[(sg + 1) & 1], first, last, p0, p1);
+          compose(Xb[sg & 1], Xb[(sg + 1) & 1], 0, first, last, p0, p1);
           if (seg_arrived[sg].fetch_add(1, std::memory_order_acq_rel) + 1 == NM) mat_done.store(sg + 1, std::memory_order_release);
         }
       });
@@ -572,7 +573,7 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
         int32_t head[256];
         for (int64_t c0 = 0; c0 < n_pseudo; c0 += 256) {
           const int64_t c1 = std::min<int64_t>(n_pseudo, c0 + 256);
-          compose(Xb[sg & 1], head - c0, sg * SEG, it.ord, c0, c1);
+          compose(Xb[sg & 1], head, c0, sg * SEG, it.ord, c0, c1);
           for (int64_t p = c0; p < c1; ++p) dst[nt + p] = (int64_t)head[p - c0];
         }
       } else {
@@ -586,10 +587,11 @@ int ggad_sched_batches(ggad_mt19937 *g, int64_t *train, int64_t n_train, int64_t
   }
   for (auto &t : composers) t.join();
   // the pool's final state: the end of the last full segment, or the shuffles of a last partial segment applied to it
-  int32_t *cur = Xb[n_full_seg & 1];
+  // (a pool of fewer than two ids never moves and has no composers: its state is the one it came with, in Xb[0])
+  int32_t *cur = Xb[n_pool >= 2 ? (n_full_seg & 1) : 0];
   if (n_pool >= 2 && n_pool_items > n_full_seg * SEG) {
     int32_t *fin = Xb[(n_full_seg + 1) & 1];
-    compose(cur, fin, n_full_seg * SEG, n_pool_items - 1, 0, n_pool);
+    compose(cur, fin, 0, n_full_seg * SEG, n_pool_items - 1, 0, n_pool);
     cur = fin;
   }
   for (auto &t : workers) t.join();
