@@ -36,6 +36,12 @@
 //                and end e of its run (neighbours first, binary search only inside a run); L_k = prefix of histU through k,
 //                E_k = histE[e], G_k = P - s.  Partial int64 numerator and float64 AP sum per workgroup, in k_rm_finish's order
 //   k_rw_final   the partials in a halving tree over the tiles, out8 (the one rm_write_out8)
+//
+// ggad_rank_operating_f32: the run-merge chain's front (rw_front: scan .. bucket) and, in place of the last two launches,
+//   k_ro_terms   k_rw_terms' sums from the one rw_terms_tile, and per run of equal positives the candidate (tp = G_k, fp = Nn - L_k:
+//                the confusion counts of `score >= pos[k]`): the curve stores, the best candidate per thread, a tree over the workgroup
+//   k_ro_final   k_rw_final's tree into out16[0..7] and a tree over the tiles' candidates into out16[8..15]
+// At 8,192 positives or fewer that is one tile and no merge pass, so there is no narrow chain for it.
 // Why runs of 2,048 and a merge by rank: head of rank_common.h.  Why the narrow chain stays although the wide one is twice as fast at
 // DGraph-Fin's size: inside a captured training epoch (run.py --select) a validation list of 3,935 nodes costs the wide chain six
 // launches against four, and the epoch is 21 us longer (profiles/rank_one_chain_time_line.json).
@@ -55,6 +61,8 @@ constexpr int RW_ROWS = 128;              // rows of k_rw_bucket's grid at most
 constexpr int RW_HDR = 8;                 // ints per workgroup of k_rw_scan: tp, fp, fn, tn, positives, flags
 constexpr int RW_META = 16;               // ints of the summary: tp, fp, fn, tn, P, status, tiles
 constexpr int RW_BUCKET_LDS = RW_TILE * 4 + 2 * (RW_TILE + 1) * 4;
+constexpr int RO_PART = 8;                // ints per tile of k_ro_terms: tp, fp, key, candidates, the float64 value, two spare
+constexpr int RO_CRITERIA = 5;            // f1, f1_macro, gmean, precision, fpr
 
 static_assert(RM_CAP == RW_TILE, "k_rm_bucket and k_rw_bucket take the same RW_BUCKET_LDS bytes");
 static_assert((RW_G * RW_HDR + RW_META + 4 * RW_TMAX) % 4 == 0 && RW_TILE % 4 == 0, "o_part, o_keys and o_hist stay 16-byte aligned");
@@ -69,6 +77,8 @@ struct RwLayout {                         // int32 offsets into the workspace (o
   int64_t o_hist() const { return o_keys() + 2 * (int64_t)tc * RW_TILE; } // histU[pc + 1] then histE[pc + 1]
   int64_t o_seg() const { return o_hist() + 2 * (pc + 1); }
   int64_t total() const { return o_seg() + (int64_t)g * seg_cap; }
+  int64_t o_op() const { return (total() + 3) & ~(int64_t)3; }            // ggad_rank_operating_f32 only: RO_PART ints per tile
+  int64_t total_op() const { return o_op() + (int64_t)RO_PART * RW_TMAX; }
 };
 
 struct RmLayout {                         // the narrow chain's int32 offsets into the workspace
@@ -419,9 +429,79 @@ __global__ void __launch_bounds__(RW_T) k_rw_bucket(const float *__restrict__ sc
   }
 }
 
-__global__ void __launch_bounds__(RW_T) k_rw_terms(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
-                                                   const int32_t *__restrict__ hist, double *__restrict__ part_ap,
-                                                   int64_t *__restrict__ part_num) {
+// ---- the operating point (ggad_rank_operating_f32).  A candidate is the run of equal positives [s, e]: threshold pos[s], tp = G,
+// fp = Nn - L, both exact.  tp == 0 marks "none" (a real candidate holds its own positive).
+struct RoCand {
+  int32_t tp, fp;
+  uint32_t key;
+  double v;                                                       // criterion 1 only: 0.5 (F1 of class 1 + F1 of class 0)
+};
+
+struct RoArgs {
+  int crit;
+  double param;
+  float *curve_thres;                                             // all three or none
+  int32_t *curve_tp, *curve_fp;
+  int32_t *part;                                                  // RO_PART ints per tile
+};
+
+__device__ __forceinline__ float ro_score(uint32_t key) { return __uint_as_float((key >> 31) ? (key & 0x7FFFFFFFu) : ~key); }    // rk_key back
+
+// the candidate of (tp, fp, key) under the criterion: macro-F1 formed as metrics._confusion_scores forms it (each class F1 one
+// division of exact integers, a zero denominator counts 0); criteria 3 and 4 drop what misses the constraint
+__device__ __forceinline__ RoCand ro_make(int crit, double param, int64_t P, int64_t Nn, int64_t tp, int64_t fp, uint32_t key) {
+  RoCand c;
+  c.tp = (int32_t)tp;  c.fp = (int32_t)fp;  c.key = key;  c.v = 0.0;
+  if (crit == 1) {
+    const int64_t fn = P - tp, tn = Nn - fp, d0 = 2 * tn + fn + fp;
+    const double f1 = 2.0 * (double)tp / (double)(2 * tp + fp + fn);
+    const double f0 = d0 ? 2.0 * (double)tn / (double)d0 : 0.0;
+    c.v = 0.5 * (f1 + f0);
+  } else if (crit == 3) {
+    c.tp = (double)tp >= param * (double)(tp + fp) ? c.tp : 0;
+  } else if (crit == 4) {
+    c.tp = (double)fp <= param * (double)Nn ? c.tp : 0;
+  }
+  return c;
+}
+
+// does b replace a?  Criteria 0 and 2 in exact int64 (cross-multiplied F1 < 2^54, tp tn < 2^51), 1 in float64, 3 and 4 by recall;
+// equal values: the higher threshold.  A total order, so the reduction's shape does not move the result.
+// Written without a branch on the candidates (`crit` is uniform over the launch; the rest are selects): the callers keep the winner
+// with selects too (ro_pick), so the per-thread loop of k_ro_terms has no divergent control flow around its four running fields.  Keep
+// it so: `if (better) best = c;` with early returns in here compiled, for gfx950, to code that left best.fp behind (DESIGN.md section 4;
+// tests/test_operating_point_gpu.py::test_tie_rule_by_hand and the case n63 show it).
+__device__ __forceinline__ bool ro_better(int crit, int64_t P, int64_t Nn, const RoCand &a, const RoCand &b) {
+  int64_t l = b.tp, r = a.tp;                                     // criteria 3 and 4: the greater recall
+  if (crit == 0) {                                                // 2tp / (2tp + fp + fn) = 2tp / (tp + fp + P)
+    l = (int64_t)b.tp * ((int64_t)a.tp + a.fp + P);  r = (int64_t)a.tp * ((int64_t)b.tp + b.fp + P);
+  } else if (crit == 2) {
+    l = (int64_t)b.tp * (Nn - b.fp);  r = (int64_t)a.tp * (Nn - a.fp);
+  }
+  bool gt = l > r, eq = l == r;
+  if (crit == 1) { gt = b.v > a.v;  eq = b.v == a.v; }            // (no NaN: both are sums of two quotients in [0, 1])
+  const bool wins = gt | (eq & (b.key > a.key));
+  return (b.tp != 0) & ((a.tp == 0) | wins);
+}
+
+// a, or b where it replaces a: four selects
+__device__ __forceinline__ RoCand ro_pick(bool take_b, const RoCand &a, const RoCand &b) {
+  RoCand c;
+  c.tp = take_b ? b.tp : a.tp;  c.fp = take_b ? b.fp : a.fp;  c.key = take_b ? b.key : a.key;  c.v = take_b ? b.v : a.v;
+  return c;
+}
+
+struct RoLds {                                                    // the candidate tree of one workgroup
+  int32_t tp[RW_T], fp[RW_T];
+  uint32_t key[RW_T];
+  double v[RW_T];
+};
+
+// k_rw_terms (OP = false) and k_ro_terms (OP = true): the same sums in the same order; OP adds the curve stores and the arg-max
+template <bool OP>
+__device__ __forceinline__ void rw_terms_tile(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                              const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                              int64_t *__restrict__ part_num, const RoArgs &A, RoLds *C) {
   constexpr int CH = RW_TILE / RW_T;                              // consecutive positives of one thread
   __shared__ RkScan S;                                            // (every prefix is a count of negatives: n <= INT32_MAX)
   __shared__ double red[RW_T];
@@ -448,6 +528,8 @@ __global__ void __launch_bounds__(RW_T) k_rw_terms(const int32_t *__restrict__ m
   const int64_t before = before_all + (rk_block_scan(S, (int32_t)run, nullptr) - (int32_t)run);    // scan of the threads' totals
   double ap = 0.0;
   int64_t num = 0;
+  RoCand best = {0, 0, 0u, 0.0};
+  int cands = 0;
 #pragma unroll
   for (int j = 0; j < CH; ++j) {
     const int k = base + t * CH + j;
@@ -460,15 +542,54 @@ __global__ void __launch_bounds__(RW_T) k_rw_terms(const int32_t *__restrict__ m
     const int64_t G = P - s;
     num += 2 * L + he[e];
     ap += (double)G / (double)(G + Nn - L);
+    if constexpr (OP) {
+      if (A.curve_thres) {                                        // entry j: the run of the j-th highest positive
+        const int j = P - 1 - k;
+        A.curve_thres[j] = ro_score(key);  A.curve_tp[j] = (int32_t)G;  A.curve_fp[j] = (int32_t)(Nn - L);
+      }
+      const bool first = s == k;                                  // one candidate per run, ascending: a later equal value wins
+      cands += first;
+      const RoCand c = ro_make(A.crit, A.param, P, Nn, G, Nn - L, key);
+      best = ro_pick(first & ro_better(A.crit, P, Nn, best, c), best, c);
+    }
   }
   red[t] = ap;
   redi[t] = num;
+  if constexpr (OP) { C->tp[t] = best.tp;  C->fp[t] = best.fp;  C->key[t] = best.key;  C->v[t] = best.v; }
   __syncthreads();
   for (int d = RW_T / 2; d > 0; d >>= 1) {
-    if (t < d) { red[t] += red[t + d]; redi[t] += redi[t + d]; }
+    if (t < d) {
+      red[t] += red[t + d];  redi[t] += redi[t + d];
+      if constexpr (OP) {
+        const RoCand a = {C->tp[t], C->fp[t], C->key[t], C->v[t]}, b = {C->tp[t + d], C->fp[t + d], C->key[t + d], C->v[t + d]};
+        const RoCand w = ro_pick(ro_better(A.crit, P, Nn, a, b), a, b);
+        C->tp[t] = w.tp;  C->fp[t] = w.fp;  C->key[t] = w.key;  C->v[t] = w.v;
+      }
+    }
     __syncthreads();
   }
   if (t == 0) { part_ap[blockIdx.x] = red[0]; part_num[blockIdx.x] = redi[0]; }
+  if constexpr (OP) {
+    const int all = rk_block_sum(S.wsum, cands);
+    if (t == 0) {
+      int32_t *o = A.part + (int64_t)blockIdx.x * RO_PART;
+      o[0] = C->tp[0];  o[1] = C->fp[0];  o[2] = (int32_t)C->key[0];  o[3] = all;
+      *reinterpret_cast<double *>(o + 4) = C->v[0];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(RW_T) k_rw_terms(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                                   const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                                   int64_t *__restrict__ part_num) {
+  rw_terms_tile<false>(meta, keys, pc, hist, part_ap, part_num, RoArgs{}, nullptr);
+}
+
+__global__ void __launch_bounds__(RW_T) k_ro_terms(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                                   const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                                   int64_t *__restrict__ part_num, RoArgs A) {
+  __shared__ RoLds C;
+  rw_terms_tile<true>(meta, keys, pc, hist, part_ap, part_num, A, &C);
 }
 
 __global__ void __launch_bounds__(RW_TMAX) k_rw_final(const int32_t *__restrict__ meta, const double *__restrict__ part_ap,
@@ -488,7 +609,106 @@ __global__ void __launch_bounds__(RW_TMAX) k_rw_final(const int32_t *__restrict_
   if (t == 0) rm_write_out8(meta, redi[0], red[0], out8);
 }
 
+// k_rw_final's tree (the same out8 bits into out16[0..7]) and beside it the tree over the tiles' candidates: out16[8..15]
+__global__ void __launch_bounds__(RW_TMAX) k_ro_final(const int32_t *__restrict__ meta, const double *__restrict__ part_ap,
+                                                      const int64_t *__restrict__ part_num, const int32_t *__restrict__ part, int crit,
+                                                      double *__restrict__ out16) {
+  __shared__ double red[RW_TMAX];
+  __shared__ int64_t redi[RW_TMAX];
+  __shared__ int32_t ctp[RW_TMAX], cfp[RW_TMAX], cnt[RW_TMAX];
+  __shared__ uint32_t ckey[RW_TMAX];
+  __shared__ double cv[RW_TMAX];
+  const int t = threadIdx.x;
+  const int status = meta[5];
+  const int T = status == 0 ? meta[6] : 0;
+  const int64_t P = meta[4], Nn = (int64_t)meta[1] + meta[3];
+  const int32_t *mine = part + (int64_t)t * RO_PART;
+  red[t] = t < T ? part_ap[t] : 0.0;
+  redi[t] = t < T ? part_num[t] : 0;
+  ctp[t] = t < T ? mine[0] : 0;
+  cfp[t] = t < T ? mine[1] : 0;
+  ckey[t] = t < T ? (uint32_t)mine[2] : 0u;
+  cnt[t] = t < T ? mine[3] : 0;
+  cv[t] = t < T ? *reinterpret_cast<const double *>(mine + 4) : 0.0;
+  __syncthreads();
+  for (int d = RW_TMAX / 2; d > 0; d >>= 1) {
+    if (t < d) {
+      red[t] += red[t + d];  redi[t] += redi[t + d];  cnt[t] += cnt[t + d];
+      const RoCand a = {ctp[t], cfp[t], ckey[t], cv[t]}, b = {ctp[t + d], cfp[t + d], ckey[t + d], cv[t + d]};
+      const RoCand w = ro_pick(ro_better(crit, P, Nn, a, b), a, b);
+      ctp[t] = w.tp;  cfp[t] = w.fp;  ckey[t] = w.key;  cv[t] = w.v;
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  rm_write_out8(meta, redi[0], red[0], out16);
+  if (status != 0) {
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    for (int j = 8; j < 15; ++j) out16[j] = nan;
+    out16[15] = (double)status;
+    return;
+  }
+  const int64_t tp = ctp[0], fp = cfp[0];
+  out16[14] = (double)cnt[0];
+  if (tp == 0) {                                                  // no candidate meets the constraint: alert on nothing
+    out16[8] = __longlong_as_double(0x7FF0000000000000ll);
+    out16[9] = 0.0;  out16[10] = 0.0;  out16[11] = (double)P;  out16[12] = (double)Nn;
+    out16[13] = 0.0;  out16[15] = 5.0;
+    return;
+  }
+  const int64_t fn = P - tp, tn = Nn - fp;
+  double v;
+  if (crit == 0) v = 2.0 * (double)tp / (double)(2 * tp + fp + fn);
+  else if (crit == 1) v = cv[0];
+  else if (crit == 2) v = sqrt((double)(tp * tn) / (double)(P * Nn));
+  else v = (double)tp / (double)P;
+  out16[8] = (double)ro_score(ckey[0]);
+  out16[9] = (double)tp;  out16[10] = (double)fp;  out16[11] = (double)fn;  out16[12] = (double)tn;
+  out16[13] = v;  out16[15] = 0.0;
+}
+
 bool rw_args_ok(int64_t n, int64_t pos_cap) { return n >= 0 && n <= INT32_MAX && pos_cap >= 1 && pos_cap <= RW_MAX; }
+
+// The front of the run-merge chain, which ggad_rank_wide_f32 and ggad_rank_operating_f32 share: scan, sorted runs, merge passes,
+// the tile bucket.  Leaves the sorted keys, the two histograms and the summary; the caller launches its terms and its final.
+struct RwFront {
+  RwLayout L;
+  hipStream_t st;
+  int32_t *meta, *hist;
+  double *part_ap;
+  int64_t *part_num;
+  const uint32_t *keys;
+};
+
+int rw_front(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, int32_t *workspace,
+             ggad_stream_t stream, RwFront &F) {
+  const RwLayout L = rw_layout(n, pos_cap);
+  static ggad_lds_optin lds;
+  const int ready = ggad_lds_opt_in(lds, RW_BUCKET_LDS, k_rw_bucket);
+  if (ready == 0) return GGAD_E_INVALID;
+  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "rank_wide: this device cannot give k_rw_bucket its LDS"); return GGAD_E_LAUNCH; }
+  hipStream_t st = as_stream(stream);
+  const int pc = (int)L.pc;
+  int32_t *hdr = workspace + L.o_hdr(), *meta = workspace + L.o_meta(), *hist = workspace + L.o_hist();
+  uint32_t *buf[2] = {reinterpret_cast<uint32_t *>(workspace + L.o_keys()),
+                      reinterpret_cast<uint32_t *>(workspace + L.o_keys() + (int64_t)L.tc * RW_TILE)};
+  uint32_t *seg = reinterpret_cast<uint32_t *>(workspace + L.o_seg());
+  k_rw_scan<<<dim3(L.g), dim3(RW_T), 0, st>>>(score, label, n, thres, L.per_block, (int)L.seg_cap, hdr, seg);
+  GGAD_CHECK_LAUNCH("rank_wide scan");
+  k_rw_sort<<<dim3(L.st), dim3(RW_T), 0, st>>>(hdr, L.g, (int)L.seg_cap, pc, seg, meta, buf[0], hist);
+  GGAD_CHECK_LAUNCH("rank_wide sort");
+  for (int p = 0; p < L.passes; ++p) {
+    k_rw_merge<<<dim3((unsigned)((L.pc + RW_T - 1) / RW_T)), dim3(RW_T), 0, st>>>(meta, buf[p & 1], buf[(p & 1) ^ 1], RW_STILE << p);
+    GGAD_CHECK_LAUNCH("rank_wide merge");
+  }
+  const uint32_t *keys = buf[L.passes & 1];
+  k_rw_bucket<<<dim3(L.tc, L.rows), dim3(RW_T), RW_BUCKET_LDS, st>>>(score, label, n, meta, keys, pc, hist);
+  GGAD_CHECK_LAUNCH("rank_wide bucket");
+  F.L = L;  F.st = st;  F.meta = meta;  F.hist = hist;  F.keys = keys;
+  F.part_ap = reinterpret_cast<double *>(workspace + L.o_part());
+  F.part_num = reinterpret_cast<int64_t *>(F.part_ap + RW_TMAX);
+  return GGAD_OK;
+}
 
 }  // namespace
 
@@ -534,34 +754,37 @@ int ggad_rank_metrics_f32(const float *score, const uint8_t *label, int64_t n, f
 int ggad_rank_wide_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, double *out8,
                        int32_t *workspace, ggad_stream_t stream) {
   GGAD_REQUIRE(out8 && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) && (n == 0 || (score && label)));
-  const RwLayout L = rw_layout(n, pos_cap);
-  static ggad_lds_optin lds;
-  const int ready = ggad_lds_opt_in(lds, RW_BUCKET_LDS, k_rw_bucket);
-  if (ready == 0) return GGAD_E_INVALID;
-  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "rank_wide: this device cannot give k_rw_bucket its LDS"); return GGAD_E_LAUNCH; }
-  hipStream_t st = as_stream(stream);
-  const int pc = (int)L.pc;
-  int32_t *hdr = workspace + L.o_hdr(), *meta = workspace + L.o_meta(), *hist = workspace + L.o_hist();
-  double *part_ap = reinterpret_cast<double *>(workspace + L.o_part());
-  int64_t *part_num = reinterpret_cast<int64_t *>(part_ap + RW_TMAX);
-  uint32_t *buf[2] = {reinterpret_cast<uint32_t *>(workspace + L.o_keys()),
-                      reinterpret_cast<uint32_t *>(workspace + L.o_keys() + (int64_t)L.tc * RW_TILE)};
-  uint32_t *seg = reinterpret_cast<uint32_t *>(workspace + L.o_seg());
-  k_rw_scan<<<dim3(L.g), dim3(RW_T), 0, st>>>(score, label, n, thres, L.per_block, (int)L.seg_cap, hdr, seg);
-  GGAD_CHECK_LAUNCH("rank_wide scan");
-  k_rw_sort<<<dim3(L.st), dim3(RW_T), 0, st>>>(hdr, L.g, (int)L.seg_cap, pc, seg, meta, buf[0], hist);
-  GGAD_CHECK_LAUNCH("rank_wide sort");
-  for (int p = 0; p < L.passes; ++p) {
-    k_rw_merge<<<dim3((unsigned)((L.pc + RW_T - 1) / RW_T)), dim3(RW_T), 0, st>>>(meta, buf[p & 1], buf[(p & 1) ^ 1], RW_STILE << p);
-    GGAD_CHECK_LAUNCH("rank_wide merge");
-  }
-  const uint32_t *keys = buf[L.passes & 1];
-  k_rw_bucket<<<dim3(L.tc, L.rows), dim3(RW_T), RW_BUCKET_LDS, st>>>(score, label, n, meta, keys, pc, hist);
-  GGAD_CHECK_LAUNCH("rank_wide bucket");
-  k_rw_terms<<<dim3(L.tc), dim3(RW_T), 0, st>>>(meta, keys, pc, hist, part_ap, part_num);
+  RwFront F;
+  const int rc = rw_front(score, label, n, pos_cap, thres, workspace, stream, F);
+  if (rc != GGAD_OK) return rc;
+  k_rw_terms<<<dim3(F.L.tc), dim3(RW_T), 0, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, F.part_ap, F.part_num);
   GGAD_CHECK_LAUNCH("rank_wide terms");
-  k_rw_final<<<dim3(1), dim3(RW_TMAX), 0, st>>>(meta, part_ap, part_num, out8);
+  k_rw_final<<<dim3(1), dim3(RW_TMAX), 0, F.st>>>(F.meta, F.part_ap, F.part_num, out8);
   GGAD_CHECK_LAUNCH("rank_wide final");
+  return GGAD_OK;
+}
+
+int32_t ggad_rank_operating_criteria(void) { return RO_CRITERIA; }
+
+int64_t ggad_rank_operating_workspace_elems(int64_t n, int64_t pos_cap) {
+  if (!rw_args_ok(n, pos_cap)) return 0;
+  return rw_layout(n, pos_cap).total_op();
+}
+
+int ggad_rank_operating_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, int32_t criterion,
+                            double param, double *out16, float *curve_thres, int32_t *curve_tp, int32_t *curve_fp, int32_t *workspace,
+                            ggad_stream_t stream) {
+  GGAD_REQUIRE(out16 && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) && (n == 0 || (score && label)));
+  GGAD_REQUIRE(criterion >= 0 && criterion < RO_CRITERIA && (criterion < 3 || (param >= 0.0 && param <= 1.0)));
+  GGAD_REQUIRE((curve_thres != nullptr) == (curve_tp != nullptr) && (curve_tp != nullptr) == (curve_fp != nullptr));
+  RwFront F;
+  const int rc = rw_front(score, label, n, pos_cap, thres, workspace, stream, F);
+  if (rc != GGAD_OK) return rc;
+  const RoArgs A = {criterion, criterion < 3 ? 0.0 : param, curve_thres, curve_tp, curve_fp, workspace + F.L.o_op()};
+  k_ro_terms<<<dim3(F.L.tc), dim3(RW_T), 0, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, F.part_ap, F.part_num, A);
+  GGAD_CHECK_LAUNCH("rank_operating terms");
+  k_ro_final<<<dim3(1), dim3(RW_TMAX), 0, F.st>>>(F.meta, F.part_ap, F.part_num, A.part, criterion, out16);
+  GGAD_CHECK_LAUNCH("rank_operating final");
   return GGAD_OK;
 }
 

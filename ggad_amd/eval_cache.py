@@ -107,6 +107,22 @@ class ResidentSweep:
             return rank_report_wide(scores, self.labels, thres, pos_cap=min(self.n_pos, int(self.engine.lib.ggad_rank_wide_max_pos())))
         return rank_report(scores, self.labels, thres)
 
+    def operating_point(self, criterion: str, param: float = None, thres: float = 0.5, scores: torch.Tensor = None):
+        """`metrics.operating_point` of the current weights' scores (or of `scores`, a result of `scores()` the caller already
+        holds) on the resident labels: the alert threshold that is best under `criterion`, with its counts.  `pos_cap` is the
+        sweep's own count of positives (counted once on the host), so the workspace and the grids are as small as they can be."""
+        from .metrics import operating_point
+        if self.labels is None:
+            raise ValueError("ResidentSweep.operating_point: this sweep was built without labels")
+        if self.n_pos is None:
+            self.n_pos = int((self.labels == 1).sum())
+        cap = int(self.engine.lib.ggad_rank_wide_max_pos())
+        if self.n_pos > cap:
+            raise ValueError(f"ResidentSweep.operating_point: the list holds {self.n_pos} positives, more than "
+                             f"ggad_rank_wide_max_pos() = {cap}")
+        return operating_point(self.scores() if scores is None else scores, self.labels, criterion, param, thres,
+                               pos_cap=max(1, self.n_pos))
+
     def top_k(self, k: int, scores: torch.Tensor = None, wide: bool = False):
         """`metrics.top_k` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) with the
         sweep's ids and resident labels: the `Ranked` head of the list, `ids` = node ids.  Nothing is uploaded and no plan is built.

@@ -119,13 +119,73 @@ def check_select_options(p, a):
     return a
 
 
+def add_threshold_options(p):
+    """`--threshold CRIT` (run.py only): after training, choose the alert threshold on idx_val on the device (`metrics.operating_point`)
+    and report idx_test at it.  Off by default and, like the options of `add_select_options`, absent from the namespace when not
+    given.  Read it with `threshold_option`; `check_threshold_options` after parsing."""
+    p.add_argument("--threshold", type=str, default=argparse.SUPPRESS, metavar="CRIT",
+                   help="choose the alert threshold on idx_val after training: f1, f1_macro, gmean, precision:X (the greatest recall at a "
+                        "precision of at least X) or fpr:X (at a false-positive rate of at most X); --save keeps it, --score reports at it")
+    return p
+
+
+def threshold_option(a):
+    """`--threshold` of a namespace: the criterion's text, or None when not given."""
+    return getattr(a, "threshold", None) or None
+
+
+def check_threshold_options(p, a):
+    crit = threshold_option(a)
+    if crit is None:
+        return a
+    if select_options(a)[2]:
+        p.error("--score reports at the threshold its checkpoint carries: --threshold chooses one at training time")
+    from .metrics import parse_criterion
+    try:
+        parse_criterion(crit)
+    except ValueError as exc:
+        p.error("--threshold: {}".format(exc))
+    return a
+
+
+def choose_threshold(crit, scores, idx_val, ano_label, dev):
+    """`--threshold CRIT` after training: the operating point of the (N,) device `scores` on `idx_val`, printed as one `[threshold]`
+    line; returns the `metrics.OperatingPoint`."""
+    from .metrics import operating_point, parse_criterion
+    name, param = parse_criterion(crit)
+    idx = np.asarray(idx_val, dtype=np.int64)
+    y8 = np.asarray(ano_label).reshape(-1)[idx].astype(np.uint8)
+    val = scores.detach().float().index_select(0, torch.as_tensor(idx, device=dev))
+    op = operating_point(val, torch.from_numpy(y8).to(dev), name, param, pos_cap=max(1, int(np.count_nonzero(y8 == 1))))
+    print("[threshold] {} on {} validation nodes: threshold {!r} value {!r} tp {} fp {} fn {} tn {} ({} candidates{})".format(
+        crit, idx.size, op.thres, op.value, op.tp, op.fp, op.fn, op.tn, op.n_candidates,
+        "" if op.feasible else "; none meets the constraint: no node alerts"))
+    return op
+
+
+def print_threshold_test(test_scores, y_dev, thres, alerts=False):
+    """One `[threshold] test` line: the confusion counts, F1-macro and G-mean of `score >= thres` on the test nodes (`alerts`: and how
+    many of them alert); returns the dict of `metrics._confusion_scores`."""
+    from .metrics import _confusion_scores
+    pred, pos = test_scores >= thres, y_dev == 1
+    c = _confusion_scores(int((pred & pos).sum()), int((pred & ~pos).sum()), int((~pred & pos).sum()), int((~pred & ~pos).sum()))
+    print("[threshold] test at {!r}: tp {} fp {} fn {} tn {} F1-macro {!r} G-mean {!r}".format(
+        float(thres), c["tp"], c["fp"], c["fn"], c["tn"], c["f1_macro"], c["gmean"]))
+    if alerts:
+        print("alerts: {} of {} test nodes".format(c["tp"] + c["fp"], test_scores.numel()))
+    return c
+
+
 # ------------------------------------------------------------------------------------------------ checkpoints
-def save_checkpoint(path, state_dict, args, n_in, nodes, epoch, value=None):
+def save_checkpoint(path, state_dict, args, n_in, nodes, epoch, value=None, threshold=None):
     """`torch.save({"state_dict", "meta"})`: the model's own state_dict (host copies; for `run.py` the reference's key names, so the
     reference's `Model` loads it) and what a later `--score` checks or reports.  `epoch`: the epoch the weights are from; `value`: the
-    validation metric `--select` chose them by (None without)."""
+    validation metric `--select` chose them by (None without).  `threshold`: the `metrics.OperatingPoint` of `--threshold`; only then
+    does `meta` hold `thres` (a float that is exactly a float32), `thres_select` (the criterion as given) and `thres_value`."""
     meta = {"dataset": args.dataset, "n_in": int(n_in), "embedding_dim": int(args.embedding_dim), "nodes": int(nodes), "seed": int(args.seed),
             "epoch": int(epoch), "select": getattr(args, "select", None), "value": None if value is None else float(value)}
+    if threshold is not None:
+        meta.update(thres=float(threshold.thres), thres_select=str(threshold_option(args)), thres_value=float(threshold.value))
     torch.save({"state_dict": type(state_dict)((k, v.detach().cpu().clone()) for k, v in state_dict.items()), "meta": meta}, path)
     return meta
 
@@ -164,7 +224,10 @@ def score_from_checkpoint(args, model, score_fn, n_in, idx_test, ano_label, dev)
     idx_dev = torch.as_tensor(idx, device=dev)
     y = np.asarray(ano_label).reshape(-1)[idx]
     test_scores = scores.index_select(0, idx_dev)
-    auc, ap = print_eval(args.dataset, test_scores, torch.as_tensor(y.astype(np.int64), device=dev))
+    y_dev = torch.as_tensor(y.astype(np.int64), device=dev)
+    auc, ap = print_eval(args.dataset, test_scores, y_dev)
+    if meta.get("thres") is not None:                                           # a checkpoint of --threshold: the alert rule it carries
+        print_threshold_test(test_scores, y_dev, meta["thres"], alerts=True)
     ranked = None
     if k:
         y8 = y.astype(np.uint8)

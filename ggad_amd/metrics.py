@@ -17,7 +17,12 @@ no full sort (only the positives are sorted), four launches and ONE read-back.  
 of a saturated sigmoid ranking is full of exact ties, and `torch.topk` fixes neither which tied elements it returns nor their
 order), with the running count of positives beside it, from `ggad_topk_f32` (csrc/topk.hip): six launches and ONE read-back.
 `top_k(..., wide=True)` is the same list for more than the 16,384 ranks one workgroup sorts, up to 4,194,304, through
-`ggad_topk_wide_f32` of the same file."""
+`ggad_topk_wide_f32` of the same file.
+
+`operating_point` turns a score into an alert rule: the threshold, among the distinct scores of the positives, that is best under
+F1, macro-F1, G-mean, or recall at a bound on precision or on the false-positive rate, with its exact confusion counts, from
+`ggad_rank_operating_f32` (the run-merge chain of csrc/rank_metrics.hip with an arg-max behind it): one call, one read-back.
+`pr_curve` is the curve behind it; `parse_criterion` reads the criterion's spelling in the configs and on the command lines."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -140,6 +145,134 @@ def _report_from_out8(o, fallback) -> Dict[str, float]:
     if status == 1:
         raise ValueError(_ONE_CLASS)
     return {"auc": float(o[0]), "ap": float(o[1]), **_confusion_scores(*(int(v) for v in o[2:6]))}
+
+
+CRITERIA = ("f1", "f1_macro", "gmean", "precision", "fpr")          # the codes of ggad_rank_operating_f32, in order
+
+
+def parse_criterion(text) -> Tuple[str, Optional[float]]:
+    """(name, param) of `f1`, `f1_macro`, `gmean`, `precision:0.9` (the greatest recall at a precision of at least 0.9) or
+    `fpr:0.01` (the greatest recall at a false-positive rate of at most 0.01); anything else: `ValueError`.  The one parser of
+    config key `thres_select` and of `run.py --threshold`."""
+    name, sep, tail = str(text).strip().partition(":")
+    if name not in CRITERIA:
+        raise ValueError(f"threshold criterion {text!r}: expected one of f1, f1_macro, gmean, precision:X, fpr:X")
+    if name in ("precision", "fpr"):
+        try:
+            param = float(tail)
+        except ValueError:
+            raise ValueError(f"threshold criterion {text!r}: `{name}` takes a bound in [0, 1], as in `{name}:0.9`") from None
+        if not 0.0 <= param <= 1.0:
+            raise ValueError(f"threshold criterion {text!r}: the bound {tail} is outside [0, 1]")
+        return name, param
+    if sep:
+        raise ValueError(f"threshold criterion {text!r}: `{name}` takes no bound")
+    return name, None
+
+
+@dataclass
+class OperatingPoint:
+    """The alert rule `score >= thres` that `operating_point` chose.  `thres`: a Python float that is exactly a float32 (the score
+    of a positive; +inf when `feasible` is false: alert on nothing).  `tp, fp, fn, tn`: its confusion counts; `value`: the
+    criterion's value there (F1, macro-F1, G-mean, or the recall under the constraint); `n_candidates`: the distinct positive
+    scores; `report`: the `binary_report` dict at `thres`."""
+    thres: float
+    tp: int
+    fp: int
+    fn: int
+    tn: int
+    value: float
+    criterion: str
+    param: Optional[float]
+    n_candidates: int
+    feasible: bool
+    report: Dict[str, float]
+
+
+def _criterion_code(criterion, param) -> Tuple[int, float]:
+    if criterion not in CRITERIA:
+        raise ValueError(f"operating_point: unknown criterion {criterion!r} (one of {', '.join(CRITERIA)})")
+    code = CRITERIA.index(criterion)
+    if code >= 3:
+        if param is None or not 0.0 <= float(param) <= 1.0:
+            raise ValueError(f"operating_point: criterion `{criterion}` needs a param in [0, 1], got {param!r}")
+        return code, float(param)
+    return code, 0.0
+
+
+def _operating_call(scores, labels_u8, code: int, param: float, thres: float, pos_cap, curve: bool):
+    """The checks of `rank_report_wide`, the workspace and ONE `ggad_rank_operating_f32` call: (out16 on the device, the three curve
+    tensors or None, pos_cap)."""
+    from . import _lib
+    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+        raise ValueError("operating_point takes float32 scores and uint8 labels of the same 1-D shape")
+    if scores.device.type != "cuda" or labels_u8.device != scores.device:
+        raise ValueError("operating_point takes scores and labels on the same GPU (there is no CPU path)")
+    lib = _lib.load()
+    n = scores.numel()
+    cap = int(lib.ggad_rank_wide_max_pos())
+    if pos_cap is None:
+        pos_cap = max(1, min(n, cap))
+    if int(pos_cap) != pos_cap or not 1 <= int(pos_cap) <= cap:
+        raise ValueError(f"operating_point: pos_cap = {pos_cap} is outside 1..ggad_rank_wide_max_pos() = {cap}")
+    pos_cap = int(pos_cap)
+    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
+    dev = scores.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(1, int(lib.ggad_rank_operating_workspace_elems(n, pos_cap))), dtype=torch.int32, device=dev)
+        out16 = torch.empty(16, dtype=torch.float64, device=dev)
+        cur = None
+        if curve:
+            cur = (torch.empty(pos_cap, dtype=torch.float32, device=dev), torch.empty(pos_cap, dtype=torch.int32, device=dev),
+                   torch.empty(pos_cap, dtype=torch.int32, device=dev))
+        _lib.call("ggad_rank_operating_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, pos_cap, float(thres), code, param,
+                  _lib.ptr(out16), *((_lib.ptr(c) for c in cur) if cur else (0, 0, 0)), _lib.ptr(ws))
+    return out16, cur, pos_cap
+
+
+def _raise_on_status(who: str, status: int, n_pos: int, pos_cap: int) -> None:
+    if status == 3:
+        raise ValueError(f"{who}: a score is NaN")
+    if status == 4:
+        raise ValueError(f"{who}: a label is neither 0 nor 1")
+    if status == 2:
+        raise ValueError(f"{who}: {n_pos} positives are more than pos_cap = {pos_cap} (there is no fallback: pass a pos_cap that "
+                         "bounds them, at most ggad_rank_wide_max_pos())")
+    if status == 1:
+        raise ValueError(_ONE_CLASS)
+
+
+def operating_point(scores: torch.Tensor, labels_u8: torch.Tensor, criterion: str = "f1", param: Optional[float] = None,
+                    thres: float = 0.5, pos_cap: Optional[int] = None) -> OperatingPoint:
+    """The threshold among the distinct scores of the positives that is best under `criterion` (`CRITERIA`; `param`: the bound of
+    `precision` and `fpr`), equal values going to the higher threshold, with its exact confusion counts: one
+    `ggad_rank_operating_f32` call (csrc/rank_metrics.hip) and one read-back of sixteen doubles.  `thres` and `pos_cap` are
+    `rank_report_wide`'s: the call also leaves that report's eight numbers, from which `report` takes AUROC and AP.  `ValueError`
+    for an unknown criterion, a missing or out-of-range `param`, a NaN score, a label other than 0/1, one class only, or more
+    positives than `pos_cap`.  No candidate meets the constraint: `feasible` is false and `thres` is +inf."""
+    code, par = _criterion_code(criterion, param)
+    out16, _, pos_cap = _operating_call(scores, labels_u8, code, par, thres, pos_cap, False)
+    o = out16.cpu().tolist()
+    status = int(o[15])
+    _raise_on_status("operating_point", int(o[7]), int(o[6]), pos_cap)
+    tp, fp, fn, tn = (int(v) for v in o[9:13])
+    return OperatingPoint(thres=float(o[8]), tp=tp, fp=fp, fn=fn, tn=tn, value=float(o[13]), criterion=criterion,
+                          param=None if code < 3 else par, n_candidates=int(o[14]), feasible=status == 0,
+                          report={"auc": float(o[0]), "ap": float(o[1]), **_confusion_scores(tp, fp, fn, tn)})
+
+
+def pr_curve(scores: torch.Tensor, labels_u8: torch.Tensor, pos_cap: Optional[int] = None):
+    """(thres float32, tp int32, fp int32) on the device, one entry per distinct score of a positive, descending: the confusion
+    counts of `score >= thres[i]` (precision tp / (tp + fp), recall tp / tp[-1]).  The kernels store one entry per positive; the
+    runs of equal scores are folded here with `torch.unique_consecutive`, which reads back the number of distinct scores."""
+    out16, cur, pos_cap = _operating_call(scores, labels_u8, 0, 0.0, 0.5, pos_cap, True)
+    o = out16.cpu().tolist()
+    _raise_on_status("pr_curve", int(o[7]), int(o[6]), pos_cap)
+    p = int(o[6])
+    tp, first = torch.unique_consecutive(cur[1][:p], return_inverse=True)      # distinct runs have distinct tp, ascending along j
+    head = torch.ones(p, dtype=torch.bool, device=tp.device)
+    head[1:] = first[1:] != first[:-1]
+    return cur[0][:p][head], tp, cur[2][:p][head]
 
 
 @dataclass

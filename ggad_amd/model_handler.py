@@ -22,6 +22,11 @@ fixed order (`metrics.top_k`, csrc/topk.hip), kept in `self.ranked`, reported in
 ``top_k_wide: true`` (with ``top_k`` > 0): the list is ranked by csrc/topk.hip, K up to 4,194,304 instead of 16,384.
 ``rank_wide: true`` (with ``eval_cache: true``): a validation / test list with more than 8,192 positives is reported from the
 counting kernels of csrc/rank_metrics.hip instead of `binary_report`'s two device sorts.
+``thres_select: CRIT`` (`model: 'GCN'`; f1, f1_macro, gmean, precision:X, fpr:X): after the best checkpoint is restored the validation
+list is scored once more, the alert threshold that is best under CRIT is chosen on the device (`metrics.operating_point`), printed as
+one `[threshold]` line, kept in `self.operating_point`, used by the closing test sweep instead of ``thres`` and written by rank 0 to
+`<checkpoint>.thres.json`; `score(checkpoint)` with the key on reads that file.  The validation list is the reference's -- the test
+split (`src/model_handler.py:260-261`) --, so the threshold, like the checkpoint, is chosen on the list it is then reported on.
 
 The loader and split, the adjacency coercion, the checkpoint rule and the epoch loop of the labelled-batch models (`_train_sage`,
 `_train_sage_device`, `_train_pcgnn` build model, optimiser and containers and hand them to it) live in `handler_loop.py`; the GGAD
@@ -101,7 +106,61 @@ class ModelHandler(object):
                 raise ValueError("config keys `top_k` / `top_k_out` run on one GPU: the ranking is not made under a torch.distributed "
                                  "world of several ranks yet")
         self.ranked = None
+        self.operating_point = None
+        self.thres_select = None                                 # config key `thres_select`: (name, param) of the criterion, else None
+        if str(getattr(args, "thres_select", "") or ""):
+            if getattr(args, "model", None) != "GCN":
+                raise ValueError("config key `thres_select` needs `model: 'GCN'`: the threshold is chosen from the scores of the GGAD "
+                                 "validation sweep")
+            from .metrics import parse_criterion
+            self.thres_select = parse_criterion(args.thres_select)
         self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
+
+    @staticmethod
+    def thres_path(checkpoint):
+        """The side file of config key `thres_select`, next to the checkpoint: settings only (the `.pkl` stays a plain state dict)."""
+        return str(checkpoint) + ".thres.json"
+
+    def _choose_threshold(self, gnn_model, ids, labels, sweep, dist, verbose):
+        """Config key `thres_select`: one more sweep over the validation list under the weights `gnn_model` holds, the operating point
+        of its scores (`metrics.operating_point`: one call, one read-back), one `[threshold]` line; kept in `self.operating_point`.
+        Under a torch.distributed world every rank calls it on the all-reduced scores."""
+        from .metrics import operating_point
+        name, param = self.thres_select
+        if sweep is not None:
+            op = sweep.operating_point(name, param, thres=self.args.thres)
+        else:
+            scores = score_nodes(gnn_model, ids, self.args.batch_size, device=True, dist=dist)
+            lab = np.asarray(labels).reshape(-1).astype(np.uint8)
+            op = operating_point(scores, torch.from_numpy(lab).to(scores.device), name, param, thres=self.args.thres,
+                                 pos_cap=max(1, int(np.count_nonzero(lab == 1))))
+        self.operating_point = op
+        if verbose:
+            print(f"[threshold] {self.args.thres_select}: threshold {op.thres!r}\tvalue {op.value!r}\tTP: {op.tp}\tFP: {op.fp}\tFN: {op.fn}"
+                  f"\tTN: {op.tn}" + ("" if op.feasible else "\t(no candidate meets the constraint: no node alerts)"))
+        return op
+
+    def _write_threshold(self, checkpoint, op, epoch):
+        import json
+        import struct
+        doc = {"criterion": op.criterion, "param": op.param, "thres": op.thres,
+               "thres_bits": struct.unpack("<I", struct.pack("<f", op.thres))[0], "value": op.value,
+               "tp": op.tp, "fp": op.fp, "fn": op.fn, "tn": op.tn, "epoch": int(epoch)}
+        with open(self.thres_path(checkpoint), "w") as fh:
+            json.dump(doc, fh, indent=1)
+            fh.write("\n")
+
+    def _read_threshold(self, checkpoint):
+        """The threshold of the side file, from its bit pattern: exactly the float32 that was chosen."""
+        import json
+        import struct
+        path = self.thres_path(checkpoint)
+        if not os.path.exists(path):
+            raise ValueError(f"config key `thres_select`: {path} not found (it is written next to the checkpoint by a training run "
+                             "with the key on)")
+        with open(path) as fh:
+            doc = json.load(fh)
+        return float(struct.unpack("<f", struct.pack("<I", int(doc["thres_bits"])))[0]), doc
 
     def _build_gcn(self):
         """The GGAD model as `src/model_handler.py:263-296` builds it, shared by `train` and `score`: device, graph (through the
@@ -170,6 +229,9 @@ class ModelHandler(object):
         if k:
             from .metrics import check_k
             check_k(k, "ModelHandler.score", wide=bool(getattr(args, "top_k_wide", False)))
+        thres = args.thres
+        if self.thres_select is not None:                        # config key `thres_select`: report at the threshold chosen in training
+            thres, self.thres_doc = self._read_threshold(checkpoint)
         _, _, _, gnn_model, engine = self._build_gcn()
         self.model = gnn_model
         gnn_model.load_state_dict(torch.load(checkpoint))
@@ -184,7 +246,7 @@ class ModelHandler(object):
         self.metrics, self.sweep_ap = None, []
         if labels is not None:
             keep = []
-            self.metrics = test_sage(ids, labels, gnn_model, args.batch_size, args.thres, resident=sweep, keep=keep)
+            self.metrics = test_sage(ids, labels, gnn_model, args.batch_size, thres, resident=sweep, keep=keep)
             self.sweep_ap.append(getattr(test_sage, "last_ap", None))
             scores = keep[0]
         else:
@@ -315,7 +377,13 @@ class ModelHandler(object):
             engine.sync_params()
         top_k = int(getattr(args, "top_k", 0) or 0)
         keep = [] if top_k else None                 # config key `top_k`: the sweep's device scores are kept and ranked, not made twice
-        res = test_sage(idx_test, y_test, gnn_model, args.batch_size, args.thres, dist=dist, verbose=rank == 0, resident=sweep_test,
+        thres = args.thres
+        if self.thres_select is not None:            # config key `thres_select`: the closing sweep reports at the chosen threshold
+            op = self._choose_threshold(gnn_model, idx_valid, y_valid, sweep_valid, dist, verbose=rank == 0)
+            thres = op.thres
+            if rank == 0 and best.ep_best >= 0:
+                self._write_threshold(best.path_saver, op, best.ep_best)
+        res = test_sage(idx_test, y_test, gnn_model, args.batch_size, thres, dist=dist, verbose=rank == 0, resident=sweep_test,
                         keep=keep)
         self.sweep_ap.append(getattr(test_sage, "last_ap", None))
         if top_k:

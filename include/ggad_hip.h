@@ -1237,6 +1237,42 @@ int ggad_rank_wide_f32(const float *score, const uint8_t *label, int64_t n, int6
                        int32_t *workspace, ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * The operating point of a score: the alert threshold that is best under a criterion, with its exact confusion counts
+ * (rank_metrics.hip).  The front is ggad_rank_wide_f32's (scan, sorted runs, merge passes, tile bucket); the last two launches also
+ * form, for every run of equal positives pos[s..e], tp = P - s and fp = Nn - L (L = the negatives strictly below it), and take the
+ * arg-max.  The distinct positive scores are the complete candidate set: a threshold between two of them only adds false positives
+ * to the next positive score above it.  +-0.0 count as one score.
+ *
+ * criterion (ggad_rank_operating_criteria() = 5 of them), with fn = P - tp and tn = Nn - fp:
+ *   0 f1         maximise 2tp / (2tp + fp + fn)                                    compared cross-multiplied in int64 (< 2^54)
+ *   1 f1_macro   maximise 0.5 (f1 + 2tn / (2tn + fn + fp)), a zero denominator = 0  compared in float64, each class F1 ONE division
+ *   2 gmean      maximise tp tn (reported: sqrt(tp tn / (P Nn)))                    compared in int64 (< 2^51)
+ *   3 precision  the greatest recall with (double)tp >= param (double)(tp + fp)     reported: tp / P
+ *   4 fpr        the greatest recall with (double)fp <= param (double)Nn            reported: tp / P
+ * Equal criterion values: the HIGHER threshold (fewer alerts).  The order of candidates is total, the reduction (per thread, a
+ * tree over the workgroup, a tree over the tiles) fixed: equal inputs give equal bits.  param is ignored for 0..2 and must lie in
+ * [0, 1] for 3 and 4.
+ *
+ * out16: [0..7] the eight doubles ggad_rank_wide_f32(score, label, n, pos_cap, thres, ...) writes, bit for bit; [8] the chosen
+ * threshold, a positive's float32 score widened (a zero of either sign); [9..12] tp, fp, fn, tn of score >= [8]; [13] the
+ * criterion's value; [14] the number of distinct positive scores; [15] status: 0 = chosen, 5 = no candidate meets the constraint
+ * ([8] = +inf, tp = fp = 0, fn = P, tn = Nn, [13] = 0), or [7] when [7] != 0 ([8..14] NaN).
+ * curve_thres / curve_tp / curve_fp: all NULL, or all pos_cap long; entry j < P = threshold, tp, fp of the run that holds the j-th
+ * highest positive (descending, equal inside a tie run, nothing compacted); entries from P on are left untouched.
+ *
+ * Limits, alignment and workspace rule of ggad_rank_wide_f32 (0 <= n <= INT32_MAX, 1 <= pos_cap <= ggad_rank_wide_max_pos(), 16-byte
+ * aligned workspace of ggad_rank_operating_workspace_elems(n, pos_cap) int32 elements, 0 = refused, no preparation needed); outside
+ * them, or with an unknown criterion, a param outside [0, 1] (or NaN) for 3 and 4, or one or two curve pointers: GGAD_E_INVALID and
+ * no launch.  The same number of launches on `stream`, no host synchronisation, no floating-point atomics, nothing that waits on
+ * another workgroup; every word a launch reads was written by an earlier launch of the same call: capturable and replayable.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_rank_operating_criteria(void);
+int64_t ggad_rank_operating_workspace_elems(int64_t n, int64_t pos_cap);   /* int32 elements; 0 = refused */
+int ggad_rank_operating_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, int32_t criterion,
+                            double param, double *out16, float *curve_thres, int32_t *curve_tp, int32_t *curve_fp,
+                            int32_t *workspace, ggad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Keep the best epoch's weights on the device (select.hip): the hand-off "if this epoch's validation metric is the best so far,
  * snapshot the parameters" without a host round trip.  Neither call takes a workspace; each reads only words the host or an earlier
  * launch wrote, so both are capturable and replayable behind ggad_rank_metrics_f32 / ggad_rank_wide_f32 in a captured epoch.

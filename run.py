@@ -24,9 +24,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ggad_amd.fullgraph import FlatAdam, ggad_loss  # noqa: E402
-from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, add_select_options, check_select_options, init_process, load_graph,  # noqa: E402,F401
-                                       make_parser, parse_with_defaults, prepare, print_captured, print_eval, print_median,
-                                       save_checkpoint, score_from_checkpoint, select_options)
+from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, add_select_options, add_threshold_options, check_select_options,  # noqa: E402,F401
+                                       check_threshold_options, choose_threshold, init_process, load_graph, make_parser,
+                                       parse_with_defaults, prepare, print_captured, print_eval, print_median, print_threshold_test,
+                                       save_checkpoint, score_from_checkpoint, select_options, threshold_option)
 from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
 from ggad_amd.model import Model  # noqa: E402
 
@@ -42,7 +43,8 @@ def parse(argv=None):
     p.add_argument("--mean", type=float, default=0.0)
     p.add_argument("--var", type=float, default=0.0)
     add_select_options(p)
-    a = check_select_options(p, parse_with_defaults(p, argv, {}, EPOCHS, fallback=(1e-3, 100)))
+    add_threshold_options(p)
+    a = check_threshold_options(p, check_select_options(p, parse_with_defaults(p, argv, {}, EPOCHS, fallback=(1e-3, 100))))
     a.mean, a.var = (0.02, 0.01) if a.dataset in ["reddit", "photo"] else (0.0, 0.0)      # run.py:61-66 (CLI values overwritten)
     return a
 
@@ -222,9 +224,20 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
         auc, ap = print_eval(args.dataset, best_scores.index_select(0, idx_test_dev), y_test_dev, prefix="[select] best epoch: ")
         if history is not None:
             history["best_scores"], history["best_auc"], history["best_ap"] = best_scores.cpu().numpy(), auc, ap
+    point = None
+    if threshold_option(args):                   # `model` holds the weights that --save writes: the kept epoch's, else the last epoch's
+        if idx_val is None:
+            raise ValueError("--threshold chooses on idx_val: pass fit(..., idx_val=...)")
+        model.eval()
+        with torch.no_grad():
+            all_scores = model.score(feats, full).detach()
+        point = choose_threshold(threshold_option(args), all_scores, idx_val, ano_label, dev)
+        print_threshold_test(all_scores.index_select(0, idx_test_dev), y_test_dev, point.thres)
+        if history is not None:
+            history["threshold"], history["threshold_scores"] = point, all_scores.cpu().numpy()
     if save:
         state = keeper.state_dict(model) if keeper is not None else model.state_dict()
-        save_checkpoint(save, state, args, feats.shape[2], nb_nodes, best_epoch, best_value)
+        save_checkpoint(save, state, args, feats.shape[2], nb_nodes, best_epoch, best_value, threshold=point)
         print("weights of epoch {:04d} written to {}".format(best_epoch, save))
 
 

@@ -136,6 +136,9 @@ if __name__ == "__main__":
                     help="override the config's rank_wide (with eval_cache: exact rank metrics in HIP above 8,192 positives)")
     ap.add_argument("--top_k_wide", action="store_true", default=None,
                     help="override the config's top_k_wide (with top_k: rank through csrc/topk.hip, K above 16384 up to 4194304)")
+    ap.add_argument("--thres_select", type=str, default=None, metavar="CRIT",
+                    help="override the config's thres_select (choose the alert threshold on the device: f1, f1_macro, gmean, "
+                         "precision:X, fpr:X)")
     ap.add_argument("--score_ids", type=str, default=None, metavar="FILE.npy",
                     help="with --score: sweep and rank this int64 id list (np.save) instead of the test split; no labels, so no report: "
                          "with top_k it is the ranked list of these ids (every node of the graph, for instance)")
@@ -158,6 +161,8 @@ if __name__ == "__main__":
         cfg["rank_wide"] = a.rank_wide
     if a.top_k_wide is not None:
         cfg["top_k_wide"] = a.top_k_wide
+    if a.thres_select is not None:
+        cfg["thres_select"] = a.thres_select
     SCORE, SCORE_IDS = a.score, a.score_ids
     use_handler(a.handler)
     init_distributed()
