@@ -292,6 +292,10 @@ SIGNATURES = {
     "ggad_select_max_tensors": (c_int32, []),
     "ggad_select_decide_f64": (c_int32, [_P, _I, _P, _P, _L, _P]),
     "ggad_select_copy_f32": (c_int32, [_I, _P, _P, _P, _P, _P]),
+    "ggad_explain_max_nbrs": (c_int32, []),
+    "ggad_explain_lds_rows": (c_int32, []),
+    "ggad_explain_workspace_elems": (c_int64, [_L, _L, _I]),
+    "ggad_explain_f32": (c_int32, [_P, _P, _I, _P, _P, _I, _I, _P, _L, _I, _P, _I, _I, _I] + [_P] * 10),
 }
 
 

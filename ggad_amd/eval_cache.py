@@ -129,3 +129,10 @@ class ResidentSweep:
         `wide`: `metrics.top_k(..., wide=True)`, k above 16,384 up to a full ranking of the list."""
         from .metrics import top_k
         return top_k(self.scores() if scores is None else scores, k, self.labels, self.ids, wide=wide)
+
+    def explain(self, ranked_or_positions, m: int):
+        """`explain.explain` of positions of this sweep (a `Ranked` of `top_k`, or a device tensor of positions) with the sweep's ids and
+        `batch_size` under the current weights: the `Explanation`, `m` neighbours listed per row.  Nothing is uploaded and no plan is
+        built; the kernel reads the graph and the feature table, not the cached rows."""
+        from .explain import explain
+        return explain(self.model, self.ids, self.batch_size, ranked_or_positions, m)

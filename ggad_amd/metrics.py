@@ -364,8 +364,6 @@ def write_ranked(path, ranked, labels=None):
     """The `.npz` of config key `top_k_out`: `node` int64, `score` float32, `label` uint8, `cum_positives` int32 (both empty without
     labels), `n_pos`, `tied_left_out`.  `labels`: the labels of the scored list, indexed by `ranked.pos`.  Entries are stored with a
     fixed date, so equal rankings give equal files byte for byte."""
-    import zipfile
-
     import numpy as np
     pos = ranked.pos.cpu().numpy()
     has = labels is not None and ranked.cum_pos is not None
@@ -373,6 +371,15 @@ def write_ranked(path, ranked, labels=None):
               "label": np.asarray(labels).reshape(-1)[pos].astype(np.uint8) if has else np.zeros(0, dtype=np.uint8),
               "cum_positives": ranked.cum_pos.cpu().numpy().astype(np.int32) if has else np.zeros(0, dtype=np.int32),
               "n_pos": np.int64(ranked.n_pos), "tied_left_out": np.int64(ranked.tied_left_out)}
+    write_npz_fixed_date(path, arrays)
+
+
+def write_npz_fixed_date(path, arrays) -> None:
+    """An uncompressed `.npz` of `arrays` (name -> array, in this order) whose entries carry a fixed date: equal arrays give equal
+    files byte for byte (`write_ranked`, `explain.write_explained`)."""
+    import zipfile
+
+    import numpy as np
     with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
         for name, a in arrays.items():
             with z.open(zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), "w", force_zip64=True) as fh:

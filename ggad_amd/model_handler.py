@@ -27,6 +27,9 @@ list is scored once more, the alert threshold that is best under CRIT is chosen 
 one `[threshold]` line, kept in `self.operating_point`, used by the closing test sweep instead of ``thres`` and written by rank 0 to
 `<checkpoint>.thres.json`; `score(checkpoint)` with the key on reads that file.  The validation list is the reference's -- the test
 split (`src/model_handler.py:260-261`) --, so the threshold, like the checkpoint, is chosen on the list it is then reported on.
+``explain: M`` / ``explain_out`` (with ``top_k`` > 0): every node of the ranked list is explained on the device (`explain.explain`,
+csrc/explain.hip): its logit split exactly per feature and per neighbour, the M signed-greatest neighbour contributions listed; kept in
+`self.explained`, reported in one `[explain]` line and written to an `.npz`; after `train()` and by `score(checkpoint)` alike.
 
 The loader and split, the adjacency coercion, the checkpoint rule and the epoch loop of the labelled-batch models (`_train_sage`,
 `_train_sage_device`, `_train_pcgnn` build model, optimiser and containers and hand them to it) live in `handler_loop.py`; the GGAD
@@ -105,7 +108,18 @@ class ModelHandler(object):
             if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                 raise ValueError("config keys `top_k` / `top_k_out` run on one GPU: the ranking is not made under a torch.distributed "
                                  "world of several ranks yet")
+        explain_m, explain_out = getattr(args, "explain", 0) or 0, str(getattr(args, "explain_out", "") or "")
+        if explain_m or explain_out:
+            if not top_k:
+                raise ValueError("config keys `explain` / `explain_out` need `top_k: K` with K > 0: `explain` explains the nodes of the "
+                                 "ranked list (there is no list while `top_k` is 0)")
+            if not explain_m:
+                raise ValueError("config key `explain_out` needs `explain: M` with M > 0: there is no explanation to write while "
+                                 "`explain` is 0")
+            from .explain import check_m
+            check_m(explain_m, "config key `explain`")
         self.ranked = None
+        self.explained = None
         self.operating_point = None
         self.thres_select = None                                 # config key `thres_select`: (name, param) of the criterion, else None
         if str(getattr(args, "thres_select", "") or ""):
@@ -189,10 +203,12 @@ class ModelHandler(object):
         engine.sync_params()
         return dev, graph, features, gnn_model, engine
 
-    def _rank(self, scores, ids, labels, sweep, k, verbose=True):
+    def _rank(self, scores, ids, labels, sweep, k, verbose=True, model=None):
         """Config key `top_k` / `score(k=)`: the `Ranked` head of `scores` (the device scores of a sweep over `ids`, already made: nothing
         is scored again), kept in `self.ranked`; one printed line; the `.npz` of config key `top_k_out`.  Config key `top_k_wide`: ranked
-        by `ggad_topk_wide_f32` (K above 16,384)."""
+        by `ggad_topk_wide_f32` (K above 16,384).  Config key `explain: M` (`model`: the `GCN` whose sweep made `scores`): every ranked
+        node is explained under the weights that scored it (`explain.explain`, csrc/explain.hip), kept in `self.explained`; one
+        `[explain]` line; the `.npz` of config key `explain_out`."""
         from .metrics import precision_recall_at, top_k
         wide = bool(getattr(self.args, "top_k_wide", False))
         if sweep is not None:
@@ -211,6 +227,20 @@ class ModelHandler(object):
             out = str(getattr(self.args, "top_k_out", "") or "")
             if out:
                 write_ranked(out, ranked, labels)
+        explain_m = int(getattr(self.args, "explain", 0) or 0)
+        if explain_m:
+            from .explain import explain, write_explained
+            if sweep is not None:
+                ex = sweep.explain(ranked, explain_m)
+            else:
+                ex = explain(model, np.asarray(ids, dtype=np.int64).reshape(-1), self.args.batch_size, ranked, explain_m)
+            self.explained = ex
+            if verbose:
+                print(f"[explain] rows explained {ex.rows}\tneighbours listed {ex.m}\tmax |z - sum_j t_j| {ex.completeness():.3e}"
+                      f"\trows on the workspace branch {ex.rows_workspace}")
+                out = str(getattr(self.args, "explain_out", "") or "")
+                if out:
+                    write_explained(out, ranked, ex)
         return ranked
 
     def score(self, checkpoint, ids=None, labels=None, k=None):
@@ -252,7 +282,7 @@ class ModelHandler(object):
         else:
             scores = sweep.scores() if sweep is not None else score_nodes(gnn_model, ids, args.batch_size, device=True)
         self.test_scores = scores
-        self.ranked = self._rank(scores, ids, labels, sweep, k) if k else None
+        self.ranked = self._rank(scores, ids, labels, sweep, k, model=gnn_model) if k else None
         return scores, self.ranked
 
     def train(self):
@@ -388,7 +418,7 @@ class ModelHandler(object):
         self.sweep_ap.append(getattr(test_sage, "last_ap", None))
         if top_k:
             self.test_scores = keep[0]
-            self._rank(keep[0], idx_test, y_test, sweep_test, top_k, verbose=rank == 0)
+            self._rank(keep[0], idx_test, y_test, sweep_test, top_k, verbose=rank == 0, model=gnn_model)
         return res
 
 

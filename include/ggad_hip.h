@@ -1293,6 +1293,45 @@ int ggad_select_decide_f64(const double *out8, int32_t which, double *state4, do
 int ggad_select_copy_f32(int32_t n, const float *const *src, float *const *dst, const int64_t *numel, const double *state4,
                          ggad_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Explain ranked alerts (explain.hip): the exact per-feature and per-neighbour attribution of the inference logit of the mini-batch
+ * GGAD model.  With a = W x1_i, z = sum_d w_d relu(a[d]) (the score is sigmoid(z): k_score) and g[f] = sum_d w_d [a[d] > 0] W[d, f]:
+ *   z = sum_f g[f] x1_i[f]  =  sum_{j in N(i)+{i}} omega_ij (g . feat[j]),   omega_ij = (1 / sqrt(r_i)) / sqrt(c_j),
+ * r_i the size of the closed row of i, c_j the rows (with multiplicity) of row i's slice of `batch_size` ids whose closed row holds j.
+ * Both sums are complete -- no baseline, no sampling -- and exact on the ReLU pattern the row has: they explain the logit, not a
+ * counterfactual.  One launch, one workgroup per explained position; nothing but the arguments is read (no plan, no cached row).
+ *
+ * rowptr / col: int32 CSR of n_nodes rows, columns sorted and distinct; feat: n_nodes x F floats, rows F apart; params: the engine's
+ * parameter block after ggad_mb_params_sync (D, F as there); ids: the scored list, int64[n], n <= INT32_MAX, its slices are
+ * [s, min(n, s + batch_size)) for s = 0, batch_size, ...; positions: int32[K] indices into ids (a position may stand twice);
+ * 1 <= m <= ggad_explain_max_nbrs() (32) neighbours are listed per row.  Any D, F of ggad_mb_wide_supported (D <= 256, F <= 1,024);
+ * another (D, F, m): GGAD_E_UNSUPPORTED, nothing launched.  Channel d = lane + 64 j belongs to lane `lane` of wave j (the wide
+ * convention) at every D.
+ * Per position k:  out_logit[k] = z;  out_feature[k * F + f] = g[f] x1[f];  out_closed_size[k] = r;  out_nbr_id / out_nbr_contrib /
+ * out_nbr_colcount [k * m + c], c < min(m, r): the c-th greatest t_j = omega_ij (g . feat[j]) -- signed: what pushed the score UP; equal
+ * values (-0.0 = +0.0) by ascending id -- with its node id (int64) and c_j; the other slots hold -1 / 0 / 0;  out_rest[k]: the sum of
+ * the t_j that are not listed.  Every float sum has one fixed order (x1: pieces of the id-ascending list, fma in ascending j, pieces
+ * ascending; a: fma over f ascending; z, g: d ascending; t_j: f ascending; rest: pieces ascending); the c_j are integers counted with
+ * integer atomics: equal inputs give equal bits.
+ * Rows of up to ggad_explain_lds_rows() (12,288) entries keep ids, counters and contributions in LDS (sized per launch for
+ * min(n_rows_max_closed, 12,288) entries: a tight bound leaves room for more workgroups per CU); longer rows keep them in the
+ * workspace.  workspace: ggad_explain_workspace_elems(n_rows_max_closed, K, m) int32 elements (0 = refused), no preparation needed,
+ * n_rows_max_closed = S >= every explained closed row (deg + 1 bounds it).  After the call: float t_j at [k * S + q], int32 c_j at
+ * [K * S + k * S + q], q < r the index in the id-ascending closed row (the rest of the workspace is scratch).
+ * out_meta (device, 4 x int64; cleared by the call): {status, rows explained, rows that took the workspace branch, 0}.  status 0: fine;
+ * 2: a closed row is longer than n_rows_max_closed (its slot: closed_size = r, everything else padding); 3: a NaN feature or weight on
+ * an explained row; 5: a position outside 0..n-1 or an id that is no node (a position's slot: padding, closed_size 0).  The greatest
+ * status of any row stands.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_explain_max_nbrs(void);
+int32_t ggad_explain_lds_rows(void);
+int64_t ggad_explain_workspace_elems(int64_t n_rows_max_closed, int64_t K, int32_t m);   /* int32 elements; 0 = refused */
+int ggad_explain_f32(const int32_t *rowptr, const int32_t *col, int32_t n_nodes, const float *feat, const float *params, int32_t D,
+                     int32_t F, const int64_t *ids, int64_t n, int32_t batch_size, const int32_t *positions, int32_t K, int32_t m,
+                     int32_t n_rows_max_closed, float *out_logit, float *out_feature, int32_t *out_closed_size, int64_t *out_nbr_id,
+                     float *out_nbr_contrib, int32_t *out_nbr_colcount, float *out_rest, int64_t *out_meta, int32_t *workspace,
+                     ggad_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

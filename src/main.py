@@ -132,6 +132,10 @@ if __name__ == "__main__":
                          "config's seed, print its report and, with top_k > 0, the ranked list")
     ap.add_argument("--top_k", type=int, default=None, help="override the config's top_k (rank the K highest test scores; 0 = off)")
     ap.add_argument("--top_k_out", type=str, default=None, help="override the config's top_k_out (.npz of the ranked list)")
+    ap.add_argument("--explain", type=int, default=None, metavar="M",
+                    help="override the config's explain (with top_k: explain every ranked node exactly, per feature and per neighbour, "
+                         "listing the M signed-greatest neighbour contributions; 0 = off)")
+    ap.add_argument("--explain_out", type=str, default=None, metavar="F", help="override the config's explain_out (.npz of the explanation)")
     ap.add_argument("--rank_wide", action="store_true", default=None,
                     help="override the config's rank_wide (with eval_cache: exact rank metrics in HIP above 8,192 positives)")
     ap.add_argument("--top_k_wide", action="store_true", default=None,
@@ -157,6 +161,10 @@ if __name__ == "__main__":
         cfg["top_k"] = a.top_k
     if a.top_k_out is not None:
         cfg["top_k_out"] = a.top_k_out
+    if a.explain is not None:
+        cfg["explain"] = a.explain
+    if a.explain_out is not None:
+        cfg["explain_out"] = a.explain_out
     if a.rank_wide is not None:
         cfg["rank_wide"] = a.rank_wide
     if a.top_k_wide is not None:
