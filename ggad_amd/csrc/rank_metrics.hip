@@ -42,6 +42,13 @@
 //                the confusion counts of `score >= pos[k]`): the curve stores, the best candidate per thread, a tree over the workgroup
 //   k_ro_final   k_rw_final's tree into out16[0..7] and a tree over the tiles' candidates into out16[8..15]
 // At 8,192 positives or fewer that is one tile and no merge pass, so there is no narrow chain for it.
+//
+// ggad_rank_delong_f32 / ggad_rank_delong_pair_f32: the same front (twice for the pair, into two halves of the workspace) and
+//   k_rd_terms   k_rw_terms' sums in its order, and the tile's exact 128-bit share of sum a^2 (positives) and sum b^2 (negatives, from
+//                the two histograms alone); the pair's variant also stores L_k per sorted rank
+//   k_rd_cross   pair only: every element looks its key up in both models' sorted keys and adds a^A a^B or b^A b^B in 128 bits
+//   k_rd_final / k_rd_pair_final   k_rw_final's tree with the 128-bit sums beside it; the variance numerators, each converted ONCE
+// (the formulas: above k_rd_terms, further down)
 // Why runs of 2,048 and a merge by rank: head of rank_common.h.  Why the narrow chain stays although the wide one is twice as fast at
 // DGraph-Fin's size: inside a captured training epoch (run.py --select) a validation list of 3,935 nodes costs the wide chain six
 // launches against four, and the epoch is 21 us longer (profiles/rank_one_chain_time_line.json).
@@ -710,6 +717,333 @@ int rw_front(const float *score, const uint8_t *label, int64_t n, int64_t pos_ca
   return GGAD_OK;
 }
 
+// ---- DeLong's variance of the AUROC, and the covariance of two AUROCs on the same labels (ggad_rank_delong_f32, _pair_f32).
+// With m = P, n = Nn, a_k = 2 L_k + E_k per positive and b_j = 2 #{pos > y_j} + #{pos == y_j} per negative (the placements, doubled):
+//     S1 = sum a = sum b (the AUROC numerator)    S2 = sum a^2    T2 = sum b^2    N10 = m S2 - S1^2    N01 = n T2 - S1^2
+//     var = N10 / (4 n^2 m^2 (m - 1)) + N01 / (4 m^2 n^2 (n - 1))
+// and for two models C10 = sum_i a_i^A a_i^B, C01 = sum_j b_j^A b_j^B by ELEMENT; the variance of the difference has numerators of
+// its own, ND10 = m (S2A + S2B - 2 C10) - (S1A - S1B)^2 and ND01 alike, so nothing cancels in floating point.  Every sum is an exact
+// integer below 2^106 (a, b <= 2^32, m <= 2^20) in 128 bits; each numerator is converted to float64 ONCE (rd_to_double).  Integer
+// sums: the shape of a reduction does not move a bit.
+typedef unsigned __int128 rd_u128;
+typedef __int128 rd_i128;
+
+constexpr int RD_SQ = 4;                  // uint64 per tile of k_rd_terms: S2 lo, hi, T2 lo, hi
+constexpr int RD_XG = 256;                // workgroups of k_rd_cross at most; threads of k_rd_pair_final
+constexpr int RD_XP = 4;                  // uint64 per workgroup of k_rd_cross: C10 lo, hi, C01 lo, hi
+
+static_assert(RD_XG >= RW_TMAX, "k_rd_pair_final reduces the tiles and the cross partials with the same threads");
+
+struct RdLayout {                         // behind the run-merge chain's words; the pair call holds two halves, then the cross partials
+  RwLayout L;
+  int64_t o_sq() const { return (L.total() + 3) & ~(int64_t)3; }                  // RD_SQ uint64 per tile
+  int64_t total() const { return o_sq() + 2 * (int64_t)RD_SQ * RW_TMAX; }
+  int64_t o_lt() const { return total(); }                                        // pair only: Lt[pc]
+  int64_t half() const { return (o_lt() + L.pc + 3) & ~(int64_t)3; }
+  int64_t o_cross() const { return 2 * half(); }
+  int64_t total_pair() const { return o_cross() + 2 * (int64_t)RD_XP * RD_XG; }
+};
+
+// x as a float64, rounded once: the top 64 bits with a sticky bit below them (11 bits more than the significand holds)
+__device__ __forceinline__ double rd_to_double(rd_u128 x) {
+  const uint64_t hi = (uint64_t)(x >> 64);
+  if (hi == 0) return (double)(uint64_t)x;
+  const int sh = __clzll((long long)hi);
+  const rd_u128 y = x << sh;
+  const uint64_t top = (uint64_t)(y >> 64) | ((uint64_t)y != 0 ? 1ull : 0ull);
+  return ldexp((double)top, 64 - sh);
+}
+__device__ __forceinline__ double rd_to_double_signed(rd_i128 x) { return x < 0 ? -rd_to_double((rd_u128)(-x)) : rd_to_double((rd_u128)x); }
+
+// k_rw_terms' sums in k_rw_terms' order (the same out8 bits), and beside them, exact in 128 bits, the tile's share of S2 and T2.
+// T2 needs no pass over the negatives: the hu[ub] negatives of bin ub have b = 2 (P - ub), except the he[ub - 1] of them that tie
+// with the run [s, e = ub - 1] of equal positives (he is non-zero only at a run's end), which have b = 2 (P - ub) + (e - s + 1).
+// Who owns a bin: bin ub >= 1 goes with positive k = ub - 1, so bin base + len goes to THIS tile, bin base to the tile before it, and
+// bin P to the last tile; bin 0 (b = 2 P) goes to tile 0.  PAIR also stores Lt[k] = L_k for k_rd_cross.
+template <bool PAIR>
+__device__ __forceinline__ void rd_terms_tile(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                              const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                              int64_t *__restrict__ part_num, uint64_t *__restrict__ part_sq, int32_t *__restrict__ lt) {
+  constexpr int CH = RW_TILE / RW_T;
+  __shared__ RkScan S;
+  __shared__ double red[RW_T];
+  __shared__ int64_t redi[RW_T];
+  __shared__ rd_u128 rs2[RW_T], rt2[RW_T];
+  if (meta[5] != 0) return;
+  const int t = threadIdx.x;
+  const int P = meta[4];
+  const int base = blockIdx.x * RW_TILE;
+  if (base >= P) return;
+  const int64_t Nn = (int64_t)meta[1] + meta[3];
+  const int32_t *hu = hist, *he = hist + (pc + 1);
+  int32_t mine = 0;
+  const int4 *hu4 = reinterpret_cast<const int4 *>(hu);
+  for (int i = t; i < base / 4; i += RW_T) { const int4 v = hu4[i]; mine += v.x + v.y + v.z + v.w; }
+  const int64_t before_all = rk_block_sum(S.wsum, mine);
+  int64_t loc[CH];
+  int64_t run = 0;
+#pragma unroll
+  for (int j = 0; j < CH; ++j) {
+    const int k = base + t * CH + j;
+    if (k < P) run += hu[k];
+    loc[j] = run;
+  }
+  const int64_t before = before_all + (rk_block_scan(S, (int32_t)run, nullptr) - (int32_t)run);
+  double ap = 0.0;
+  int64_t num = 0;
+  rd_u128 s2 = 0, t2 = 0;
+  if (base == 0 && t == 0) t2 = (rd_u128)(uint64_t)hu[0] * (uint64_t)(4 * (int64_t)P * P);
+#pragma unroll
+  for (int j = 0; j < CH; ++j) {
+    const int k = base + t * CH + j;
+    if (k >= P) continue;
+    const int64_t L = before + loc[j];
+    const uint32_t key = keys[k];
+    int s = k, e = k;
+    if (k > 0 && keys[k - 1] == key) s = rk_lower(keys, 0, k - 1, key);
+    if (k + 1 < P && keys[k + 1] == key) e = rk_upper(keys, k + 2, P, key) - 1;
+    const int64_t G = P - s;
+    const int64_t a = 2 * L + he[e];
+    num += a;
+    ap += (double)G / (double)(G + Nn - L);
+    s2 += (rd_u128)(uint64_t)a * (uint64_t)a;
+    const int64_t in_bin = hu[k + 1], tied = he[k];               // bin k + 1 <= P <= pc
+    const uint64_t b0 = 2 * (uint64_t)(P - k - 1), b1 = b0 + (uint64_t)(k - s + 1);
+    t2 += (rd_u128)(uint64_t)(in_bin - tied) * (b0 * b0) + (rd_u128)(uint64_t)tied * (b1 * b1);
+    if constexpr (PAIR) lt[k] = (int32_t)L;
+  }
+  red[t] = ap;
+  redi[t] = num;
+  rs2[t] = s2;
+  rt2[t] = t2;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) { red[t] += red[t + d];  redi[t] += redi[t + d];  rs2[t] += rs2[t + d];  rt2[t] += rt2[t + d]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    part_ap[blockIdx.x] = red[0];
+    part_num[blockIdx.x] = redi[0];
+    uint64_t *o = part_sq + (int64_t)blockIdx.x * RD_SQ;
+    o[0] = (uint64_t)rs2[0];  o[1] = (uint64_t)(rs2[0] >> 64);  o[2] = (uint64_t)rt2[0];  o[3] = (uint64_t)(rt2[0] >> 64);
+  }
+}
+
+__global__ void __launch_bounds__(RW_T) k_rd_terms(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                                   const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                                   int64_t *__restrict__ part_num, uint64_t *__restrict__ part_sq) {
+  rd_terms_tile<false>(meta, keys, pc, hist, part_ap, part_num, part_sq, nullptr);
+}
+
+__global__ void __launch_bounds__(RW_T) k_rd_terms_lt(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                                      const int32_t *__restrict__ hist, double *__restrict__ part_ap,
+                                                      int64_t *__restrict__ part_num, uint64_t *__restrict__ part_sq,
+                                                      int32_t *__restrict__ lt) {
+  rd_terms_tile<true>(meta, keys, pc, hist, part_ap, part_num, part_sq, lt);
+}
+
+// One model's words for k_rd_cross and the finals
+struct RdModel {
+  const int32_t *meta, *hist;
+  const uint32_t *keys;
+  const int32_t *lt;
+  const double *part_ap;
+  const int64_t *part_num;
+  const uint64_t *part_sq;
+};
+
+// the doubled placement of one element under one model: a for a positive (only the upper bound: its own key is among the keys), b for
+// a negative (the second search only on a tie)
+__device__ __forceinline__ uint64_t rd_placement(const RdModel &M, int P, int pc, uint32_t key, bool is_pos) {
+  const int ub = rk_upper(M.keys, 0, P, key);
+  if (is_pos) return ub > 0 ? 2 * (uint64_t)M.lt[ub - 1] + (uint64_t)M.hist[(pc + 1) + ub - 1] : 0;
+  uint64_t b = 2 * (uint64_t)(P - ub);
+  if (ub > 0 && M.keys[ub - 1] == key) b += (uint64_t)(ub - rk_lower(M.keys, 0, ub - 1, key));
+  return b;
+}
+
+// C10 and C01 over the n elements: both models' sorted keys (at most 4 MB each, L2-resident) searched per element, as k_rw_merge
+// searches them.  Per thread, a tree over the workgroup, then k_rd_pair_final's tree over the workgroups.
+__global__ void __launch_bounds__(RW_T) k_rd_cross(const float *__restrict__ score_a, const float *__restrict__ score_b,
+                                                   const uint8_t *__restrict__ label, int64_t n, int pc, RdModel A, RdModel B,
+                                                   uint64_t *__restrict__ part_x) {
+  __shared__ rd_u128 r10[RW_T], r01[RW_T];
+  if (A.meta[5] != 0 || B.meta[5] != 0) return;
+  const int t = threadIdx.x;
+  const int P = A.meta[4];                                        // (the same labels: B's is the same)
+  rd_u128 c10 = 0, c01 = 0;
+  for (int64_t i = (int64_t)blockIdx.x * RW_T + t; i < n; i += (int64_t)gridDim.x * RW_T) {
+    const bool is_pos = label[i] != 0;
+    const uint64_t pa = rd_placement(A, P, pc, rk_key(score_a[i]), is_pos), pb = rd_placement(B, P, pc, rk_key(score_b[i]), is_pos);
+    const rd_u128 prod = (rd_u128)pa * pb;
+    if (is_pos) c10 += prod; else c01 += prod;
+  }
+  r10[t] = c10;
+  r01[t] = c01;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) { r10[t] += r10[t + d];  r01[t] += r01[t + d]; }
+    __syncthreads();
+  }
+  if (t == 0) {
+    uint64_t *o = part_x + (int64_t)blockIdx.x * RD_XP;
+    o[0] = (uint64_t)r10[0];  o[1] = (uint64_t)(r10[0] >> 64);  o[2] = (uint64_t)r01[0];  o[3] = (uint64_t)(r01[0] >> 64);
+  }
+}
+
+struct RdLds {                                                    // the trees of the two finals (RD_XG >= RW_TMAX slots)
+  double red[RD_XG];
+  int64_t redi[RD_XG];
+  rd_u128 x[RD_XG], y[RD_XG];
+};
+
+struct RdSums {
+  int64_t s1;
+  double ap;
+  rd_u128 s2, t2;
+};
+
+// k_rw_final's halving tree over the tiles (the same bits of the AP sum), with S2 and T2 beside it; the result for every thread
+__device__ __forceinline__ RdSums rd_tile_tree(RdLds &T, const RdModel &M) {
+  const int t = threadIdx.x;
+  const int Tn = M.meta[5] == 0 ? M.meta[6] : 0;
+  __syncthreads();                                                // (an earlier tree's result has been read)
+  if (t < RW_TMAX) {
+    const bool in = t < Tn;
+    const uint64_t *q = M.part_sq + (int64_t)t * RD_SQ;
+    T.red[t] = in ? M.part_ap[t] : 0.0;
+    T.redi[t] = in ? M.part_num[t] : 0;
+    T.x[t] = in ? ((rd_u128)q[1] << 64) | q[0] : (rd_u128)0;
+    T.y[t] = in ? ((rd_u128)q[3] << 64) | q[2] : (rd_u128)0;
+  }
+  __syncthreads();
+  for (int d = RW_TMAX / 2; d > 0; d >>= 1) {
+    if (t < d) { T.red[t] += T.red[t + d];  T.redi[t] += T.redi[t + d];  T.x[t] += T.x[t + d];  T.y[t] += T.y[t + d]; }
+    __syncthreads();
+  }
+  RdSums R;
+  R.s1 = T.redi[0];  R.ap = T.red[0];  R.s2 = T.x[0];  R.t2 = T.y[0];
+  return R;
+}
+
+__device__ __forceinline__ void rd_store_limbs(int64_t *__restrict__ sums, int at, rd_u128 v) {
+  sums[2 * at] = (int64_t)(uint64_t)v;
+  sums[2 * at + 1] = (int64_t)(uint64_t)(v >> 64);
+}
+
+// 4 n^2 m^2 (m - 1) and 4 m^2 n^2 (n - 1) in float64
+__device__ __forceinline__ double rd_den(double m, double n, double side) { return 4.0 * n * n * m * m * (side - 1.0); }
+
+__global__ void __launch_bounds__(RW_TMAX) k_rd_final(RdModel M, double *__restrict__ out16, int64_t *__restrict__ sums) {
+  __shared__ RdLds T;
+  const RdSums R = rd_tile_tree(T, M);
+  if (threadIdx.x != 0) return;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  rm_write_out8(M.meta, R.s1, R.ap, out16);
+  const int status = M.meta[5];
+  if (status != 0) {
+    for (int j = 8; j < 15; ++j) out16[j] = nan;
+    for (int j = 0; j < 12; ++j) sums[j] = 0;
+    out16[15] = (double)status;
+    return;
+  }
+  const int64_t m = M.meta[4], n = (int64_t)M.meta[1] + M.meta[3];
+  const rd_u128 sq = (rd_u128)(uint64_t)R.s1 * (uint64_t)R.s1;
+  const rd_u128 n10 = (rd_u128)(uint64_t)m * R.s2 - sq, n01 = (rd_u128)(uint64_t)n * R.t2 - sq;      // >= 0 (Cauchy-Schwarz)
+  rd_store_limbs(sums, 0, (rd_u128)(uint64_t)R.s1);  rd_store_limbs(sums, 1, R.s2);  rd_store_limbs(sums, 2, R.t2);
+  rd_store_limbs(sums, 3, n10);  rd_store_limbs(sums, 4, n01);
+  sums[10] = 0;  sums[11] = 0;
+  out16[12] = 0.0;  out16[13] = 0.0;  out16[14] = 0.0;
+  if (m < 2 || n < 2) {                                           // no unbiased variance of one placement
+    for (int j = 8; j < 12; ++j) out16[j] = nan;
+    out16[15] = 6.0;
+    return;
+  }
+  const double v10 = rd_to_double(n10) / rd_den((double)m, (double)n, (double)m);
+  const double v01 = rd_to_double(n01) / rd_den((double)m, (double)n, (double)n);
+  const double var = v10 + v01;
+  out16[8] = var;  out16[9] = v10;  out16[10] = v01;  out16[11] = sqrt(var);
+  out16[15] = 0.0;
+}
+
+__global__ void __launch_bounds__(RD_XG) k_rd_pair_final(RdModel A, RdModel B, const uint64_t *__restrict__ part_x, int xg,
+                                                         double *__restrict__ out24, int64_t *__restrict__ sums) {
+  __shared__ RdLds T;
+  const int t = threadIdx.x;
+  const RdSums Ra = rd_tile_tree(T, A);
+  const RdSums Rb = rd_tile_tree(T, B);
+  const int sa = A.meta[5], sb = B.meta[5];
+  const bool both = sa == 0 && sb == 0;                           // else k_rd_cross wrote nothing
+  __syncthreads();
+  {
+    const bool in = both && t < xg;
+    const uint64_t *q = part_x + (int64_t)t * RD_XP;
+    T.x[t] = in ? ((rd_u128)q[1] << 64) | q[0] : (rd_u128)0;
+    T.y[t] = in ? ((rd_u128)q[3] << 64) | q[2] : (rd_u128)0;
+  }
+  __syncthreads();
+  for (int d = RD_XG / 2; d > 0; d >>= 1) {
+    if (t < d) { T.x[t] += T.x[t + d];  T.y[t] += T.y[t + d]; }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const double nan = __longlong_as_double(0x7FF8000000000000ll);
+  rm_write_out8(A.meta, Ra.s1, Ra.ap, out24);
+  rm_write_out8(B.meta, Rb.s1, Rb.ap, out24 + 8);
+  if (!both) {
+    for (int j = 16; j < 23; ++j) out24[j] = nan;
+    for (int j = 0; j < 24; ++j) sums[j] = 0;
+    out24[23] = (double)(sa != 0 ? sa : sb);
+    return;
+  }
+  const rd_u128 c10 = T.x[0], c01 = T.y[0];
+  const int64_t m = A.meta[4], n = (int64_t)A.meta[1] + A.meta[3];
+  const rd_u128 um = (rd_u128)(uint64_t)m, un = (rd_u128)(uint64_t)n;
+  const rd_i128 d = (rd_i128)Ra.s1 - (rd_i128)Rb.s1;
+  const rd_u128 dd = (rd_u128)(d * d);
+  const rd_u128 nd10 = um * (Ra.s2 + Rb.s2 - 2 * c10) - dd, nd01 = un * (Ra.t2 + Rb.t2 - 2 * c01) - dd;   // >= 0 (Cauchy-Schwarz)
+  rd_store_limbs(sums, 0, (rd_u128)(uint64_t)Ra.s1);  rd_store_limbs(sums, 1, (rd_u128)(uint64_t)Rb.s1);
+  rd_store_limbs(sums, 2, Ra.s2);  rd_store_limbs(sums, 3, Rb.s2);  rd_store_limbs(sums, 4, c10);
+  rd_store_limbs(sums, 5, Ra.t2);  rd_store_limbs(sums, 6, Rb.t2);  rd_store_limbs(sums, 7, c01);
+  rd_store_limbs(sums, 8, nd10);  rd_store_limbs(sums, 9, nd01);
+  for (int j = 20; j < 24; ++j) sums[j] = 0;
+  out24[22] = 0.0;
+  if (m < 2 || n < 2) {
+    for (int j = 16; j < 22; ++j) out24[j] = nan;
+    out24[23] = 6.0;
+    return;
+  }
+  const double den10 = rd_den((double)m, (double)n, (double)m), den01 = rd_den((double)m, (double)n, (double)n);
+  const rd_u128 qa = (rd_u128)(uint64_t)Ra.s1 * (uint64_t)Ra.s1, qb = (rd_u128)(uint64_t)Rb.s1 * (uint64_t)Rb.s1;
+  const rd_i128 ab = (rd_i128)Ra.s1 * (rd_i128)Rb.s1;
+  out24[16] = rd_to_double(um * Ra.s2 - qa) / den10 + rd_to_double(un * Ra.t2 - qa) / den01;
+  out24[17] = rd_to_double(um * Rb.s2 - qb) / den10 + rd_to_double(un * Rb.t2 - qb) / den01;
+  out24[18] = rd_to_double_signed((rd_i128)(um * c10) - ab) / den10 + rd_to_double_signed((rd_i128)(un * c01) - ab) / den01;
+  const double vd = rd_to_double(nd10) / den10 + rd_to_double(nd01) / den01;
+  const double diff = (double)(Ra.s1 - Rb.s1) / (double)(2 * m * n);
+  out24[19] = vd;
+  out24[20] = diff;
+  const bool same = nd10 == 0 && nd01 == 0;                       // the two rankings induce the same placements
+  out24[21] = same ? nan : diff / sqrt(vd);
+  out24[23] = same ? 7.0 : 0.0;
+}
+
+// the launches behind rw_front of one model: its terms kernel; M names what the cross kernel and the finals read
+int rd_model(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, int32_t *workspace,
+             ggad_stream_t stream, const RdLayout &D, bool pair, RdModel &M, hipStream_t &st) {
+  RwFront F;
+  const int rc = rw_front(score, label, n, pos_cap, thres, workspace, stream, F);
+  if (rc != GGAD_OK) return rc;
+  uint64_t *part_sq = reinterpret_cast<uint64_t *>(workspace + D.o_sq());
+  int32_t *lt = workspace + D.o_lt();
+  if (pair) k_rd_terms_lt<<<dim3(F.L.tc), dim3(RW_T), 0, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, F.part_ap, F.part_num, part_sq, lt);
+  else k_rd_terms<<<dim3(F.L.tc), dim3(RW_T), 0, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, F.part_ap, F.part_num, part_sq);
+  GGAD_CHECK_LAUNCH("rank_delong terms");
+  M.meta = F.meta;  M.hist = F.hist;  M.keys = F.keys;  M.lt = lt;  M.part_ap = F.part_ap;  M.part_num = F.part_num;  M.part_sq = part_sq;
+  st = F.st;
+  return GGAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -785,6 +1119,50 @@ int ggad_rank_operating_f32(const float *score, const uint8_t *label, int64_t n,
   GGAD_CHECK_LAUNCH("rank_operating terms");
   k_ro_final<<<dim3(1), dim3(RW_TMAX), 0, F.st>>>(F.meta, F.part_ap, F.part_num, A.part, criterion, out16);
   GGAD_CHECK_LAUNCH("rank_operating final");
+  return GGAD_OK;
+}
+
+int64_t ggad_rank_delong_workspace_elems(int64_t n, int64_t pos_cap) {
+  if (!rw_args_ok(n, pos_cap)) return 0;
+  return RdLayout{rw_layout(n, pos_cap)}.total();
+}
+
+int64_t ggad_rank_delong_pair_workspace_elems(int64_t n, int64_t pos_cap) {
+  if (!rw_args_ok(n, pos_cap)) return 0;
+  return RdLayout{rw_layout(n, pos_cap)}.total_pair();
+}
+
+int ggad_rank_delong_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, double *out16,
+                         int64_t *sums, int32_t *workspace, ggad_stream_t stream) {
+  GGAD_REQUIRE(out16 && sums && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) && (n == 0 || (score && label)));
+  const RdLayout D{rw_layout(n, pos_cap)};
+  RdModel M;
+  hipStream_t st;
+  const int rc = rd_model(score, label, n, pos_cap, thres, workspace, stream, D, false, M, st);
+  if (rc != GGAD_OK) return rc;
+  k_rd_final<<<dim3(1), dim3(RW_TMAX), 0, st>>>(M, out16, sums);
+  GGAD_CHECK_LAUNCH("rank_delong final");
+  return GGAD_OK;
+}
+
+int ggad_rank_delong_pair_f32(const float *score_a, const float *score_b, const uint8_t *label, int64_t n, int64_t pos_cap, float thres,
+                              double *out24, int64_t *sums, int32_t *workspace, ggad_stream_t stream) {
+  GGAD_REQUIRE(out24 && sums && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) &&
+               (n == 0 || (score_a && score_b && label)));
+  const RdLayout D{rw_layout(n, pos_cap)};
+  RdModel A, B;
+  hipStream_t st;
+  int rc = rd_model(score_a, label, n, pos_cap, thres, workspace, stream, D, true, A, st);
+  if (rc != GGAD_OK) return rc;
+  rc = rd_model(score_b, label, n, pos_cap, thres, workspace + D.half(), stream, D, true, B, st);
+  if (rc != GGAD_OK) return rc;
+  uint64_t *part_x = reinterpret_cast<uint64_t *>(workspace + D.o_cross());
+  int64_t xg = (n + 4 * RW_T - 1) / (4 * RW_T);
+  xg = xg < 1 ? 1 : (xg > RD_XG ? RD_XG : xg);
+  k_rd_cross<<<dim3((unsigned)xg), dim3(RW_T), 0, st>>>(score_a, score_b, label, n, (int)D.L.pc, A, B, part_x);
+  GGAD_CHECK_LAUNCH("rank_delong cross");
+  k_rd_pair_final<<<dim3(1), dim3(RD_XG), 0, st>>>(A, B, part_x, (int)xg, out24, sums);
+  GGAD_CHECK_LAUNCH("rank_delong pair final");
   return GGAD_OK;
 }
 

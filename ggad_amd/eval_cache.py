@@ -123,6 +123,31 @@ class ResidentSweep:
         return operating_point(self.scores() if scores is None else scores, self.labels, criterion, param, thres,
                                pos_cap=max(1, self.n_pos))
 
+    def _own_pos_cap(self, who: str) -> int:
+        """The sweep's own count of positives as the `pos_cap` of a run-merge call (counted once), as `operating_point` takes it."""
+        if self.labels is None:
+            raise ValueError(f"ResidentSweep.{who}: this sweep was built without labels")
+        if self.n_pos is None:
+            self.n_pos = int((self.labels == 1).sum())
+        cap = int(self.engine.lib.ggad_rank_wide_max_pos())
+        if self.n_pos > cap:
+            raise ValueError(f"ResidentSweep.{who}: the list holds {self.n_pos} positives, more than ggad_rank_wide_max_pos() = {cap}")
+        return max(1, self.n_pos)
+
+    def auc_ci(self, level: float = 0.95, scores: torch.Tensor = None):
+        """`metrics.auc_ci` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) on the
+        resident labels: the AUROC with DeLong's standard error and the normal interval at `level`."""
+        from .metrics import auc_ci
+        cap = self._own_pos_cap("auc_ci")
+        return auc_ci(self.scores() if scores is None else scores, self.labels, level, pos_cap=cap)
+
+    def compare(self, scores_b: torch.Tensor, scores: torch.Tensor = None):
+        """`metrics.compare_auc` of the current weights' scores (or of `scores`) against `scores_b`, another model's scores of the
+        same list, on the resident labels: DeLong's paired test of the two AUROCs."""
+        from .metrics import compare_auc
+        cap = self._own_pos_cap("compare")
+        return compare_auc(self.scores() if scores is None else scores, scores_b, self.labels, pos_cap=cap)
+
     def top_k(self, k: int, scores: torch.Tensor = None, wide: bool = False):
         """`metrics.top_k` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) with the
         sweep's ids and resident labels: the `Ranked` head of the list, `ids` = node ids.  Nothing is uploaded and no plan is built.

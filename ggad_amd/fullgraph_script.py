@@ -176,6 +176,61 @@ def print_threshold_test(test_scores, y_dev, thres, alerts=False):
     return c
 
 
+def add_compare_options(p):
+    """`--auc_ci [LEVEL]` / `--compare CKPT_B` (run.py only): the test AUROC with DeLong's standard error and interval
+    (`metrics.auc_ci`), and DeLong's paired test of two checkpoints' AUROCs on idx_test (`metrics.compare_auc`).  Off by default and,
+    like the options of `add_select_options`, absent from the namespace when not given.  Read them with `compare_options`;
+    `check_compare_options` after parsing."""
+    p.add_argument("--auc_ci", type=float, nargs="?", const=0.95, default=argparse.SUPPRESS, metavar="LEVEL",
+                   help="after training, or with --score: the AUROC on idx_test with DeLong's standard error and the normal interval at "
+                        "LEVEL (default 0.95), from exact counts on the device")
+    p.add_argument("--compare", type=str, default=argparse.SUPPRESS, metavar="CKPT_B",
+                   help="with --score CKPT: score idx_test under CKPT_B too and test the two AUROCs against each other (DeLong's paired "
+                        "z and two-sided p)")
+    return p
+
+
+def compare_options(a):
+    """(auc_ci level or None, compare path or None) of a namespace."""
+    return getattr(a, "auc_ci", None) or None, getattr(a, "compare", None) or None
+
+
+def check_compare_options(p, a):
+    level, other = compare_options(a)
+    if hasattr(a, "auc_ci") and not 0.0 < float(a.auc_ci) < 1.0:
+        p.error("--auc_ci LEVEL: a confidence level inside (0, 1), as in --auc_ci 0.9")
+    if other and not select_options(a)[2]:
+        p.error("--compare CKPT_B compares with the checkpoint of --score CKPT: it needs --score")
+    return a
+
+
+def _test_lists(scores, idx_test, ano_label, dev):
+    """(float32 scores, uint8 labels, count of positives) of idx_test on the device, as the DeLong calls take them."""
+    idx = np.asarray(idx_test, dtype=np.int64)
+    y8 = np.asarray(ano_label).reshape(-1)[idx].astype(np.uint8)
+    return (scores.detach().float().index_select(0, torch.as_tensor(idx, device=dev)).contiguous(), torch.from_numpy(y8).to(dev),
+            max(1, int(np.count_nonzero(y8 == 1))))
+
+
+def print_auc_ci(level, scores, idx_test, ano_label, dev):
+    """`--auc_ci LEVEL`: one `[auc_ci]` line for the (N,) device `scores` on idx_test; returns the `metrics.AucInterval`."""
+    from .metrics import auc_ci, format_auc_ci
+    s, y, cap = _test_lists(scores, idx_test, ano_label, dev)
+    ci = auc_ci(s, y, level, pos_cap=cap)
+    print(format_auc_ci(ci))
+    return ci
+
+
+def print_compare(scores_a, scores_b, idx_test, ano_label, dev):
+    """`--compare`: one `[compare]` line for two (N,) device score tensors on idx_test; returns the `metrics.AucComparison`."""
+    from .metrics import compare_auc, format_compare
+    a, y, cap = _test_lists(scores_a, idx_test, ano_label, dev)
+    b = _test_lists(scores_b, idx_test, ano_label, dev)[0]
+    c = compare_auc(a, b, y, pos_cap=cap)
+    print(format_compare(c))
+    return c
+
+
 # ------------------------------------------------------------------------------------------------ checkpoints
 def save_checkpoint(path, state_dict, args, n_in, nodes, epoch, value=None, threshold=None):
     """`torch.save({"state_dict", "meta"})`: the model's own state_dict (host copies; for `run.py` the reference's key names, so the

@@ -22,7 +22,11 @@ order), with the running count of positives beside it, from `ggad_topk_f32` (csr
 `operating_point` turns a score into an alert rule: the threshold, among the distinct scores of the positives, that is best under
 F1, macro-F1, G-mean, or recall at a bound on precision or on the false-positive rate, with its exact confusion counts, from
 `ggad_rank_operating_f32` (the run-merge chain of csrc/rank_metrics.hip with an arg-max behind it): one call, one read-back.
-`pr_curve` is the curve behind it; `parse_criterion` reads the criterion's spelling in the configs and on the command lines."""
+`pr_curve` is the curve behind it; `parse_criterion` reads the criterion's spelling in the configs and on the command lines.
+
+`auc_ci` says how far an AUROC can be trusted -- DeLong's variance, standard error and normal interval -- and `compare_auc` whether two
+models' AUROCs on the same labels differ (DeLong's paired z and p), from `ggad_rank_delong_f32` / `ggad_rank_delong_pair_f32`: the
+same chain with the variance's numerators as exact 128-bit integers, one call and one read-back each."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -273,6 +277,122 @@ def pr_curve(scores: torch.Tensor, labels_u8: torch.Tensor, pos_cap: Optional[in
     head = torch.ones(p, dtype=torch.bool, device=tp.device)
     head[1:] = first[1:] != first[:-1]
     return cur[0][:p][head], tp, cur[2][:p][head]
+
+
+@dataclass
+class AucInterval:
+    """AUROC with DeLong's standard error (`auc_ci`).  `var`: the variance of the AUROC, `se` its root; `lo`, `hi`: `auc -+ q se`
+    clipped to [0, 1], q the two-sided normal quantile of `level`; `report`: the `binary_report` dict at the call's `thres`."""
+    auc: float
+    var: float
+    se: float
+    lo: float
+    hi: float
+    level: float
+    n_pos: int
+    n_neg: int
+    status_ok: bool
+    report: Dict[str, float]
+
+
+@dataclass
+class AucComparison:
+    """Two AUROCs on the same labels (`compare_auc`): `diff = auc_a - auc_b`, the two variances, their covariance, the variance of
+    the difference, `z = diff / sqrt(var_diff)` and the two-sided p-value of z under a standard normal.  `identical`: the two score
+    lists induce the same placements (`var_diff` is exactly 0): `z = 0.0`, `p = 1.0`."""
+    auc_a: float
+    auc_b: float
+    diff: float
+    var_a: float
+    var_b: float
+    cov: float
+    var_diff: float
+    z: float
+    p: float
+    n_pos: int
+    n_neg: int
+    identical: bool
+
+
+_TOO_FEW = "needs at least two positives and two negatives"
+
+
+def format_auc_ci(ci: AucInterval) -> str:
+    """The one `[auc_ci]` line of `main.py --auc_ci` and `run.py --auc_ci`."""
+    return (f"[auc_ci] AUROC {ci.auc!r} ± {ci.se!r} ({ci.level:.0%}: [{ci.lo!r}, {ci.hi!r}]) on {ci.n_pos} positives, "
+            f"{ci.n_neg} negatives")
+
+
+def format_compare(c: AucComparison) -> str:
+    """The one `[compare]` line of `--score CKPT --compare CKPT_B`."""
+    return f"[compare] AUROC A {c.auc_a!r} B {c.auc_b!r} diff {c.diff!r} z {c.z!r} p {c.p!r}"
+
+
+def _delong_call(who: str, lists, labels_u8, thres: float, pos_cap):
+    """`operating_point`'s checks for every score list of `lists` (one: `ggad_rank_delong_f32`, two: `ggad_rank_delong_pair_f32`),
+    the workspace, ONE native call and ONE read-back: (the 16 or 24 doubles as a list, pos_cap)."""
+    from . import _lib
+    for scores in lists:
+        if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+            raise ValueError(f"{who} takes float32 scores and uint8 labels of the same 1-D shape")
+        if scores.device.type != "cuda" or labels_u8.device != scores.device:
+            raise ValueError(f"{who} takes scores and labels on the same GPU (there is no CPU path)")
+    lib = _lib.load()
+    n = labels_u8.numel()
+    cap = int(lib.ggad_rank_wide_max_pos())
+    if pos_cap is None:
+        pos_cap = max(1, min(n, cap))
+    if int(pos_cap) != pos_cap or not 1 <= int(pos_cap) <= cap:
+        raise ValueError(f"{who}: pos_cap = {pos_cap} is outside 1..ggad_rank_wide_max_pos() = {cap}")
+    pos_cap = int(pos_cap)
+    lists, labels_u8 = [s.contiguous() for s in lists], labels_u8.contiguous()
+    dev = labels_u8.device
+    entry = "ggad_rank_delong_pair" if len(lists) == 2 else "ggad_rank_delong"
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(1, int(getattr(lib, entry + "_workspace_elems")(n, pos_cap))), dtype=torch.int32, device=dev)
+        out = torch.empty(8 + 8 * len(lists), dtype=torch.float64, device=dev)
+        sums = torch.empty(12 * len(lists), dtype=torch.int64, device=dev)
+        _lib.call(entry + "_f32", *(_lib.ptr(s) for s in lists), _lib.ptr(labels_u8), n, pos_cap, float(thres), _lib.ptr(out),
+                  _lib.ptr(sums), _lib.ptr(ws))
+        return out.cpu().tolist(), pos_cap
+
+
+def auc_ci(scores: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, thres: float = 0.5,
+           pos_cap: Optional[int] = None) -> AucInterval:
+    """AUROC with DeLong's variance and the normal interval at `level`: one `ggad_rank_delong_f32` call (csrc/rank_metrics.hip: the
+    run-merge chain, the variance's numerators exact 128-bit integers) and one read-back of sixteen doubles.  `thres` and `pos_cap` are
+    `rank_report_wide`'s.  `ValueError` for a `level` outside (0, 1), a NaN score, a label other than 0/1, one class only, more
+    positives than `pos_cap`, or fewer than two positives or two negatives."""
+    from statistics import NormalDist
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"auc_ci: level = {level!r} is outside (0, 1)")
+    o, pos_cap = _delong_call("auc_ci", [scores], labels_u8, thres, pos_cap)
+    _raise_on_status("auc_ci", int(o[7]), int(o[6]), pos_cap)
+    tp, fp, fn, tn = (int(v) for v in o[2:6])
+    if int(o[15]) == 6:
+        raise ValueError(f"auc_ci: {tp + fn} positives and {fp + tn} negatives: DeLong's variance {_TOO_FEW}")
+    auc, var, se = float(o[0]), float(o[8]), float(o[11])
+    q = NormalDist().inv_cdf(0.5 + float(level) / 2)
+    return AucInterval(auc=auc, var=var, se=se, lo=max(0.0, auc - q * se), hi=min(1.0, auc + q * se), level=float(level),
+                       n_pos=tp + fn, n_neg=fp + tn, status_ok=int(o[15]) == 0,
+                       report={"auc": auc, "ap": float(o[1]), **_confusion_scores(tp, fp, fn, tn)})
+
+
+def compare_auc(scores_a: torch.Tensor, scores_b: torch.Tensor, labels_u8: torch.Tensor, pos_cap: Optional[int] = None) -> AucComparison:
+    """DeLong's paired test of two score lists on the same labels: one `ggad_rank_delong_pair_f32` call and one read-back of
+    twenty-four doubles.  The variance of the difference comes from exact integer numerators of its own, not from
+    `var_a + var_b - 2 cov`.  The `ValueError`s of `auc_ci`, for either list."""
+    import math
+    o, pos_cap = _delong_call("compare_auc", [scores_a, scores_b], labels_u8, 0.5, pos_cap)
+    _raise_on_status("compare_auc", int(o[23]) if int(o[23]) in (1, 2, 3, 4) else 0, int(o[6]), pos_cap)
+    n_pos, n_neg = int(o[2]) + int(o[4]), int(o[3]) + int(o[5])
+    if int(o[23]) == 6:
+        raise ValueError(f"compare_auc: {n_pos} positives and {n_neg} negatives: DeLong's variance {_TOO_FEW}")
+    same = int(o[23]) == 7
+    z = 0.0 if same else float(o[21])
+    return AucComparison(auc_a=float(o[0]), auc_b=float(o[8]), diff=float(o[20]), var_a=float(o[16]), var_b=float(o[17]),
+                         cov=float(o[18]), var_diff=float(o[19]), z=z, p=1.0 if same else math.erfc(abs(z) / 2 ** 0.5),
+                         n_pos=n_pos, n_neg=n_neg, identical=same)
 
 
 @dataclass

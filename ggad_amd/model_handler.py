@@ -27,6 +27,10 @@ list is scored once more, the alert threshold that is best under CRIT is chosen 
 one `[threshold]` line, kept in `self.operating_point`, used by the closing test sweep instead of ``thres`` and written by rank 0 to
 `<checkpoint>.thres.json`; `score(checkpoint)` with the key on reads that file.  The validation list is the reference's -- the test
 split (`src/model_handler.py:260-261`) --, so the threshold, like the checkpoint, is chosen on the list it is then reported on.
+``auc_ci: LEVEL`` (`model: 'GCN'`; 0 = off): after the closing test sweep, and in `score(checkpoint)`, the test AUROC is printed with
+DeLong's standard error and the normal interval at LEVEL as one `[auc_ci]` line (`metrics.auc_ci`, csrc/rank_metrics.hip: exact
+integer numerators), kept in `self.auc_interval`; `score(checkpoint, compare=other)` scores the same list under a second checkpoint and
+prints DeLong's paired test of the two AUROCs as one `[compare]` line (`metrics.compare_auc`), kept in `self.auc_comparison`.
 ``explain: M`` / ``explain_out`` (with ``top_k`` > 0): every node of the ranked list is explained on the device (`explain.explain`,
 csrc/explain.hip): its logit split exactly per feature and per neighbour, the M signed-greatest neighbour contributions listed; kept in
 `self.explained`, reported in one `[explain]` line and written to an `.npz`; after `train()` and by `score(checkpoint)` alike.
@@ -128,6 +132,13 @@ class ModelHandler(object):
                                  "validation sweep")
             from .metrics import parse_criterion
             self.thres_select = parse_criterion(args.thres_select)
+        self.auc_interval = self.auc_comparison = None
+        self.auc_level = float(getattr(args, "auc_ci", 0) or 0)  # config key `auc_ci`: the level of the interval, 0 = off
+        if self.auc_level:
+            if getattr(args, "model", None) != "GCN":
+                raise ValueError("config key `auc_ci` needs `model: 'GCN'`: the interval is made from the scores of the GGAD test sweep")
+            if not 0.0 < self.auc_level < 1.0:
+                raise ValueError(f"config key `auc_ci`: {args.auc_ci!r} is not a confidence level inside (0, 1) (0 = off)")
         self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
 
     @staticmethod
@@ -175,6 +186,36 @@ class ModelHandler(object):
         with open(path) as fh:
             doc = json.load(fh)
         return float(struct.unpack("<f", struct.pack("<I", int(doc["thres_bits"])))[0]), doc
+
+    def _auc_ci(self, scores, labels, sweep, verbose=True):
+        """Config key `auc_ci`: the interval of `scores` (the device scores of a sweep, already made) on `labels`, one `[auc_ci]` line;
+        kept in `self.auc_interval`."""
+        from .metrics import auc_ci, format_auc_ci
+        if sweep is not None:
+            ci = sweep.auc_ci(self.auc_level, scores=scores)
+        else:
+            lab = np.asarray(labels).reshape(-1).astype(np.uint8)
+            ci = auc_ci(scores, torch.from_numpy(lab).to(scores.device), self.auc_level, pos_cap=max(1, int(np.count_nonzero(lab == 1))))
+        self.auc_interval = ci
+        if verbose:
+            print(format_auc_ci(ci))
+        return ci
+
+    def _compare(self, scores, other, gnn_model, engine, ids, labels, sweep):
+        """`score(compare=other)`: the same list scored under the weights of `other` -- by the same sweep, whose cached rows do not
+        depend on the weights -- and DeLong's paired test of the two AUROCs, one `[compare]` line; kept in `self.auc_comparison`."""
+        from .metrics import compare_auc, format_compare
+        gnn_model.load_state_dict(torch.load(other))
+        engine.sync_params()
+        if sweep is not None:
+            c = sweep.compare(sweep.scores(), scores=scores)
+        else:
+            lab = np.asarray(labels).reshape(-1).astype(np.uint8)
+            scores_b = score_nodes(gnn_model, ids, self.args.batch_size, device=True)
+            c = compare_auc(scores, scores_b, torch.from_numpy(lab).to(scores.device), pos_cap=max(1, int(np.count_nonzero(lab == 1))))
+        self.auc_comparison = c
+        print(format_compare(c))
+        return c
 
     def _build_gcn(self):
         """The GGAD model as `src/model_handler.py:263-296` builds it, shared by `train` and `score`: device, graph (through the
@@ -243,13 +284,14 @@ class ModelHandler(object):
                     write_explained(out, ranked, ex)
         return ranked
 
-    def score(self, checkpoint, ids=None, labels=None, k=None):
+    def score(self, checkpoint, ids=None, labels=None, k=None, compare=None):
         """Scores from a saved checkpoint, without training: the model is built as `train` builds it, the state dict of `checkpoint`
         (a `.pkl` of `BestCheckpoint`) is loaded and the engine synchronised exactly as the restore at the end of `train` does, and
         `ids` are swept in `test_sage`'s slices of `batch_size` (whose per-slice normalisation matters).  Default: the test split with
         its labels, which follows from the config alone (`split_dgraphfin` reseeds itself from `seed`).  With labels `test_sage`'s report
         is printed and its 5-tuple kept in `self.metrics`; with `k` (default: config key `top_k`) > 0 the scores are ranked (`_rank`).
-        Honours `eval_cache`.  Returns (device float32 scores, `Ranked` or None)."""
+        Honours `eval_cache`.  With labels, config key `auc_ci` prints the `[auc_ci]` line and `compare` (a second checkpoint) the
+        `[compare]` line; the model then holds the second checkpoint's weights.  Returns (device float32 scores, `Ranked` or None)."""
         args = self.args
         if args.model != "GCN":
             raise NotImplementedError("ModelHandler.score serves model 'GCN' (GGAD)")
@@ -259,6 +301,8 @@ class ModelHandler(object):
         if k:
             from .metrics import check_k
             check_k(k, "ModelHandler.score", wide=bool(getattr(args, "top_k_wide", False)))
+        if compare is not None and ids is not None and labels is None:
+            raise ValueError("ModelHandler.score: `compare` tests two AUROCs against each other: it needs labels")
         thres = args.thres
         if self.thres_select is not None:                        # config key `thres_select`: report at the threshold chosen in training
             thres, self.thres_doc = self._read_threshold(checkpoint)
@@ -283,6 +327,10 @@ class ModelHandler(object):
             scores = sweep.scores() if sweep is not None else score_nodes(gnn_model, ids, args.batch_size, device=True)
         self.test_scores = scores
         self.ranked = self._rank(scores, ids, labels, sweep, k, model=gnn_model) if k else None
+        if self.auc_level and labels is not None:
+            self._auc_ci(scores, labels, sweep)
+        if compare is not None:
+            self._compare(scores, compare, gnn_model, engine, ids, labels, sweep)
         return scores, self.ranked
 
     def train(self):
@@ -406,7 +454,7 @@ class ModelHandler(object):
                 dist.broadcast(engine.params, src=0)          # every rank tests the restored weights
             engine.sync_params()
         top_k = int(getattr(args, "top_k", 0) or 0)
-        keep = [] if top_k else None                 # config key `top_k`: the sweep's device scores are kept and ranked, not made twice
+        keep = [] if top_k or self.auc_level else None    # config keys `top_k`, `auc_ci`: the sweep's device scores are kept, not made twice
         thres = args.thres
         if self.thres_select is not None:            # config key `thres_select`: the closing sweep reports at the chosen threshold
             op = self._choose_threshold(gnn_model, idx_valid, y_valid, sweep_valid, dist, verbose=rank == 0)
@@ -419,6 +467,8 @@ class ModelHandler(object):
         if top_k:
             self.test_scores = keep[0]
             self._rank(keep[0], idx_test, y_test, sweep_test, top_k, verbose=rank == 0, model=gnn_model)
+        if self.auc_level:
+            self._auc_ci(keep[0], y_test, sweep_test, verbose=rank == 0)
         return res
 
 

@@ -1273,6 +1273,42 @@ int ggad_rank_operating_f32(const float *score, const uint8_t *label, int64_t n,
                             int32_t *workspace, ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * DeLong's variance of the AUROC, and the paired comparison of two score lists on the same labels (rank_metrics.hip).  The front is
+ * ggad_rank_wide_f32's.  With m = P positives, n = Nn negatives, +-0.0 one score, and the doubled placements
+ *   a_i = 2 #{neg < x_i} + #{neg == x_i} per positive      b_j = 2 #{pos > y_j} + #{pos == y_j} per negative
+ * the sums S1 = sum a = sum b (the AUROC numerator), S2 = sum a^2, T2 = sum b^2, N10 = m S2 - S1^2, N01 = n T2 - S1^2 are exact
+ * integers (128-bit accumulators: m S2 passes 64 bits at 1.7 M scores) and
+ *   var = N10 / (4 n^2 m^2 (m - 1)) + N01 / (4 m^2 n^2 (n - 1)),
+ * each numerator converted to float64 once.  For two lists A and B, by element, C10 = sum_i a_i^A a_i^B, C01 = sum_j b_j^A b_j^B,
+ *   cov      = (m C10 - S1A S1B) / (4 n^2 m^2 (m - 1)) + (n C01 - S1A S1B) / (4 m^2 n^2 (n - 1))
+ *   ND10     = m (S2A + S2B - 2 C10) - (S1A - S1B)^2,  ND01 = n (T2A + T2B - 2 C01) - (S1A - S1B)^2
+ *   var_diff = ND10 / (4 n^2 m^2 (m - 1)) + ND01 / (4 m^2 n^2 (n - 1))      (never var_a + var_b - 2 cov in floating point)
+ *
+ * ggad_rank_delong_f32.  out16: [0..7] the eight doubles of ggad_rank_wide_f32 for the same arguments, bit for bit; [8] var; [9],
+ * [10] its positive-side and negative-side terms; [11] sqrt(var); [12..14] 0.0; [15] status.  sums (12 int64): lo, hi limbs of S1,
+ * S2, T2, N10, N01, then two zeros.  Status: [7] when [7] != 0 ([8..14] NaN, sums all zero); 6 = fewer than two positives or two
+ * negatives, both classes present (the AUROC words and sums valid, [8..11] NaN); else 0 (a variance of exactly 0 included).
+ *
+ * ggad_rank_delong_pair_f32.  out24: [0..7] A's out8, [8..15] B's; [16] var_a, [17] var_b, [18] cov, [19] var_diff, [20] auroc_a -
+ * auroc_b as (S1A - S1B) / (2 m n), [21] z = [20] / sqrt([19]), [22] 0.0, [23] status.  sums (24 int64): limbs of S1A, S1B, S2A, S2B,
+ * C10, T2A, T2B, C01, ND10, ND01, then zeros.  Status: the first non-zero of [7], [15] ([16..22] NaN, sums all zero); else 6 as
+ * above ([16..21] NaN); else 7 when ND10 == ND01 == 0 (the two lists induce the same placements: z NaN, the rest valid); else 0.
+ *
+ * Limits, alignment and workspace rule of ggad_rank_wide_f32, with ggad_rank_delong_workspace_elems / _pair_workspace_elems(n,
+ * pos_cap) int32 elements (0 = refused); outside them, or with a NULL pointer: GGAD_E_INVALID and no launch.  The single call has
+ * ggad_rank_wide_f32's number of launches; the pair runs the front and the terms kernel twice, one cross kernel over the n elements
+ * and one final.  No host synchronisation, no floating-point atomics, nothing that waits on another workgroup; every
+ * word a launch reads was written by an earlier launch of the same call: capturable and replayable.  Integer sums: equal inputs give
+ * equal bits on any grid.
+ * ---------------------------------------------------------------------------------- */
+int64_t ggad_rank_delong_workspace_elems(int64_t n, int64_t pos_cap);        /* int32 elements; 0 = refused */
+int64_t ggad_rank_delong_pair_workspace_elems(int64_t n, int64_t pos_cap);   /* int32 elements; 0 = refused */
+int ggad_rank_delong_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, double *out16,
+                         int64_t *sums, int32_t *workspace, ggad_stream_t stream);
+int ggad_rank_delong_pair_f32(const float *score_a, const float *score_b, const uint8_t *label, int64_t n, int64_t pos_cap,
+                              float thres, double *out24, int64_t *sums, int32_t *workspace, ggad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Keep the best epoch's weights on the device (select.hip): the hand-off "if this epoch's validation metric is the best so far,
  * snapshot the parameters" without a host round trip.  Neither call takes a workspace; each reads only words the host or an earlier
  * launch wrote, so both are capturable and replayable behind ggad_rank_metrics_f32 / ggad_rank_wide_f32 in a captured epoch.

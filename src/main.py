@@ -63,6 +63,7 @@ def use_handler(name):
 
 SCORE = None          # --score CKPT: score from this checkpoint instead of training
 SCORE_IDS = None      # --score_ids FILE.npy: the int64 ids --score sweeps and ranks (no labels) instead of the test split
+COMPARE = None        # --compare CKPT_B: with --score, DeLong's paired test of the two checkpoints' test AUROCs
 
 
 def run_once(config):
@@ -71,6 +72,8 @@ def run_once(config):
         handler = HANDLER(config)
         if SCORE_IDS is not None:
             handler.score(SCORE, ids=np.asarray(np.load(SCORE_IDS), dtype=np.int64).reshape(-1))
+        elif COMPARE is not None:
+            handler.score(SCORE, compare=COMPARE)
         else:
             handler.score(SCORE)
         return handler.metrics
@@ -146,7 +149,20 @@ if __name__ == "__main__":
     ap.add_argument("--score_ids", type=str, default=None, metavar="FILE.npy",
                     help="with --score: sweep and rank this int64 id list (np.save) instead of the test split; no labels, so no report: "
                          "with top_k it is the ranked list of these ids (every node of the graph, for instance)")
+    ap.add_argument("--auc_ci", type=float, nargs="?", const=0.95, default=None, metavar="LEVEL",
+                    help="override the config's auc_ci (--handler ggad: after the closing test sweep, and with --score, print the test "
+                         "AUROC with DeLong's standard error and the normal interval at LEVEL, default 0.95; 0 = off)")
+    ap.add_argument("--compare", type=str, default=None, metavar="CKPT_B",
+                    help="with --score CKPT: score the test split under CKPT_B too and print DeLong's paired test of the two AUROCs")
     a = ap.parse_args()
+    if a.compare is not None and a.score is None:
+        ap.error("--compare CKPT_B compares with the checkpoint of --score CKPT: it needs --score")
+    if a.compare is not None and a.score_ids is not None:
+        ap.error("--compare tests two AUROCs against each other: the ids of --score_ids carry no labels")
+    if a.auc_ci and a.handler != "ggad":
+        ap.error("--auc_ci serves --handler ggad only")
+    if a.auc_ci is not None and not 0.0 <= a.auc_ci < 1.0:
+        ap.error("--auc_ci LEVEL: a confidence level inside (0, 1), as in --auc_ci 0.9 (0 = off)")
     if a.score_ids is not None and a.score is None:
         ap.error("--score_ids names the ids --score CKPT sweeps: it needs --score")
     if a.score is not None and a.handler != "ggad":
@@ -171,7 +187,9 @@ if __name__ == "__main__":
         cfg["top_k_wide"] = a.top_k_wide
     if a.thres_select is not None:
         cfg["thres_select"] = a.thres_select
-    SCORE, SCORE_IDS = a.score, a.score_ids
+    if a.auc_ci is not None:
+        cfg["auc_ci"] = a.auc_ci
+    SCORE, SCORE_IDS, COMPARE = a.score, a.score_ids, a.compare
     use_handler(a.handler)
     init_distributed()
     torch.set_num_threads(min(8, os.cpu_count() or 1))        # host tensors are tiny here; 128 intra-op threads only add jitter
