@@ -49,6 +49,10 @@
 //   k_rd_cross   pair only: every element looks its key up in both models' sorted keys and adds a^A a^B or b^A b^B in 128 bits
 //   k_rd_final / k_rd_pair_final   k_rw_final's tree with the 128-bit sums beside it; the variance numerators, each converted ONCE
 // (the formulas: above k_rd_terms, further down)
+//
+// ggad_rank_bootstrap_f32: ggad_rank_wide_f32's launches as they are (out16[0..7] = its out8) and ONE more,
+//   k_rb_boot    one workgroup per replicate of a stratified bootstrap: Philox draws binned by a search in the prefix of histU, three
+//                integer histograms in LDS, AP* and the AUROC numerator of the replicate (the scheme: above rb_philox, further down)
 // Why runs of 2,048 and a merge by rank: head of rank_common.h.  Why the narrow chain stays although the wide one is twice as fast at
 // DGraph-Fin's size: inside a captured training epoch (run.py --select) a validation list of 3,935 nodes costs the wide chain six
 // launches against four, and the epoch is 21 us longer (profiles/rank_one_chain_time_line.json).
@@ -1044,6 +1048,164 @@ int rd_model(const float *score, const uint8_t *label, int64_t n, int64_t pos_ca
   return GGAD_OK;
 }
 
+// ---- Stratified bootstrap of AP and AUROC from the chain's bins (ggad_rank_bootstrap_f32).  A replicate redraws P positives among
+// the P sorted ranks (w[k] = how often rank k was drawn) and Nn negatives among the Nn negatives; a negative is known by its bin only:
+// bin b of histU (the negatives with exactly b positives at or below them), and inside the bin whether it is one of the histE[b - 1]
+// that tie the positive run ending at b - 1 (the first histE[b - 1] places of the bin, by convention).  So a replicate is three
+// integer histograms, w[P], cU[P + 1], cE[P + 1], and never touches the n elements:
+//     L*_k  = prefix of cU through k       TP*_k = sum of w from the start s of k's run of equal keys
+//     AP*   = (1 / P) sum_k w_k TP*_k / (TP*_k + Nn - L*_k)        num* = sum_k w_k (2 L*_k + cE[e]), e the run's end (exact int64)
+// Draws are Philox4x32-10 (Random123; the constants of rocrand_philox4x32_10.h), key (seed lo, seed hi), counter (j lo, j hi,
+// replicate, stream): call j gives draws 2j and 2j + 1 as x = c0 | c1 << 32 and c2 | c3 << 32, a draw over m outcomes is
+// mulhi64(x, m).  Stream 0 the positives, 1 the negatives.  Which thread makes which draw does not matter: LDS integer atomics only.
+constexpr int RB_MAXP = 9216;             // four int32 arrays of P + 1 entries (147,472 bytes) beside the tree and scan scratch
+constexpr int RB_MAXREPS = 4096;
+constexpr int RB_TOO_FEW = 8, RB_TOO_MANY = 9;      // statuses behind the chain's 1 .. 4 (5: operating point, 6 and 7: DeLong)
+constexpr int RB_LDS_MAX = 4 * (RB_MAXP + 1) * 4;
+
+static_assert(RB_LDS_MAX + RW_T * 8 + (int)sizeof(RkScan) <= 160 * 1024, "k_rb_boot's arrays, its tree and its scan share one CU's LDS");
+
+__device__ __forceinline__ void rb_philox(uint32_t k0, uint32_t k1, uint64_t j, uint32_t rep, uint32_t stream, uint64_t &x0, uint64_t &x1) {
+  uint32_t c0 = (uint32_t)j, c1 = (uint32_t)(j >> 32), c2 = rep, c3 = stream;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+    c0 = n0;  c1 = l1;  c2 = n2;  c3 = l0;
+    k0 += 0x9E3779B9u;  k1 += 0xBB67AE85u;
+  }
+  x0 = (uint64_t)c0 | ((uint64_t)c1 << 32);
+  x1 = (uint64_t)c2 | ((uint64_t)c3 << 32);
+}
+
+// a[0, len) in LDS replaced by its inclusive (EXCL: exclusive) prefix sums: `chunk` consecutive entries per thread, a scan of the
+// threads' totals between two passes.  Whole workgroup; the caller's stores to a[] need a barrier before it, the sums none after it.
+template <bool EXCL>
+__device__ __forceinline__ void rb_prefix(RkScan &S, int32_t *a, int len, int chunk) {
+  const int lo = threadIdx.x * chunk, hi = lo + chunk < len ? lo + chunk : len;
+  int32_t tot = 0;
+  for (int i = lo; i < hi; ++i) tot += a[i];
+  int32_t run = rk_block_scan(S, tot, nullptr) - tot;
+  for (int i = lo; i < hi; ++i) {
+    const int32_t v = a[i];
+    a[i] = EXCL ? run : run + v;
+    run += v;
+  }
+  __syncthreads();
+}
+
+// One workgroup = one replicate.  LDS: four arrays of ls >= P + 1 ints.  While the negatives are drawn they hold cum (the inclusive
+// prefix of histU), histE, cU and cE; then cum's place takes w, and histE's the exclusive prefix of w.
+__global__ void __launch_bounds__(RW_T) k_rb_boot(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
+                                                  const int32_t *__restrict__ hist, uint32_t seed_lo, uint32_t seed_hi, int reps, int ls,
+                                                  double *__restrict__ out16, double *__restrict__ rep_ap,
+                                                  int64_t *__restrict__ rep_num, int32_t *__restrict__ hist_out, int64_t hstride) {
+  extern __shared__ __attribute__((aligned(16))) int32_t rb_lds[];
+  __shared__ RkScan S;
+  __shared__ union { double d[RW_T]; int64_t i[RW_T]; } red;
+  const int t = threadIdx.x;
+  const uint32_t r = blockIdx.x;
+  const int status = meta[5];
+  const int P = meta[4];
+  const int64_t Nn = (int64_t)meta[1] + meta[3];
+  const int code = status != 0 ? status : (P > RB_MAXP ? RB_TOO_MANY : ((P < 2 || Nn < 2) ? RB_TOO_FEW : 0));
+  if (r == 0 && t == 0) {
+    out16[8] = (double)reps;  out16[9] = (double)P;  out16[10] = (double)Nn;
+    out16[11] = 0.0;  out16[12] = 0.0;  out16[13] = 0.0;  out16[14] = 0.0;
+    out16[15] = (double)code;
+  }
+  int32_t *ho = hist_out ? hist_out + (int64_t)r * hstride : nullptr;
+  if (code != 0) {                                                // (uniform over the launch)
+    if (t == 0) { rep_ap[r] = __longlong_as_double(0x7FF8000000000000ll);  rep_num[r] = 0; }
+    if (ho) for (int64_t i = t; i < hstride; i += RW_T) ho[i] = 0;
+    return;
+  }
+  int32_t *a0 = rb_lds, *a1 = a0 + ls, *cu = a1 + ls, *ce = cu + ls;       // P + 1 <= ls
+  const int32_t *hu = hist, *he = hist + (pc + 1);
+  const int chunk = (P + 1 + RW_T - 1) / RW_T;
+  for (int i = t; i <= P; i += RW_T) { a0[i] = hu[i];  a1[i] = he[i];  cu[i] = 0;  ce[i] = 0; }
+  __syncthreads();
+  rb_prefix<false>(S, a0, P + 1, chunk);                          // cum[b]: negatives of bins 0 .. b; cum[P] = Nn
+  {
+    const uint64_t m = (uint64_t)Nn, calls = (m + 1) >> 1;
+    for (uint64_t j = t; j < calls; j += RW_T) {
+      uint64_t x[2];
+      rb_philox(seed_lo, seed_hi, j, r, 1u, x[0], x[1]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (2 * j + h >= m) continue;                             // (an odd count: the last call is half used)
+        const int32_t u = (int32_t)__umul64hi(x[h], m);           // < Nn <= INT32_MAX
+        int b = rk_upper(a0, 0, P + 1, u);                        // entries of cum that are <= u
+        b = b < P ? b : P;                                        // (cum[P] = Nn > u: never taken)
+        atomicAdd(&cu[b], 1);
+        if (b >= 1 && u - a0[b - 1] < a1[b - 1]) atomicAdd(&ce[b - 1], 1);     // one of the bin's first histE[b - 1] places
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = t; i <= P; i += RW_T) a0[i] = 0;                   // w (w[P] stays 0)
+  __syncthreads();
+  {
+    const uint64_t m = (uint64_t)P, calls = (m + 1) >> 1;
+    for (uint64_t j = t; j < calls; j += RW_T) {
+      uint64_t x[2];
+      rb_philox(seed_lo, seed_hi, j, r, 0u, x[0], x[1]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (2 * j + h >= m) continue;
+        int k = (int)__umul64hi(x[h], m);
+        k = k < P ? k : P - 1;                                    // (never taken)
+        atomicAdd(&a0[k], 1);
+      }
+    }
+  }
+  __syncthreads();
+  if (ho) {                                                       // tests only: w, cU, cE of this replicate, the rest of the row zero
+    const int64_t third = hstride / 3;
+    for (int64_t i = t; i < third; i += RW_T) {
+      const bool in = i <= P;
+      ho[i] = in ? a0[i] : 0;  ho[third + i] = in ? cu[i] : 0;  ho[2 * third + i] = in ? ce[i] : 0;
+    }
+  }
+  for (int i = t; i <= P; i += RW_T) a1[i] = a0[i];
+  __syncthreads();
+  rb_prefix<true>(S, a1, P + 1, chunk);                           // a1[k]: draws of ranks below k; P - a1[s] = TP* of a run from s
+  const int lo = t * chunk, hi = lo + chunk < P ? lo + chunk : P;
+  int32_t tot = 0;
+  for (int k = lo; k < hi; ++k) tot += cu[k];
+  int64_t L = (int64_t)(rk_block_scan(S, tot, nullptr) - tot);    // cU before this thread's ranks (every prefix <= Nn <= INT32_MAX)
+  double ap = 0.0;
+  int64_t num = 0;
+  for (int k = lo; k < hi; ++k) {
+    L += cu[k];
+    const uint32_t key = keys[k];
+    int s = k, e = k;                                             // the run of equal keys that holds k: [s, e]
+    if (k > 0 && keys[k - 1] == key) s = rk_lower(keys, 0, k - 1, key);
+    if (k + 1 < P && keys[k + 1] == key) e = rk_upper(keys, k + 2, P, key) - 1;
+    const int64_t w = a0[k], tp = P - a1[s];
+    // w == 0: nothing, by a select and not by a branch around the running sums (the note above ro_better).  The quotient may then
+    // be 0 / 0: the top positive above every negative, and not drawn
+    const double q = (double)(w * tp) / (double)(tp + Nn - L);
+    ap += w != 0 ? q : 0.0;
+    num += w * (2 * L + ce[e]);
+  }
+  red.d[t] = ap;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) red.d[t] += red.d[t + d];
+    __syncthreads();
+  }
+  const double ap_sum = red.d[0];
+  __syncthreads();
+  red.i[t] = num;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) red.i[t] += red.i[t + d];
+    __syncthreads();
+  }
+  if (t == 0) { rep_ap[r] = ap_sum / (double)P;  rep_num[r] = red.i[0]; }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1163,6 +1325,39 @@ int ggad_rank_delong_pair_f32(const float *score_a, const float *score_b, const 
   GGAD_CHECK_LAUNCH("rank_delong cross");
   k_rd_pair_final<<<dim3(1), dim3(RD_XG), 0, st>>>(A, B, part_x, (int)xg, out24, sums);
   GGAD_CHECK_LAUNCH("rank_delong pair final");
+  return GGAD_OK;
+}
+
+int32_t ggad_rank_bootstrap_max_pos(void) { return RB_MAXP; }
+int32_t ggad_rank_bootstrap_max_reps(void) { return RB_MAXREPS; }
+
+int64_t ggad_rank_bootstrap_workspace_elems(int64_t n, int64_t pos_cap) {
+  if (!rw_args_ok(n, pos_cap)) return 0;
+  return rw_layout(n, pos_cap).total();
+}
+
+int ggad_rank_bootstrap_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, uint64_t seed,
+                            int32_t reps, double *out16, double *rep_ap, int64_t *rep_auc_num, int32_t *hist_out, int32_t *workspace,
+                            ggad_stream_t stream) {
+  GGAD_REQUIRE(out16 && rep_ap && rep_auc_num && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) &&
+               (n == 0 || (score && label)));
+  GGAD_REQUIRE(reps >= 1 && reps <= RB_MAXREPS);
+  static ggad_lds_optin lds;
+  const int ready = ggad_lds_opt_in(lds, RB_LDS_MAX, k_rb_boot);
+  if (ready == 0) return GGAD_E_INVALID;
+  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "rank_bootstrap: this device cannot give k_rb_boot its LDS"); return GGAD_E_LAUNCH; }
+  RwFront F;
+  const int rc = rw_front(score, label, n, pos_cap, thres, workspace, stream, F);
+  if (rc != GGAD_OK) return rc;
+  k_rw_terms<<<dim3(F.L.tc), dim3(RW_T), 0, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, F.part_ap, F.part_num);
+  GGAD_CHECK_LAUNCH("rank_bootstrap terms");
+  k_rw_final<<<dim3(1), dim3(RW_TMAX), 0, F.st>>>(F.meta, F.part_ap, F.part_num, out16);
+  GGAD_CHECK_LAUNCH("rank_bootstrap final");
+  const int ls = (int)(F.L.pc < RB_MAXP ? F.L.pc : RB_MAXP) + 1;  // the LDS follows from (n, pos_cap) alone, like every grid here
+  k_rb_boot<<<dim3((unsigned)reps), dim3(RW_T), (size_t)4 * ls * 4, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, (uint32_t)seed,
+                                                                            (uint32_t)(seed >> 32), reps, ls, out16, rep_ap, rep_auc_num,
+                                                                            hist_out, 3 * (pos_cap + 1));
+  GGAD_CHECK_LAUNCH("rank_bootstrap replicates");
   return GGAD_OK;
 }
 

@@ -141,6 +141,13 @@ class ResidentSweep:
         cap = self._own_pos_cap("auc_ci")
         return auc_ci(self.scores() if scores is None else scores, self.labels, level, pos_cap=cap)
 
+    def ap_ci(self, level: float = 0.95, reps: int = 1000, seed: int = 0, scores: torch.Tensor = None):
+        """`metrics.ap_ci` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) on the
+        resident labels: average precision and AUROC with the percentile intervals of `reps` stratified bootstrap replicates."""
+        from .metrics import ap_ci
+        cap = self._own_pos_cap("ap_ci")
+        return ap_ci(self.scores() if scores is None else scores, self.labels, level, reps, seed, pos_cap=cap)
+
     def compare(self, scores_b: torch.Tensor, scores: torch.Tensor = None):
         """`metrics.compare_auc` of the current weights' scores (or of `scores`) against `scores_b`, another model's scores of the
         same list, on the resident labels: DeLong's paired test of the two AUROCs."""

@@ -221,6 +221,46 @@ def print_auc_ci(level, scores, idx_test, ano_label, dev):
     return ci
 
 
+def add_bootstrap_options(p):
+    """`--ap_ci [LEVEL]`, `--boot_reps B`, `--boot_seed S` (run.py only): the test average precision and AUROC with the percentile
+    intervals of a stratified bootstrap (`metrics.ap_ci`).  Off by default and absent from the namespace when not given.  Read them
+    with `bootstrap_options`; `check_bootstrap_options` after parsing."""
+    p.add_argument("--ap_ci", type=float, nargs="?", const=0.95, default=argparse.SUPPRESS, metavar="LEVEL",
+                   help="after training, or with --score: average precision and AUROC on idx_test with the percentile intervals of a "
+                        "stratified bootstrap at LEVEL (default 0.95), every replicate made on the device")
+    p.add_argument("--boot_reps", type=int, default=argparse.SUPPRESS, metavar="B", help="with --ap_ci: replicates (default 1000)")
+    p.add_argument("--boot_seed", type=int, default=argparse.SUPPRESS, metavar="S", help="with --ap_ci: the Philox seed (default 0)")
+    return p
+
+
+def bootstrap_options(a):
+    """(ap_ci level or None, replicates, seed) of a namespace."""
+    return getattr(a, "ap_ci", None) or None, getattr(a, "boot_reps", 1000), getattr(a, "boot_seed", 0)
+
+
+def check_bootstrap_options(p, a):
+    if hasattr(a, "ap_ci") and not 0.0 < float(a.ap_ci) < 1.0:
+        p.error("--ap_ci LEVEL: a confidence level inside (0, 1), as in --ap_ci 0.9")
+    if (hasattr(a, "boot_reps") or hasattr(a, "boot_seed")) and not hasattr(a, "ap_ci"):
+        p.error("--boot_reps and --boot_seed set the bootstrap of --ap_ci: they need --ap_ci")
+    if hasattr(a, "boot_reps") and a.boot_reps < 1:
+        p.error("--boot_reps B: at least one replicate")
+    if hasattr(a, "boot_seed") and not 0 <= a.boot_seed < 1 << 64:
+        p.error("--boot_seed S: an unsigned 64-bit integer")
+    return a
+
+
+def print_ap_ci(options, scores, idx_test, ano_label, dev):
+    """`--ap_ci LEVEL`: one `[ap_ci]` line for the (N,) device `scores` on idx_test, `options` the triple of `bootstrap_options`;
+    returns the `metrics.BootstrapInterval`."""
+    from .metrics import ap_ci, format_ap_ci
+    level, reps, seed = options
+    s, y, cap = _test_lists(scores, idx_test, ano_label, dev)
+    ci = ap_ci(s, y, level, reps, seed, pos_cap=cap)
+    print(format_ap_ci(ci))
+    return ci
+
+
 def print_compare(scores_a, scores_b, idx_test, ano_label, dev):
     """`--compare`: one `[compare]` line for two (N,) device score tensors on idx_test; returns the `metrics.AucComparison`."""
     from .metrics import compare_auc, format_compare

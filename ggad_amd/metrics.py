@@ -26,7 +26,11 @@ F1, macro-F1, G-mean, or recall at a bound on precision or on the false-positive
 
 `auc_ci` says how far an AUROC can be trusted -- DeLong's variance, standard error and normal interval -- and `compare_auc` whether two
 models' AUROCs on the same labels differ (DeLong's paired z and p), from `ggad_rank_delong_f32` / `ggad_rank_delong_pair_f32`: the
-same chain with the variance's numerators as exact 128-bit integers, one call and one read-back each."""
+same chain with the variance's numerators as exact 128-bit integers, one call and one read-back each.
+
+`ap_ci` does the same for average precision, which has no closed-form variance: the percentile interval, standard error and bias of a
+stratified bootstrap whose replicates `ggad_rank_bootstrap_f32` makes from the chain's sorted positives and two histograms alone, one
+workgroup per replicate; the AUROC's bootstrap interval comes with it."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -393,6 +397,111 @@ def compare_auc(scores_a: torch.Tensor, scores_b: torch.Tensor, labels_u8: torch
     return AucComparison(auc_a=float(o[0]), auc_b=float(o[8]), diff=float(o[20]), var_a=float(o[16]), var_b=float(o[17]),
                          cov=float(o[18]), var_diff=float(o[19]), z=z, p=1.0 if same else math.erfc(abs(z) / 2 ** 0.5),
                          n_pos=n_pos, n_neg=n_neg, identical=same)
+
+
+@dataclass(eq=False)
+class BootstrapInterval:
+    """Average precision and AUROC with stratified-bootstrap percentile intervals (`ap_ci`).  `ap`, `auc`: the point estimates of the
+    list; `*_lo`, `*_hi`: the `(1 - level) / 2` and `(1 + level) / 2` quantiles of the replicates (numpy's linear method); `*_se`:
+    their standard deviation (`ddof=1`; NaN for one replicate); `ap_bias`: the replicates' mean minus `ap`.  `ap_reps` float64 and
+    `auc_reps` float64 hold the `reps` replicates in replicate order; `report`: the `binary_report` dict at the call's `thres`."""
+    ap: float
+    ap_lo: float
+    ap_hi: float
+    ap_se: float
+    ap_bias: float
+    auc: float
+    auc_lo: float
+    auc_hi: float
+    auc_se: float
+    level: float
+    reps: int
+    seed: int
+    n_pos: int
+    n_neg: int
+    report: Dict[str, float]
+    ap_reps: "numpy.ndarray"
+    auc_reps: "numpy.ndarray"
+
+    def __eq__(self, other):
+        if not isinstance(other, BootstrapInterval):
+            return NotImplemented
+        mine, theirs = dict(self.__dict__), dict(other.__dict__)
+        return all(mine.pop(k).tobytes() == theirs.pop(k).tobytes() for k in ("ap_reps", "auc_reps")) and repr(mine) == repr(theirs)
+
+
+def format_ap_ci(ci: BootstrapInterval) -> str:
+    """The one `[ap_ci]` line of `main.py --ap_ci` and `run.py --ap_ci`."""
+    return (f"[ap_ci] AP {ci.ap!r} ± {ci.ap_se!r} ({ci.level:.0%}: [{ci.ap_lo!r}, {ci.ap_hi!r}], bias {ci.ap_bias!r}) "
+            f"AUROC {ci.auc!r} ({ci.level:.0%}: [{ci.auc_lo!r}, {ci.auc_hi!r}]) from {ci.reps} stratified replicates, seed {ci.seed}, "
+            f"on {ci.n_pos} positives, {ci.n_neg} negatives")
+
+
+def ap_ci(scores: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, reps: int = 1000, seed: int = 0, thres: float = 0.5,
+          pos_cap: Optional[int] = None) -> BootstrapInterval:
+    """Average precision (and AUROC) with the percentile interval of a stratified bootstrap at `level`: one `ggad_rank_bootstrap_f32`
+    call (csrc/rank_metrics.hip: the run-merge chain, then one workgroup per replicate that redraws the positives' ranks and the
+    negatives' bins with Philox4x32-10 under `seed` and never touches the elements again) and one read-back of `16 + 2 reps` words.
+    Stratified: every replicate holds the list's own counts of positives and negatives.  `thres` and `pos_cap` are
+    `rank_report_wide`'s (default `pos_cap`: the bootstrap's cap).  `ValueError` for a `level` outside (0, 1), `reps` outside
+    1..ggad_rank_bootstrap_max_reps(), a seed outside 64 bits, a NaN score, a label other than 0/1, one class only, fewer than two
+    positives or two negatives, more positives than `pos_cap` or than ggad_rank_bootstrap_max_pos() (an error: there is no second route)."""
+    import numpy as np
+    from . import _lib
+    who = "ap_ci"
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError(f"{who}: level = {level!r} is outside (0, 1)")
+    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+        raise ValueError(f"{who} takes float32 scores and uint8 labels of the same 1-D shape")
+    if scores.device.type != "cuda" or labels_u8.device != scores.device:
+        raise ValueError(f"{who} takes scores and labels on the same GPU (there is no CPU path)")
+    lib = _lib.load()
+    max_reps, boot_cap, cap = int(lib.ggad_rank_bootstrap_max_reps()), int(lib.ggad_rank_bootstrap_max_pos()), int(lib.ggad_rank_wide_max_pos())
+    if int(reps) != reps or not 1 <= int(reps) <= max_reps:
+        raise ValueError(f"{who}: reps = {reps!r} is outside 1..ggad_rank_bootstrap_max_reps() = {max_reps}")
+    if int(seed) != seed or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"{who}: seed = {seed!r} is not an unsigned 64-bit integer")
+    reps, seed, n = int(reps), int(seed), labels_u8.numel()
+    if pos_cap is None:
+        pos_cap = max(1, min(n, boot_cap))
+    if int(pos_cap) != pos_cap or not 1 <= int(pos_cap) <= cap:
+        raise ValueError(f"{who}: pos_cap = {pos_cap} is outside 1..ggad_rank_wide_max_pos() = {cap}")
+    pos_cap = int(pos_cap)
+    too_many = ("{} positives are more than ggad_rank_bootstrap_max_pos() = {}: a replicate's histograms no longer fit one "
+                "workgroup's LDS, and there is no fallback")
+    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
+    dev = labels_u8.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(1, int(lib.ggad_rank_bootstrap_workspace_elems(n, pos_cap))), dtype=torch.int32, device=dev)
+        out = torch.empty(16 + 2 * reps, dtype=torch.float64, device=dev)          # out16, rep_ap, rep_auc_num (int64 words)
+        base = _lib.ptr(out)
+        _lib.call("ggad_rank_bootstrap_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, pos_cap, float(thres), seed, reps, base,
+                  base + 16 * 8, base + (16 + reps) * 8, 0, _lib.ptr(ws))
+        host = out.cpu().numpy()
+    o = host[:16].tolist()
+    status, n_pos = int(o[15]), int(o[6])
+    if status == 2 and pos_cap >= boot_cap:
+        raise ValueError(f"{who}: " + too_many.format(n_pos, boot_cap))
+    _raise_on_status(who, status if status in (1, 2, 3, 4) else 0, n_pos, pos_cap)
+    tp, fp, fn, tn = (int(v) for v in o[2:6])
+    if status == 9:
+        raise ValueError(f"{who}: " + too_many.format(n_pos, boot_cap))
+    if status == 8:
+        raise ValueError(f"{who}: {tp + fn} positives and {fp + tn} negatives: a stratified bootstrap {_TOO_FEW}")
+    if status != 0:
+        raise ValueError(f"{who}: ggad_rank_bootstrap_f32 left status {status}")
+    ap_reps = host[16:16 + reps].copy()
+    auc_reps = host[16 + reps:].view(np.int64).astype(np.float64) / float(2 * (tp + fn) * (fp + tn))
+    q = [(1.0 - float(level)) / 2, (1.0 + float(level)) / 2]
+    ap_lo, ap_hi = (float(v) for v in np.quantile(ap_reps, q))
+    auc_lo, auc_hi = (float(v) for v in np.quantile(auc_reps, q))
+    nan = float("nan")
+    ap, auc = float(o[1]), float(o[0])
+    return BootstrapInterval(ap=ap, ap_lo=ap_lo, ap_hi=ap_hi, ap_se=float(ap_reps.std(ddof=1)) if reps > 1 else nan,
+                             ap_bias=float(ap_reps.mean() - ap), auc=auc, auc_lo=auc_lo, auc_hi=auc_hi,
+                             auc_se=float(auc_reps.std(ddof=1)) if reps > 1 else nan, level=float(level), reps=reps, seed=seed,
+                             n_pos=tp + fn, n_neg=fp + tn, report={"auc": auc, "ap": ap, **_confusion_scores(tp, fp, fn, tn)},
+                             ap_reps=ap_reps, auc_reps=auc_reps)
 
 
 @dataclass

@@ -31,6 +31,9 @@ split (`src/model_handler.py:260-261`) --, so the threshold, like the checkpoint
 DeLong's standard error and the normal interval at LEVEL as one `[auc_ci]` line (`metrics.auc_ci`, csrc/rank_metrics.hip: exact
 integer numerators), kept in `self.auc_interval`; `score(checkpoint, compare=other)` scores the same list under a second checkpoint and
 prints DeLong's paired test of the two AUROCs as one `[compare]` line (`metrics.compare_auc`), kept in `self.auc_comparison`.
+``ap_ci: LEVEL`` with ``boot_reps`` / ``boot_seed`` (`model: 'GCN'`; 0 = off): at the same two places, behind the `[auc_ci]` line, the
+test average precision and AUROC are printed with the percentile intervals of a stratified bootstrap as one `[ap_ci]` line
+(`metrics.ap_ci`, csrc/rank_metrics.hip: one workgroup per replicate), kept in `self.ap_interval`; the sweep's device scores are reused.
 ``explain: M`` / ``explain_out`` (with ``top_k`` > 0): every node of the ranked list is explained on the device (`explain.explain`,
 csrc/explain.hip): its logit split exactly per feature and per neighbour, the M signed-greatest neighbour contributions listed; kept in
 `self.explained`, reported in one `[explain]` line and written to an `.npz`; after `train()` and by `score(checkpoint)` alike.
@@ -139,6 +142,14 @@ class ModelHandler(object):
                 raise ValueError("config key `auc_ci` needs `model: 'GCN'`: the interval is made from the scores of the GGAD test sweep")
             if not 0.0 < self.auc_level < 1.0:
                 raise ValueError(f"config key `auc_ci`: {args.auc_ci!r} is not a confidence level inside (0, 1) (0 = off)")
+        self.ap_interval = None
+        self.ap_level = float(getattr(args, "ap_ci", 0) or 0)    # config key `ap_ci`: the level of the bootstrap interval, 0 = off
+        self.boot_reps, self.boot_seed = getattr(args, "boot_reps", 1000), getattr(args, "boot_seed", 0)
+        if self.ap_level:
+            if getattr(args, "model", None) != "GCN":
+                raise ValueError("config key `ap_ci` needs `model: 'GCN'`: the interval is made from the scores of the GGAD test sweep")
+            if not 0.0 < self.ap_level < 1.0:
+                raise ValueError(f"config key `ap_ci`: {args.ap_ci!r} is not a confidence level inside (0, 1) (0 = off)")
         self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
 
     @staticmethod
@@ -199,6 +210,21 @@ class ModelHandler(object):
         self.auc_interval = ci
         if verbose:
             print(format_auc_ci(ci))
+        return ci
+
+    def _ap_ci(self, scores, labels, sweep, verbose=True):
+        """Config key `ap_ci`: the bootstrap interval of `scores` (the device scores of a sweep, already made) on `labels`, one
+        `[ap_ci]` line; kept in `self.ap_interval`."""
+        from .metrics import ap_ci, format_ap_ci
+        if sweep is not None:
+            ci = sweep.ap_ci(self.ap_level, self.boot_reps, self.boot_seed, scores=scores)
+        else:
+            lab = np.asarray(labels).reshape(-1).astype(np.uint8)
+            ci = ap_ci(scores, torch.from_numpy(lab).to(scores.device), self.ap_level, self.boot_reps, self.boot_seed,
+                       pos_cap=max(1, int(np.count_nonzero(lab == 1))))
+        self.ap_interval = ci
+        if verbose:
+            print(format_ap_ci(ci))
         return ci
 
     def _compare(self, scores, other, gnn_model, engine, ids, labels, sweep):
@@ -329,6 +355,8 @@ class ModelHandler(object):
         self.ranked = self._rank(scores, ids, labels, sweep, k, model=gnn_model) if k else None
         if self.auc_level and labels is not None:
             self._auc_ci(scores, labels, sweep)
+        if self.ap_level and labels is not None:
+            self._ap_ci(scores, labels, sweep)
         if compare is not None:
             self._compare(scores, compare, gnn_model, engine, ids, labels, sweep)
         return scores, self.ranked
@@ -454,7 +482,7 @@ class ModelHandler(object):
                 dist.broadcast(engine.params, src=0)          # every rank tests the restored weights
             engine.sync_params()
         top_k = int(getattr(args, "top_k", 0) or 0)
-        keep = [] if top_k or self.auc_level else None    # config keys `top_k`, `auc_ci`: the sweep's device scores are kept, not made twice
+        keep = [] if top_k or self.auc_level or self.ap_level else None    # config keys `top_k`, `auc_ci`, `ap_ci`: the sweep's device scores are kept, not made twice
         thres = args.thres
         if self.thres_select is not None:            # config key `thres_select`: the closing sweep reports at the chosen threshold
             op = self._choose_threshold(gnn_model, idx_valid, y_valid, sweep_valid, dist, verbose=rank == 0)
@@ -469,6 +497,8 @@ class ModelHandler(object):
             self._rank(keep[0], idx_test, y_test, sweep_test, top_k, verbose=rank == 0, model=gnn_model)
         if self.auc_level:
             self._auc_ci(keep[0], y_test, sweep_test, verbose=rank == 0)
+        if self.ap_level:
+            self._ap_ci(keep[0], y_test, sweep_test, verbose=rank == 0)
         return res
 
 

@@ -1309,6 +1309,37 @@ int ggad_rank_delong_pair_f32(const float *score_a, const float *score_b, const 
                               float thres, double *out24, int64_t *sums, int32_t *workspace, ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Stratified bootstrap of average precision and AUROC (rank_metrics.hip).  The front and the first eight doubles are
+ * ggad_rank_wide_f32's; one more launch makes `reps` replicates, one workgroup each, from the sorted keys of the P positives and the
+ * two histograms alone (histU[b]: negatives with exactly b positives at or below them; histE[k]: those of bin k + 1 that tie the run
+ * of equal positives ending at k).  Replicate r draws, with Philox4x32-10 (Random123) under key (seed & 0xffffffff, seed >> 32) and
+ * counter (j & 0xffffffff, j >> 32, r, stream) -- call j gives draws 2j and 2j + 1 as x = c0 | c1 << 32 and c2 | c3 << 32, a draw
+ * over m outcomes is u = (x * m) >> 64 --
+ *   stream 0: P draws over m = P, w[u] += 1 (u a sorted rank);
+ *   stream 1: Nn draws over m = Nn; with cum the inclusive prefix of histU, b = #{cum <= u}: cU[b] += 1, and cE[b - 1] += 1 when
+ *             b >= 1 and u - cum[b - 1] < histE[b - 1];
+ * and with L*_k the prefix of cU through k, [s, e] the run of equal keys that holds k and TP*_k = w[s] + ... + w[P - 1]
+ *   rep_ap[r]      = (1 / P) sum_k w_k TP*_k / (TP*_k + Nn - L*_k)   (w_k = 0 adds nothing; consecutive ranks per thread, then a tree)
+ *   rep_auc_num[r] = sum_k w_k (2 L*_k + cE[e])                      (exact; AUROC* = rep_auc_num[r] / (2 P Nn))
+ * The bootstrap is stratified (P and Nn are those of the list in every replicate).  out16: [0..7] ggad_rank_wide_f32's out8 for the
+ * same arguments, bit for bit; [8] reps, [9] P, [10] Nn, [11..14] 0.0, [15] status: [7] when [7] != 0; 8 = fewer than two
+ * positives or two negatives; 9 = more positives than ggad_rank_bootstrap_max_pos() = 9216 (the replicate's four histograms of
+ * P + 1 ints live in one CU's LDS: an error, there is no second route); else 0.  With a status other than 0 every rep_ap is NaN,
+ * every rep_auc_num 0.  hist_out: NULL, or reps rows of 3 (pos_cap + 1) int32 that receive w, cU and cE of every replicate at
+ * offsets 0, pos_cap + 1 and 2 (pos_cap + 1), zero beyond entry P (for tests).
+ * Limits, alignment and workspace rule of ggad_rank_wide_f32 (ggad_rank_bootstrap_workspace_elems(n, pos_cap) int32 elements, 0 =
+ * refused); outside them, with reps outside 1 .. ggad_rank_bootstrap_max_reps() = 4096, or with a NULL pointer other than
+ * hist_out: GGAD_E_INVALID and no launch.  No host synchronisation, LDS integer atomics only, every word a launch reads was
+ * written by an earlier launch of the same call: capturable and replayable; equal arguments give equal bits.
+ * ---------------------------------------------------------------------------------- */
+int32_t ggad_rank_bootstrap_max_pos(void);
+int32_t ggad_rank_bootstrap_max_reps(void);
+int64_t ggad_rank_bootstrap_workspace_elems(int64_t n, int64_t pos_cap);     /* int32 elements; 0 = refused */
+int ggad_rank_bootstrap_f32(const float *score, const uint8_t *label, int64_t n, int64_t pos_cap, float thres, uint64_t seed,
+                            int32_t reps, double *out16, double *rep_ap, int64_t *rep_auc_num, int32_t *hist_out, int32_t *workspace,
+                            ggad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Keep the best epoch's weights on the device (select.hip): the hand-off "if this epoch's validation metric is the best so far,
  * snapshot the parameters" without a host round trip.  Neither call takes a workspace; each reads only words the host or an earlier
  * launch wrote, so both are capturable and replayable behind ggad_rank_metrics_f32 / ggad_rank_wide_f32 in a captured epoch.

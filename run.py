@@ -16,6 +16,8 @@ the CPU generator are untouched.  `--save PATH` writes the weights (the best epo
 `--top_k_wide` ranks through csrc/topk.hip, K above 16,384 up to 4,194,304 (the whole test split of T-Finance or Elliptic).
 `--auc_ci [LEVEL]` (after training or with `--score`) prints the test AUROC with DeLong's standard error and interval; `--score A.pt
 --compare B.pt` tests the AUROCs of two checkpoints against each other on idx_test (`metrics.auc_ci` / `compare_auc`).
+`--ap_ci [LEVEL] [--boot_reps B] [--boot_seed S]` (at the same places) prints the test average precision and AUROC with the percentile
+intervals of a stratified bootstrap made on the device (`metrics.ap_ci`).
 """
 import os
 import sys
@@ -26,10 +28,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ggad_amd.fullgraph import FlatAdam, ggad_loss  # noqa: E402
-from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, add_compare_options, add_select_options, add_threshold_options,  # noqa: E402,F401
-                                       check_compare_options, check_select_options, check_threshold_options, choose_threshold,
-                                       compare_options, init_process, load_checkpoint, load_graph, make_parser, parse_with_defaults,
-                                       prepare, print_auc_ci, print_captured, print_compare, print_eval, print_median,
+from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, add_bootstrap_options, add_compare_options, add_select_options,  # noqa: E402,F401
+                                       add_threshold_options, bootstrap_options, check_bootstrap_options, check_compare_options,
+                                       check_select_options, check_threshold_options, choose_threshold, compare_options, init_process,
+                                       load_checkpoint, load_graph, make_parser, parse_with_defaults, prepare, print_ap_ci,
+                                       print_auc_ci, print_captured, print_compare, print_eval, print_median,
                                        print_threshold_test, save_checkpoint, score_from_checkpoint, select_options, threshold_option)
 from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
 from ggad_amd.model import Model  # noqa: E402
@@ -48,8 +51,9 @@ def parse(argv=None):
     add_select_options(p)
     add_threshold_options(p)
     add_compare_options(p)
+    add_bootstrap_options(p)
     a = check_threshold_options(p, check_select_options(p, parse_with_defaults(p, argv, {}, EPOCHS, fallback=(1e-3, 100))))
-    a = check_compare_options(p, a)
+    a = check_bootstrap_options(p, check_compare_options(p, a))
     a.mean, a.var = (0.02, 0.01) if a.dataset in ["reddit", "photo"] else (0.0, 0.0)      # run.py:61-66 (CLI values overwritten)
     return a
 
@@ -74,6 +78,8 @@ def main(argv=None):
             level, other = compare_options(args)
             if level:
                 print_auc_ci(level, scores, g.idx_test, g.ano_label, dev)
+            if bootstrap_options(args)[0]:
+                print_ap_ci(bootstrap_options(args), scores, g.idx_test, g.ano_label, dev)
             if other:                                    # the same model and graph under the second checkpoint's weights
                 model.load_state_dict(load_checkpoint(other, ft_size, args.embedding_dim)["state_dict"], strict=True)
                 model.eval()
@@ -247,12 +253,18 @@ def _fit(args, dev, full, feats, model, normal_label_idx, abnormal_label_idx, id
         print_threshold_test(all_scores.index_select(0, idx_test_dev), y_test_dev, point.thres)
         if history is not None:
             history["threshold"], history["threshold_scores"] = point, all_scores.cpu().numpy()
-    if compare_options(args)[0]:                 # --auc_ci: idx_test under the weights `model` ends with
-        model.eval()
+    if compare_options(args)[0] or bootstrap_options(args)[0]:    # --auc_ci, --ap_ci: idx_test under the weights `model` ends with,
+        model.eval()                                              # scored once for both
         with torch.no_grad():
-            ci = print_auc_ci(compare_options(args)[0], model.score(feats, full).detach(), idx_test, ano_label, dev)
-        if history is not None:
-            history["auc_ci"] = ci
+            end_scores = model.score(feats, full).detach()
+        if compare_options(args)[0]:
+            ci = print_auc_ci(compare_options(args)[0], end_scores, idx_test, ano_label, dev)
+            if history is not None:
+                history["auc_ci"] = ci
+        if bootstrap_options(args)[0]:
+            ci = print_ap_ci(bootstrap_options(args), end_scores, idx_test, ano_label, dev)
+            if history is not None:
+                history["ap_ci"] = ci
     if save:
         state = keeper.state_dict(model) if keeper is not None else model.state_dict()
         save_checkpoint(save, state, args, feats.shape[2], nb_nodes, best_epoch, best_value, threshold=point)

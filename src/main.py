@@ -152,6 +152,12 @@ if __name__ == "__main__":
     ap.add_argument("--auc_ci", type=float, nargs="?", const=0.95, default=None, metavar="LEVEL",
                     help="override the config's auc_ci (--handler ggad: after the closing test sweep, and with --score, print the test "
                          "AUROC with DeLong's standard error and the normal interval at LEVEL, default 0.95; 0 = off)")
+    ap.add_argument("--ap_ci", type=float, nargs="?", const=0.95, default=None, metavar="LEVEL",
+                    help="override the config's ap_ci (--handler ggad: after the closing test sweep, and with --score, print the test "
+                         "average precision and AUROC with the percentile intervals of a stratified bootstrap at LEVEL, default 0.95; "
+                         "0 = off)")
+    ap.add_argument("--boot_reps", type=int, default=None, metavar="B", help="override the config's boot_reps (replicates of --ap_ci)")
+    ap.add_argument("--boot_seed", type=int, default=None, metavar="S", help="override the config's boot_seed (Philox seed of --ap_ci)")
     ap.add_argument("--compare", type=str, default=None, metavar="CKPT_B",
                     help="with --score CKPT: score the test split under CKPT_B too and print DeLong's paired test of the two AUROCs")
     a = ap.parse_args()
@@ -163,6 +169,14 @@ if __name__ == "__main__":
         ap.error("--auc_ci serves --handler ggad only")
     if a.auc_ci is not None and not 0.0 <= a.auc_ci < 1.0:
         ap.error("--auc_ci LEVEL: a confidence level inside (0, 1), as in --auc_ci 0.9 (0 = off)")
+    if a.ap_ci and a.handler != "ggad":
+        ap.error("--ap_ci serves --handler ggad only")
+    if a.ap_ci is not None and not 0.0 <= a.ap_ci < 1.0:
+        ap.error("--ap_ci LEVEL: a confidence level inside (0, 1), as in --ap_ci 0.9 (0 = off)")
+    if a.boot_reps is not None and a.boot_reps < 1:
+        ap.error("--boot_reps B: at least one replicate")
+    if a.boot_seed is not None and not 0 <= a.boot_seed < 1 << 64:
+        ap.error("--boot_seed S: an unsigned 64-bit integer")
     if a.score_ids is not None and a.score is None:
         ap.error("--score_ids names the ids --score CKPT sweeps: it needs --score")
     if a.score is not None and a.handler != "ggad":
@@ -189,6 +203,9 @@ if __name__ == "__main__":
         cfg["thres_select"] = a.thres_select
     if a.auc_ci is not None:
         cfg["auc_ci"] = a.auc_ci
+    for key in ("ap_ci", "boot_reps", "boot_seed"):
+        if getattr(a, key) is not None:
+            cfg[key] = getattr(a, key)
     SCORE, SCORE_IDS, COMPARE = a.score, a.score_ids, a.compare
     use_handler(a.handler)
     init_distributed()
