@@ -297,6 +297,8 @@ SIGNATURES = {
     "ggad_rank_bootstrap_max_reps": (c_int32, []),
     "ggad_rank_bootstrap_workspace_elems": (c_int64, [_L, _L]),
     "ggad_rank_bootstrap_f32": (c_int32, [_P, _P, _L, _L, _F, c_uint64, _I, _P, _P, _P, _P, _P, _P]),
+    "ggad_rank_bootstrap_pair_workspace_elems": (c_int64, [_L, _L]),
+    "ggad_rank_bootstrap_pair_f32": (c_int32, [_P, _P, _P, _L, _L, _F, c_uint64, _I, _P, _P, _P, _P, _P, _P]),
     "ggad_select_max_tensors": (c_int32, []),
     "ggad_select_decide_f64": (c_int32, [_P, _I, _P, _P, _L, _P]),
     "ggad_select_copy_f32": (c_int32, [_I, _P, _P, _P, _P, _P]),

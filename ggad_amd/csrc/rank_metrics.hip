@@ -53,6 +53,12 @@
 // ggad_rank_bootstrap_f32: ggad_rank_wide_f32's launches as they are (out16[0..7] = its out8) and ONE more,
 //   k_rb_boot    one workgroup per replicate of a stratified bootstrap: Philox draws binned by a search in the prefix of histU, three
 //                integer histograms in LDS, AP* and the AUROC numerator of the replicate (the scheme: above rb_philox, further down)
+//
+// ggad_rank_bootstrap_pair_f32: ggad_rank_wide_f32's launches twice, into two halves of the workspace (out24[0..7], [8..15]), and
+//   k_rp_cells   one pass over the n elements: per negative a uint16 cell (ub | tie << 15) under A and under B, per positive its two
+//                uint16 ranks, stored at the element's number among its class in position order (k_rw_scan's headers give the offsets)
+//   k_rp_boot    one workgroup per replicate of a PAIRED bootstrap: the replicate draws element numbers, and each model's three
+//                histograms come from one 2-byte gather per draw; model A completely, then B from the same regenerated draws
 // Why runs of 2,048 and a merge by rank: head of rank_common.h.  Why the narrow chain stays although the wide one is twice as fast at
 // DGraph-Fin's size: inside a captured training epoch (run.py --select) a validation list of 3,935 nodes costs the wide chain six
 // launches against four, and the epoch is 21 us longer (profiles/rank_one_chain_time_line.json).
@@ -1094,6 +1100,53 @@ __device__ __forceinline__ void rb_prefix(RkScan &S, int32_t *a, int len, int ch
   __syncthreads();
 }
 
+union RbRed { double d[RW_T]; int64_t i[RW_T]; };                // the tree of rb_terms: the AP sum, then the numerator
+
+// The two formulas from a replicate's histograms in LDS, for k_rb_boot and k_rp_boot alike: a0 = w (a0[P] = 0), cu, ce; a1 is
+// scratch of P + 1 ints.  Consecutive ranks per thread, then the halving tree: ap_sum (before the division by P) and num, both valid
+// in thread 0.  Whole workgroup; the caller's stores to the histograms need a barrier before it, red none after it.
+__device__ __forceinline__ void rb_terms(RkScan &S, RbRed &red, const int32_t *a0, int32_t *a1, const int32_t *cu, const int32_t *ce,
+                                         const uint32_t *__restrict__ keys, int P, int64_t Nn, int chunk, double &ap_sum, int64_t &num_sum) {
+  const int t = threadIdx.x;
+  for (int i = t; i <= P; i += RW_T) a1[i] = a0[i];
+  __syncthreads();
+  rb_prefix<true>(S, a1, P + 1, chunk);                           // a1[k]: draws of ranks below k; P - a1[s] = TP* of a run from s
+  const int lo = t * chunk, hi = lo + chunk < P ? lo + chunk : P;
+  int32_t tot = 0;
+  for (int k = lo; k < hi; ++k) tot += cu[k];
+  int64_t L = (int64_t)(rk_block_scan(S, tot, nullptr) - tot);    // cU before this thread's ranks (every prefix <= Nn <= INT32_MAX)
+  double ap = 0.0;
+  int64_t num = 0;
+  for (int k = lo; k < hi; ++k) {
+    L += cu[k];
+    const uint32_t key = keys[k];
+    int s = k, e = k;                                             // the run of equal keys that holds k: [s, e]
+    if (k > 0 && keys[k - 1] == key) s = rk_lower(keys, 0, k - 1, key);
+    if (k + 1 < P && keys[k + 1] == key) e = rk_upper(keys, k + 2, P, key) - 1;
+    const int64_t w = a0[k], tp = P - a1[s];
+    // w == 0: nothing, by a select and not by a branch around the running sums (the note above ro_better).  The quotient may then
+    // be 0 / 0: the top positive above every negative, and not drawn
+    const double q = (double)(w * tp) / (double)(tp + Nn - L);
+    ap += w != 0 ? q : 0.0;
+    num += w * (2 * L + ce[e]);
+  }
+  red.d[t] = ap;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) red.d[t] += red.d[t + d];
+    __syncthreads();
+  }
+  ap_sum = red.d[0];
+  __syncthreads();
+  red.i[t] = num;
+  __syncthreads();
+  for (int d = RW_T / 2; d > 0; d >>= 1) {
+    if (t < d) red.i[t] += red.i[t + d];
+    __syncthreads();
+  }
+  num_sum = red.i[0];
+}
+
 // One workgroup = one replicate.  LDS: four arrays of ls >= P + 1 ints.  While the negatives are drawn they hold cum (the inclusive
 // prefix of histU), histE, cU and cE; then cum's place takes w, and histE's the exclusive prefix of w.
 __global__ void __launch_bounds__(RW_T) k_rb_boot(const int32_t *__restrict__ meta, const uint32_t *__restrict__ keys, int pc,
@@ -1102,7 +1155,7 @@ __global__ void __launch_bounds__(RW_T) k_rb_boot(const int32_t *__restrict__ me
                                                   int64_t *__restrict__ rep_num, int32_t *__restrict__ hist_out, int64_t hstride) {
   extern __shared__ __attribute__((aligned(16))) int32_t rb_lds[];
   __shared__ RkScan S;
-  __shared__ union { double d[RW_T]; int64_t i[RW_T]; } red;
+  __shared__ RbRed red;
   const int t = threadIdx.x;
   const uint32_t r = blockIdx.x;
   const int status = meta[5];
@@ -1167,43 +1220,174 @@ __global__ void __launch_bounds__(RW_T) k_rb_boot(const int32_t *__restrict__ me
       ho[i] = in ? a0[i] : 0;  ho[third + i] = in ? cu[i] : 0;  ho[2 * third + i] = in ? ce[i] : 0;
     }
   }
-  for (int i = t; i <= P; i += RW_T) a1[i] = a0[i];
-  __syncthreads();
-  rb_prefix<true>(S, a1, P + 1, chunk);                           // a1[k]: draws of ranks below k; P - a1[s] = TP* of a run from s
-  const int lo = t * chunk, hi = lo + chunk < P ? lo + chunk : P;
-  int32_t tot = 0;
-  for (int k = lo; k < hi; ++k) tot += cu[k];
-  int64_t L = (int64_t)(rk_block_scan(S, tot, nullptr) - tot);    // cU before this thread's ranks (every prefix <= Nn <= INT32_MAX)
-  double ap = 0.0;
-  int64_t num = 0;
-  for (int k = lo; k < hi; ++k) {
-    L += cu[k];
-    const uint32_t key = keys[k];
-    int s = k, e = k;                                             // the run of equal keys that holds k: [s, e]
-    if (k > 0 && keys[k - 1] == key) s = rk_lower(keys, 0, k - 1, key);
-    if (k + 1 < P && keys[k + 1] == key) e = rk_upper(keys, k + 2, P, key) - 1;
-    const int64_t w = a0[k], tp = P - a1[s];
-    // w == 0: nothing, by a select and not by a branch around the running sums (the note above ro_better).  The quotient may then
-    // be 0 / 0: the top positive above every negative, and not drawn
-    const double q = (double)(w * tp) / (double)(tp + Nn - L);
-    ap += w != 0 ? q : 0.0;
-    num += w * (2 * L + ce[e]);
+  double ap_sum;
+  int64_t num;
+  rb_terms(S, red, a0, a1, cu, ce, keys, P, Nn, chunk, ap_sum, num);
+  if (t == 0) { rep_ap[r] = ap_sum / (double)P;  rep_num[r] = num; }
+}
+
+// ---- Paired stratified bootstrap of two models on the same labels (ggad_rank_bootstrap_pair_f32).  A replicate draws ELEMENTS, and
+// every drawn element is counted at its own bin under A and under B.  An element is named by its number in position order --
+// positive j: the j-th element with label 1; negative u: the u-th with label 0 -- which is the same thing under both models; the
+// sorted ranks of k_rb_boot are not.  Replicate r draws P positive numbers on Philox stream 0 and Nn negative numbers on stream 1
+// (rb_philox, its key, counter layout and draw rule) and, per model M,
+//     w_M[rank_M(j)] += 1       rank_M(j): lower bound of the positive's key in M's sorted positives (a run of equal keys is counted
+//                               at its first rank: the bins strictly inside a run are empty, so TP*, L* and cE[e] there are the run's)
+//     cU_M[ub_M(u)] += 1        and cE_M[ub_M(u) - 1] += 1 when the negative ties the positive at ub_M(u) - 1
+// then rb_terms.  k_rp_cells makes the per-element tables once per call: uint16 cells ub | tie << 15 per negative number and uint16
+// ranks per positive number, one array per model, so that a replicate's pass over one model gathers 2 bytes per draw.
+struct RpLayout {                         // two halves of the run-merge chain's words, then the four uint16 tables
+  RwLayout L;
+  int64_t n;
+  int64_t half() const { return (L.total() + 3) & ~(int64_t)3; }
+  int64_t cell_words() const { return ((n + 1) / 2 + 3) & ~(int64_t)3; }          // uint16 per negative number (Nn <= n)
+  int64_t rank_words() const { return ((L.pc + 1) / 2 + 3) & ~(int64_t)3; }       // uint16 per positive number (P <= pc)
+  int64_t o_cell(int m) const { return 2 * half() + m * cell_words(); }
+  int64_t o_rank(int m) const { return 2 * half() + 2 * cell_words() + m * rank_words(); }
+  int64_t total() const { return o_rank(2); }
+};
+
+static_assert(RB_MAXP < (1 << 15), "a cell holds ub <= P in 15 bits beside the tie bit; a rank is below P");
+
+struct RpModel {                          // one model's words for k_rp_cells and k_rp_boot
+  const int32_t *meta;
+  const uint32_t *keys;
+  uint16_t *cell, *rank;
+};
+
+// the call's status (out24[23]) from the two summaries: the first non-zero chain status, 8, 9, else 0 (the same labels: P and Nn of A)
+__device__ __forceinline__ int rp_code(const int32_t *__restrict__ ma, const int32_t *__restrict__ mb) {
+  const int sa = ma[5], sb = mb[5], P = ma[4];
+  const int64_t Nn = (int64_t)ma[1] + ma[3];
+  if (sa != 0) return sa;
+  if (sb != 0) return sb;
+  if (P < 2 || Nn < 2) return RB_TOO_FEW;
+  return P > RB_MAXP ? RB_TOO_MANY : 0;
+}
+
+// One pass over the n elements in k_rw_scan's block ranges.  The numbering does not depend on the grid's schedule: a block's first
+// positive and negative numbers are sums over the headers k_rw_scan left for the blocks before it (A's: the labels are shared), and
+// inside a block every chunk of RW_T elements is numbered by a workgroup scan (both counts in one int: at most 1,024 each).
+__global__ void __launch_bounds__(RW_T) k_rp_cells(const float *__restrict__ score_a, const float *__restrict__ score_b,
+                                                   const uint8_t *__restrict__ label, int64_t n, int64_t per_block,
+                                                   const int32_t *__restrict__ hdr, RpModel A, RpModel B) {
+  __shared__ RkScan S;
+  if (rp_code(A.meta, B.meta) != 0) return;                       // (uniform over the launch; with 0, P <= pc and P <= RB_MAXP)
+  const int t = threadIdx.x, b = blockIdx.x;
+  const int P = A.meta[4];
+  const bool before = t < b;                                      // (b < RW_G <= RW_T: one thread per earlier header)
+  int neg0 = rk_block_sum(S.wsum, before ? hdr[t * RW_HDR + 1] + hdr[t * RW_HDR + 3] : 0);
+  int pos0 = rk_block_sum(S.wsum, before ? hdr[t * RW_HDR + 4] : 0);
+  const int64_t lo = (int64_t)b * per_block;
+  const int64_t hi = lo + per_block < n ? lo + per_block : n;
+  for (int64_t base = lo; base < hi; base += RW_T) {              // (whole workgroup: the scan needs every thread)
+    const int64_t i = base + t;
+    const int y = i < hi ? label[i] : 2;
+    const bool is_neg = y == 0, is_pos = y == 1;
+    int total;
+    const int incl = rk_block_scan(S, (is_neg ? 1 : 0) | (is_pos ? 1 << 16 : 0), &total);
+    if (is_neg) {
+      const int64_t u = (int64_t)neg0 + (incl & 0xFFFF) - 1;      // < Nn <= n
+      const uint32_t ka = rk_key(score_a[i]), kb = rk_key(score_b[i]);
+      const int ua = rk_upper(A.keys, 0, P, ka), ub = rk_upper(B.keys, 0, P, kb);
+      A.cell[u] = (uint16_t)(ua | ((ua > 0 && A.keys[ua - 1] == ka) ? 1 << 15 : 0));
+      B.cell[u] = (uint16_t)(ub | ((ub > 0 && B.keys[ub - 1] == kb) ? 1 << 15 : 0));
+    } else if (is_pos) {
+      const int j = pos0 + (incl >> 16) - 1;                      // < P
+      A.rank[j] = (uint16_t)rk_lower(A.keys, 0, P, rk_key(score_a[i]));
+      B.rank[j] = (uint16_t)rk_lower(B.keys, 0, P, rk_key(score_b[i]));
+    }
+    neg0 += total & 0xFFFF;
+    pos0 += total >> 16;
   }
-  red.d[t] = ap;
-  __syncthreads();
-  for (int d = RW_T / 2; d > 0; d >>= 1) {
-    if (t < d) red.d[t] += red.d[t + d];
+}
+
+constexpr int RP_BATCH = 4;               // Philox calls of one thread whose 2 RP_BATCH gathers are in flight together
+constexpr uint32_t RP_NONE = 0xFFFFu;     // no draw (ub = 32,767 cannot be)
+
+// One workgroup = one replicate: model A completely, then model B from the same draws (counter-based: regenerated, not stored).
+// LDS: k_rb_boot's four arrays of ls >= P + 1 ints -- w, rb_terms' scratch, cU, cE.  LDS integer atomics only.
+__global__ void __launch_bounds__(RW_T) k_rp_boot(RpModel A, RpModel B, uint32_t seed_lo, uint32_t seed_hi, int reps, int ls,
+                                                  double *__restrict__ out24, double *__restrict__ rep_ap,
+                                                  int64_t *__restrict__ rep_num, int32_t *__restrict__ hist_out, int64_t hstride) {
+  extern __shared__ __attribute__((aligned(16))) int32_t rb_lds[];
+  __shared__ RkScan S;
+  __shared__ RbRed red;
+  const int t = threadIdx.x;
+  const uint32_t r = blockIdx.x;
+  const int P = A.meta[4];
+  const int64_t Nn = (int64_t)A.meta[1] + A.meta[3];
+  const int code = rp_code(A.meta, B.meta);
+  if (r == 0 && t == 0) {
+    out24[16] = (double)reps;  out24[17] = (double)P;  out24[18] = (double)Nn;
+    out24[19] = 0.0;  out24[20] = 0.0;  out24[21] = 0.0;  out24[22] = 0.0;
+    out24[23] = (double)code;
+  }
+  int32_t *ho = hist_out ? hist_out + (int64_t)r * hstride : nullptr;
+  if (code != 0) {                                                // (uniform over the launch)
+    if (t < 2) { rep_ap[t * reps + r] = __longlong_as_double(0x7FF8000000000000ll);  rep_num[t * reps + r] = 0; }
+    if (ho) for (int64_t i = t; i < hstride; i += RW_T) ho[i] = 0;
+    return;
+  }
+  int32_t *a0 = rb_lds, *a1 = a0 + ls, *cu = a1 + ls, *ce = cu + ls;       // P + 1 <= ls
+  const int chunk = (P + 1 + RW_T - 1) / RW_T;
+  const int64_t third = hstride / 6;
+#pragma unroll 1
+  for (int model = 0; model < 2; ++model) {
+    const RpModel &M = model ? B : A;
+    const uint16_t *__restrict__ cell = M.cell, *__restrict__ rank = M.rank;
+    __syncthreads();                                              // (the model before has read its histograms)
+    for (int i = t; i <= P; i += RW_T) { a0[i] = 0;  cu[i] = 0;  ce[i] = 0; }
     __syncthreads();
-  }
-  const double ap_sum = red.d[0];
-  __syncthreads();
-  red.i[t] = num;
-  __syncthreads();
-  for (int d = RW_T / 2; d > 0; d >>= 1) {
-    if (t < d) red.i[t] += red.i[t + d];
+    {
+      const uint64_t m = (uint64_t)Nn, calls = (m + 1) >> 1;
+      for (uint64_t j0 = t; j0 < calls; j0 += (uint64_t)RP_BATCH * RW_T) {
+        uint32_t c[2 * RP_BATCH];
+#pragma unroll
+        for (int q = 0; q < RP_BATCH; ++q) {
+          const uint64_t j = j0 + (uint64_t)q * RW_T;
+          uint64_t x[2] = {0, 0};
+          if (j < calls) rb_philox(seed_lo, seed_hi, j, r, 1u, x[0], x[1]);
+#pragma unroll
+          for (int h = 0; h < 2; ++h)                             // (an odd count: the last call is half used)
+            c[2 * q + h] = 2 * j + h < m ? (uint32_t)cell[__umul64hi(x[h], m)] : RP_NONE;      // negative number < Nn
+        }
+#pragma unroll
+        for (int q = 0; q < 2 * RP_BATCH; ++q) {
+          if (c[q] == RP_NONE) continue;
+          const int bin = (int)(c[q] & 0x7FFFu);                  // <= P
+          atomicAdd(&cu[bin], 1);
+          if ((c[q] >> 15) && bin >= 1) atomicAdd(&ce[bin - 1], 1);
+        }
+      }
+    }
+    {
+      const uint64_t m = (uint64_t)P, calls = (m + 1) >> 1;
+      for (uint64_t j = t; j < calls; j += RW_T) {
+        uint64_t x[2];
+        rb_philox(seed_lo, seed_hi, j, r, 0u, x[0], x[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (2 * j + h >= m) continue;
+          int k = (int)rank[__umul64hi(x[h], m)];                 // positive number < P
+          k = k < P ? k : P - 1;                                  // (never taken)
+          atomicAdd(&a0[k], 1);
+        }
+      }
+    }
     __syncthreads();
+    if (ho) {                                                     // tests only: w, cU, cE of this model, the rest of the row zero
+      int32_t *hm = ho + 3 * third * model;
+      for (int64_t i = t; i < third; i += RW_T) {
+        const bool in = i <= P;
+        hm[i] = in ? a0[i] : 0;  hm[third + i] = in ? cu[i] : 0;  hm[2 * third + i] = in ? ce[i] : 0;
+      }
+    }
+    double ap_sum;
+    int64_t num;
+    rb_terms(S, red, a0, a1, cu, ce, M.keys, P, Nn, chunk, ap_sum, num);
+    if (t == 0) { rep_ap[model * reps + r] = ap_sum / (double)P;  rep_num[model * reps + r] = num; }
   }
-  if (t == 0) { rep_ap[r] = ap_sum / (double)P;  rep_num[r] = red.i[0]; }
 }
 
 }  // namespace
@@ -1358,6 +1542,42 @@ int ggad_rank_bootstrap_f32(const float *score, const uint8_t *label, int64_t n,
                                                                             (uint32_t)(seed >> 32), reps, ls, out16, rep_ap, rep_auc_num,
                                                                             hist_out, 3 * (pos_cap + 1));
   GGAD_CHECK_LAUNCH("rank_bootstrap replicates");
+  return GGAD_OK;
+}
+
+int64_t ggad_rank_bootstrap_pair_workspace_elems(int64_t n, int64_t pos_cap) {
+  if (!rw_args_ok(n, pos_cap)) return 0;
+  return RpLayout{rw_layout(n, pos_cap), n}.total();
+}
+
+int ggad_rank_bootstrap_pair_f32(const float *score_a, const float *score_b, const uint8_t *label, int64_t n, int64_t pos_cap,
+                                 float thres, uint64_t seed, int32_t reps, double *out24, double *rep_ap, int64_t *rep_auc_num,
+                                 int32_t *hist_out, int32_t *workspace, ggad_stream_t stream) {
+  GGAD_REQUIRE(out24 && rep_ap && rep_auc_num && workspace && ((uintptr_t)workspace & 15) == 0 && rw_args_ok(n, pos_cap) &&
+               (n == 0 || (score_a && score_b && label)));
+  GGAD_REQUIRE(reps >= 1 && reps <= RB_MAXREPS);
+  static ggad_lds_optin lds;
+  const int ready = ggad_lds_opt_in(lds, RB_LDS_MAX, k_rp_boot);
+  if (ready == 0) return GGAD_E_INVALID;
+  if (ready != 1) { ggad_set_error(hipErrorInvalidValue, "rank_bootstrap_pair: this device cannot give k_rp_boot its LDS"); return GGAD_E_LAUNCH; }
+  const RpLayout D{rw_layout(n, pos_cap), n};
+  RpModel M[2];
+  RwFront F;
+  for (int m = 0; m < 2; ++m) {
+    const int rc = rw_front(m ? score_b : score_a, label, n, pos_cap, thres, workspace + m * D.half(), stream, F);
+    if (rc != GGAD_OK) return rc;
+    k_rw_terms<<<dim3(F.L.tc), dim3(RW_T), 0, F.st>>>(F.meta, F.keys, (int)F.L.pc, F.hist, F.part_ap, F.part_num);
+    GGAD_CHECK_LAUNCH("rank_bootstrap_pair terms");
+    k_rw_final<<<dim3(1), dim3(RW_TMAX), 0, F.st>>>(F.meta, F.part_ap, F.part_num, out24 + 8 * m);
+    GGAD_CHECK_LAUNCH("rank_bootstrap_pair final");
+    M[m] = {F.meta, F.keys, reinterpret_cast<uint16_t *>(workspace + D.o_cell(m)), reinterpret_cast<uint16_t *>(workspace + D.o_rank(m))};
+  }
+  k_rp_cells<<<dim3(D.L.g), dim3(RW_T), 0, F.st>>>(score_a, score_b, label, n, D.L.per_block, workspace + D.L.o_hdr(), M[0], M[1]);
+  GGAD_CHECK_LAUNCH("rank_bootstrap_pair cells");
+  const int ls = (int)(D.L.pc < RB_MAXP ? D.L.pc : RB_MAXP) + 1;
+  k_rp_boot<<<dim3((unsigned)reps), dim3(RW_T), (size_t)4 * ls * 4, F.st>>>(M[0], M[1], (uint32_t)seed, (uint32_t)(seed >> 32), reps, ls, out24,
+                                                                            rep_ap, rep_auc_num, hist_out, 6 * (pos_cap + 1));
+  GGAD_CHECK_LAUNCH("rank_bootstrap_pair replicates");
   return GGAD_OK;
 }
 

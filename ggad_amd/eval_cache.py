@@ -155,6 +155,13 @@ class ResidentSweep:
         cap = self._own_pos_cap("compare")
         return compare_auc(self.scores() if scores is None else scores, scores_b, self.labels, pos_cap=cap)
 
+    def compare_ap(self, scores_b: torch.Tensor, scores: torch.Tensor = None, level: float = 0.95, reps: int = 1000, seed: int = 0):
+        """`metrics.compare_ap` of the current weights' scores (or of `scores`) against `scores_b`, another model's scores of the
+        same list, on the resident labels: the paired stratified bootstrap of the two average precisions."""
+        from .metrics import compare_ap
+        cap = self._own_pos_cap("compare_ap")
+        return compare_ap(self.scores() if scores is None else scores, scores_b, self.labels, level, reps, seed, pos_cap=cap)
+
     def top_k(self, k: int, scores: torch.Tensor = None, wide: bool = False):
         """`metrics.top_k` of the current weights' scores (or of `scores`, a result of `scores()` the caller already holds) with the
         sweep's ids and resident labels: the `Ranked` head of the list, `ids` = node ids.  Nothing is uploaded and no plan is built.

@@ -177,16 +177,20 @@ def print_threshold_test(test_scores, y_dev, thres, alerts=False):
 
 
 def add_compare_options(p):
-    """`--auc_ci [LEVEL]` / `--compare CKPT_B` (run.py only): the test AUROC with DeLong's standard error and interval
-    (`metrics.auc_ci`), and DeLong's paired test of two checkpoints' AUROCs on idx_test (`metrics.compare_auc`).  Off by default and,
-    like the options of `add_select_options`, absent from the namespace when not given.  Read them with `compare_options`;
-    `check_compare_options` after parsing."""
+    """`--auc_ci [LEVEL]` / `--compare CKPT_B` / `--compare_ap [LEVEL]` (run.py only): the test AUROC with DeLong's standard error and
+    interval (`metrics.auc_ci`), DeLong's paired test of two checkpoints' AUROCs on idx_test (`metrics.compare_auc`) and, with it,
+    the paired bootstrap of their average precisions (`metrics.compare_ap`; `--boot_reps` / `--boot_seed` of `add_bootstrap_options`).
+    Off by default and, like the options of `add_select_options`, absent from the namespace when not given.  Read them with
+    `compare_options` and `compare_ap_option`; `check_compare_options` after parsing."""
     p.add_argument("--auc_ci", type=float, nargs="?", const=0.95, default=argparse.SUPPRESS, metavar="LEVEL",
                    help="after training, or with --score: the AUROC on idx_test with DeLong's standard error and the normal interval at "
                         "LEVEL (default 0.95), from exact counts on the device")
     p.add_argument("--compare", type=str, default=argparse.SUPPRESS, metavar="CKPT_B",
                    help="with --score CKPT: score idx_test under CKPT_B too and test the two AUROCs against each other (DeLong's paired "
                         "z and two-sided p)")
+    p.add_argument("--compare_ap", type=float, nargs="?", const=0.95, default=argparse.SUPPRESS, metavar="LEVEL",
+                   help="with --score CKPT --compare CKPT_B: test the two average precisions against each other too, by a paired "
+                        "stratified bootstrap made on the device (interval of the difference at LEVEL, default 0.95, and two-sided p)")
     return p
 
 
@@ -195,8 +199,17 @@ def compare_options(a):
     return getattr(a, "auc_ci", None) or None, getattr(a, "compare", None) or None
 
 
+def compare_ap_option(a):
+    """The level of `--compare_ap`, or None."""
+    return getattr(a, "compare_ap", None) or None
+
+
 def check_compare_options(p, a):
     level, other = compare_options(a)
+    if hasattr(a, "compare_ap") and not 0.0 < float(a.compare_ap) < 1.0:
+        p.error("--compare_ap LEVEL: a confidence level inside (0, 1), as in --compare_ap 0.9")
+    if hasattr(a, "compare_ap") and not other:
+        p.error("--compare_ap tests the average precisions of --score CKPT and --compare CKPT_B: it needs --compare")
     if hasattr(a, "auc_ci") and not 0.0 < float(a.auc_ci) < 1.0:
         p.error("--auc_ci LEVEL: a confidence level inside (0, 1), as in --auc_ci 0.9")
     if other and not select_options(a)[2]:
@@ -223,13 +236,13 @@ def print_auc_ci(level, scores, idx_test, ano_label, dev):
 
 def add_bootstrap_options(p):
     """`--ap_ci [LEVEL]`, `--boot_reps B`, `--boot_seed S` (run.py only): the test average precision and AUROC with the percentile
-    intervals of a stratified bootstrap (`metrics.ap_ci`).  Off by default and absent from the namespace when not given.  Read them
-    with `bootstrap_options`; `check_bootstrap_options` after parsing."""
+    intervals of a stratified bootstrap (`metrics.ap_ci`); B and S also serve `--compare_ap`.  Off by default and absent from the
+    namespace when not given.  Read them with `bootstrap_options`; `check_bootstrap_options` after parsing."""
     p.add_argument("--ap_ci", type=float, nargs="?", const=0.95, default=argparse.SUPPRESS, metavar="LEVEL",
                    help="after training, or with --score: average precision and AUROC on idx_test with the percentile intervals of a "
                         "stratified bootstrap at LEVEL (default 0.95), every replicate made on the device")
-    p.add_argument("--boot_reps", type=int, default=argparse.SUPPRESS, metavar="B", help="with --ap_ci: replicates (default 1000)")
-    p.add_argument("--boot_seed", type=int, default=argparse.SUPPRESS, metavar="S", help="with --ap_ci: the Philox seed (default 0)")
+    p.add_argument("--boot_reps", type=int, default=argparse.SUPPRESS, metavar="B", help="with --ap_ci or --compare_ap: replicates (default 1000)")
+    p.add_argument("--boot_seed", type=int, default=argparse.SUPPRESS, metavar="S", help="with --ap_ci or --compare_ap: the Philox seed (default 0)")
     return p
 
 
@@ -241,8 +254,8 @@ def bootstrap_options(a):
 def check_bootstrap_options(p, a):
     if hasattr(a, "ap_ci") and not 0.0 < float(a.ap_ci) < 1.0:
         p.error("--ap_ci LEVEL: a confidence level inside (0, 1), as in --ap_ci 0.9")
-    if (hasattr(a, "boot_reps") or hasattr(a, "boot_seed")) and not hasattr(a, "ap_ci"):
-        p.error("--boot_reps and --boot_seed set the bootstrap of --ap_ci: they need --ap_ci")
+    if (hasattr(a, "boot_reps") or hasattr(a, "boot_seed")) and not (hasattr(a, "ap_ci") or hasattr(a, "compare_ap")):
+        p.error("--boot_reps and --boot_seed set the bootstrap of --ap_ci and --compare_ap: they need one of them")
     if hasattr(a, "boot_reps") and a.boot_reps < 1:
         p.error("--boot_reps B: at least one replicate")
     if hasattr(a, "boot_seed") and not 0 <= a.boot_seed < 1 << 64:
@@ -268,6 +281,18 @@ def print_compare(scores_a, scores_b, idx_test, ano_label, dev):
     b = _test_lists(scores_b, idx_test, ano_label, dev)[0]
     c = compare_auc(a, b, y, pos_cap=cap)
     print(format_compare(c))
+    return c
+
+
+def print_compare_ap(options, scores_a, scores_b, idx_test, ano_label, dev):
+    """`--compare_ap LEVEL`: one `[compare_ap]` line for two (N,) device score tensors on idx_test, `options` = (level, replicates,
+    seed); returns the `metrics.ApComparison`."""
+    from .metrics import compare_ap, format_compare_ap
+    level, reps, seed = options
+    a, y, cap = _test_lists(scores_a, idx_test, ano_label, dev)
+    b = _test_lists(scores_b, idx_test, ano_label, dev)[0]
+    c = compare_ap(a, b, y, level, reps, seed, pos_cap=cap)
+    print(format_compare_ap(c))
     return c
 
 

@@ -30,7 +30,9 @@ same chain with the variance's numerators as exact 128-bit integers, one call an
 
 `ap_ci` does the same for average precision, which has no closed-form variance: the percentile interval, standard error and bias of a
 stratified bootstrap whose replicates `ggad_rank_bootstrap_f32` makes from the chain's sorted positives and two histograms alone, one
-workgroup per replicate; the AUROC's bootstrap interval comes with it."""
+workgroup per replicate; the AUROC's bootstrap interval comes with it.  `compare_ap` says whether two models' average precisions on the
+same labels differ: a PAIRED bootstrap (`ggad_rank_bootstrap_pair_f32`), whose replicates draw elements and count each at its own bin
+under either model -- the interval, standard error and two-sided p-value of the difference."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -437,24 +439,19 @@ def format_ap_ci(ci: BootstrapInterval) -> str:
             f"on {ci.n_pos} positives, {ci.n_neg} negatives")
 
 
-def ap_ci(scores: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, reps: int = 1000, seed: int = 0, thres: float = 0.5,
-          pos_cap: Optional[int] = None) -> BootstrapInterval:
-    """Average precision (and AUROC) with the percentile interval of a stratified bootstrap at `level`: one `ggad_rank_bootstrap_f32`
-    call (csrc/rank_metrics.hip: the run-merge chain, then one workgroup per replicate that redraws the positives' ranks and the
-    negatives' bins with Philox4x32-10 under `seed` and never touches the elements again) and one read-back of `16 + 2 reps` words.
-    Stratified: every replicate holds the list's own counts of positives and negatives.  `thres` and `pos_cap` are
-    `rank_report_wide`'s (default `pos_cap`: the bootstrap's cap).  `ValueError` for a `level` outside (0, 1), `reps` outside
-    1..ggad_rank_bootstrap_max_reps(), a seed outside 64 bits, a NaN score, a label other than 0/1, one class only, fewer than two
-    positives or two negatives, more positives than `pos_cap` or than ggad_rank_bootstrap_max_pos() (an error: there is no second route)."""
-    import numpy as np
+def _bootstrap_call(who: str, lists, labels_u8, level, reps, seed, thres: float, pos_cap):
+    """The argument checks of `ap_ci` / `compare_ap` for every score list of `lists` (one: `ggad_rank_bootstrap_f32`, two:
+    `ggad_rank_bootstrap_pair_f32`), the workspace, ONE native call, ONE read-back and the `ValueError` of every status: (the 16 or
+    24 doubles as a list, the replicate words behind them -- every list's `rep_ap`, then every list's `rep_auc_num` as int64 words
+    -- as a float64 array, reps, seed)."""
     from . import _lib
-    who = "ap_ci"
     if not 0.0 < float(level) < 1.0:
         raise ValueError(f"{who}: level = {level!r} is outside (0, 1)")
-    if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
-        raise ValueError(f"{who} takes float32 scores and uint8 labels of the same 1-D shape")
-    if scores.device.type != "cuda" or labels_u8.device != scores.device:
-        raise ValueError(f"{who} takes scores and labels on the same GPU (there is no CPU path)")
+    for scores in lists:
+        if scores.dtype != torch.float32 or labels_u8.dtype != torch.uint8 or scores.dim() != 1 or scores.shape != labels_u8.shape:
+            raise ValueError(f"{who} takes float32 scores and uint8 labels of the same 1-D shape")
+        if scores.device.type != "cuda" or labels_u8.device != scores.device:
+            raise ValueError(f"{who} takes scores and labels on the same GPU (there is no CPU path)")
     lib = _lib.load()
     max_reps, boot_cap, cap = int(lib.ggad_rank_bootstrap_max_reps()), int(lib.ggad_rank_bootstrap_max_pos()), int(lib.ggad_rank_wide_max_pos())
     if int(reps) != reps or not 1 <= int(reps) <= max_reps:
@@ -469,29 +466,45 @@ def ap_ci(scores: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, re
     pos_cap = int(pos_cap)
     too_many = ("{} positives are more than ggad_rank_bootstrap_max_pos() = {}: a replicate's histograms no longer fit one "
                 "workgroup's LDS, and there is no fallback")
-    scores, labels_u8 = scores.contiguous(), labels_u8.contiguous()
+    lists, labels_u8 = [s.contiguous() for s in lists], labels_u8.contiguous()
     dev = labels_u8.device
+    entry = "ggad_rank_bootstrap_pair" if len(lists) == 2 else "ggad_rank_bootstrap"
+    head, per = 8 + 8 * len(lists), reps * len(lists)
     with torch.cuda.device(dev):
-        ws = torch.empty(max(1, int(lib.ggad_rank_bootstrap_workspace_elems(n, pos_cap))), dtype=torch.int32, device=dev)
-        out = torch.empty(16 + 2 * reps, dtype=torch.float64, device=dev)          # out16, rep_ap, rep_auc_num (int64 words)
+        ws = torch.empty(max(1, int(getattr(lib, entry + "_workspace_elems")(n, pos_cap))), dtype=torch.int32, device=dev)
+        out = torch.empty(head + 2 * per, dtype=torch.float64, device=dev)         # the head, rep_ap, rep_auc_num (int64 words)
         base = _lib.ptr(out)
-        _lib.call("ggad_rank_bootstrap_f32", _lib.ptr(scores), _lib.ptr(labels_u8), n, pos_cap, float(thres), seed, reps, base,
-                  base + 16 * 8, base + (16 + reps) * 8, 0, _lib.ptr(ws))
+        _lib.call(entry + "_f32", *(_lib.ptr(s) for s in lists), _lib.ptr(labels_u8), n, pos_cap, float(thres), seed, reps, base,
+                  base + head * 8, base + (head + per) * 8, 0, _lib.ptr(ws))
         host = out.cpu().numpy()
-    o = host[:16].tolist()
-    status, n_pos = int(o[15]), int(o[6])
+    o = host[:head].tolist()
+    status, n_pos = int(o[head - 1]), int(o[6])
     if status == 2 and pos_cap >= boot_cap:
         raise ValueError(f"{who}: " + too_many.format(n_pos, boot_cap))
     _raise_on_status(who, status if status in (1, 2, 3, 4) else 0, n_pos, pos_cap)
-    tp, fp, fn, tn = (int(v) for v in o[2:6])
     if status == 9:
         raise ValueError(f"{who}: " + too_many.format(n_pos, boot_cap))
     if status == 8:
-        raise ValueError(f"{who}: {tp + fn} positives and {fp + tn} negatives: a stratified bootstrap {_TOO_FEW}")
+        raise ValueError(f"{who}: {int(o[2]) + int(o[4])} positives and {int(o[3]) + int(o[5])} negatives: a stratified bootstrap {_TOO_FEW}")
     if status != 0:
-        raise ValueError(f"{who}: ggad_rank_bootstrap_f32 left status {status}")
-    ap_reps = host[16:16 + reps].copy()
-    auc_reps = host[16 + reps:].view(np.int64).astype(np.float64) / float(2 * (tp + fn) * (fp + tn))
+        raise ValueError(f"{who}: {entry}_f32 left status {status}")
+    return o, host[head:], reps, seed
+
+
+def ap_ci(scores: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, reps: int = 1000, seed: int = 0, thres: float = 0.5,
+          pos_cap: Optional[int] = None) -> BootstrapInterval:
+    """Average precision (and AUROC) with the percentile interval of a stratified bootstrap at `level`: one `ggad_rank_bootstrap_f32`
+    call (csrc/rank_metrics.hip: the run-merge chain, then one workgroup per replicate that redraws the positives' ranks and the
+    negatives' bins with Philox4x32-10 under `seed` and never touches the elements again) and one read-back of `16 + 2 reps` words.
+    Stratified: every replicate holds the list's own counts of positives and negatives.  `thres` and `pos_cap` are
+    `rank_report_wide`'s (default `pos_cap`: the bootstrap's cap).  `ValueError` for a `level` outside (0, 1), `reps` outside
+    1..ggad_rank_bootstrap_max_reps(), a seed outside 64 bits, a NaN score, a label other than 0/1, one class only, fewer than two
+    positives or two negatives, more positives than `pos_cap` or than ggad_rank_bootstrap_max_pos() (an error: there is no second route)."""
+    import numpy as np
+    o, words, reps, seed = _bootstrap_call("ap_ci", [scores], labels_u8, level, reps, seed, thres, pos_cap)
+    tp, fp, fn, tn = (int(v) for v in o[2:6])
+    ap_reps = words[:reps].copy()
+    auc_reps = words[reps:].view(np.int64).astype(np.float64) / float(2 * (tp + fn) * (fp + tn))
     q = [(1.0 - float(level)) / 2, (1.0 + float(level)) / 2]
     ap_lo, ap_hi = (float(v) for v in np.quantile(ap_reps, q))
     auc_lo, auc_hi = (float(v) for v in np.quantile(auc_reps, q))
@@ -502,6 +515,77 @@ def ap_ci(scores: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, re
                              auc_se=float(auc_reps.std(ddof=1)) if reps > 1 else nan, level=float(level), reps=reps, seed=seed,
                              n_pos=tp + fn, n_neg=fp + tn, report={"auc": auc, "ap": ap, **_confusion_scores(tp, fp, fn, tn)},
                              ap_reps=ap_reps, auc_reps=auc_reps)
+
+
+@dataclass(eq=False)
+class ApComparison:
+    """Two models' average precision (and AUROC) on the same labels from a paired stratified bootstrap (`compare_ap`).  `ap_a`,
+    `ap_b`, `diff = ap_a - ap_b`: the point estimates; `diff_lo`, `diff_hi`: the `(1 - level) / 2` and `(1 + level) / 2` quantiles of
+    the replicate differences (numpy's linear method); `diff_se`: their standard deviation (`ddof=1`; NaN for one replicate); `p`: the
+    two-sided bootstrap p-value min(1, 2 min((1 + #{d* <= 0}) / (B + 1), (1 + #{d* >= 0}) / (B + 1))); the `auc_*` fields alike for
+    the AUROC.  `identical`: every replicate difference, AP and AUROC numerator, is exactly 0 (then `p = 1.0`).  `diff_reps` and
+    `auc_diff_reps` float64 hold the `reps` replicate differences in replicate order."""
+    ap_a: float
+    ap_b: float
+    diff: float
+    diff_lo: float
+    diff_hi: float
+    diff_se: float
+    p: float
+    auc_a: float
+    auc_b: float
+    auc_diff: float
+    auc_diff_lo: float
+    auc_diff_hi: float
+    auc_diff_se: float
+    level: float
+    reps: int
+    seed: int
+    n_pos: int
+    n_neg: int
+    identical: bool
+    diff_reps: "numpy.ndarray"
+    auc_diff_reps: "numpy.ndarray"
+
+    def __eq__(self, other):
+        if not isinstance(other, ApComparison):
+            return NotImplemented
+        mine, theirs = dict(self.__dict__), dict(other.__dict__)
+        return all(mine.pop(k).tobytes() == theirs.pop(k).tobytes() for k in ("diff_reps", "auc_diff_reps")) and repr(mine) == repr(theirs)
+
+
+def format_compare_ap(c: ApComparison) -> str:
+    """The one `[compare_ap]` line of `--score CKPT --compare CKPT_B --compare_ap`."""
+    return (f"[compare_ap] AP A {c.ap_a!r} B {c.ap_b!r} diff {c.diff!r} ± {c.diff_se!r} ({c.level:.0%}: [{c.diff_lo!r}, {c.diff_hi!r}]) "
+            f"p {c.p!r} AUROC diff {c.auc_diff!r} ({c.level:.0%}: [{c.auc_diff_lo!r}, {c.auc_diff_hi!r}]) from {c.reps} paired stratified "
+            f"replicates, seed {c.seed}, on {c.n_pos} positives, {c.n_neg} negatives")
+
+
+def compare_ap(scores_a: torch.Tensor, scores_b: torch.Tensor, labels_u8: torch.Tensor, level: float = 0.95, reps: int = 1000,
+               seed: int = 0, pos_cap: Optional[int] = None) -> ApComparison:
+    """Whether two models' average precisions on the same labels differ: a paired stratified bootstrap, one
+    `ggad_rank_bootstrap_pair_f32` call (csrc/rank_metrics.hip: the run-merge chain for either list, a table of where every element
+    falls under either model, then one workgroup per replicate that draws ELEMENTS with Philox4x32-10 under `seed` and counts each
+    at its own bin under A and under B) and one read-back of `24 + 4 reps` words.  Two unpaired `ap_ci` intervals are no substitute:
+    on the same labels the two APs are strongly correlated.  The `ValueError`s of `ap_ci`, for either list."""
+    import numpy as np
+    o, words, reps, seed = _bootstrap_call("compare_ap", [scores_a, scores_b], labels_u8, level, reps, seed, 0.5, pos_cap)
+    n_pos, n_neg = int(o[2]) + int(o[4]), int(o[3]) + int(o[5])
+    ap_reps, num_reps = words[:2 * reps], words[2 * reps:].view(np.int64)
+    d_ap = ap_reps[:reps] - ap_reps[reps:]
+    d_num = num_reps[:reps] - num_reps[reps:]                                      # exact int64
+    d_auc = d_num.astype(np.float64) / float(2 * n_pos * n_neg)
+    same = not d_ap.any() and not d_num.any()
+    q = [(1.0 - float(level)) / 2, (1.0 + float(level)) / 2]
+    lo, hi = (float(v) for v in np.quantile(d_ap, q))
+    alo, ahi = (float(v) for v in np.quantile(d_auc, q))
+    nan = float("nan")
+    p = min(1.0, 2.0 * min(1 + int((d_ap <= 0).sum()), 1 + int((d_ap >= 0).sum())) / (reps + 1))
+    return ApComparison(ap_a=float(o[1]), ap_b=float(o[9]), diff=float(o[1]) - float(o[9]), diff_lo=lo, diff_hi=hi,
+                        diff_se=float(d_ap.std(ddof=1)) if reps > 1 else nan, p=1.0 if same else p, auc_a=float(o[0]), auc_b=float(o[8]),
+                        auc_diff=float(o[0]) - float(o[8]), auc_diff_lo=alo, auc_diff_hi=ahi,
+                        auc_diff_se=float(d_auc.std(ddof=1)) if reps > 1 else nan, level=float(level), reps=reps, seed=seed,
+                        n_pos=n_pos, n_neg=n_neg, identical=same, diff_reps=d_ap, auc_diff_reps=d_auc)
 
 
 @dataclass

@@ -34,6 +34,9 @@ prints DeLong's paired test of the two AUROCs as one `[compare]` line (`metrics.
 ``ap_ci: LEVEL`` with ``boot_reps`` / ``boot_seed`` (`model: 'GCN'`; 0 = off): at the same two places, behind the `[auc_ci]` line, the
 test average precision and AUROC are printed with the percentile intervals of a stratified bootstrap as one `[ap_ci]` line
 (`metrics.ap_ci`, csrc/rank_metrics.hip: one workgroup per replicate), kept in `self.ap_interval`; the sweep's device scores are reused.
+``compare_ap: LEVEL`` (`model: 'GCN'`; 0 = off; ``boot_reps`` / ``boot_seed`` as for ``ap_ci``): `score(checkpoint, compare=other)`
+prints, behind the `[compare]` line, the paired stratified bootstrap of the two checkpoints' average precisions as one `[compare_ap]`
+line (`metrics.compare_ap`: interval, standard error and p-value of the difference), kept in `self.ap_comparison`.
 ``explain: M`` / ``explain_out`` (with ``top_k`` > 0): every node of the ranked list is explained on the device (`explain.explain`,
 csrc/explain.hip): its logit split exactly per feature and per neighbour, the M signed-greatest neighbour contributions listed; kept in
 `self.explained`, reported in one `[explain]` line and written to an `.npz`; after `train()` and by `score(checkpoint)` alike.
@@ -150,6 +153,13 @@ class ModelHandler(object):
                 raise ValueError("config key `ap_ci` needs `model: 'GCN'`: the interval is made from the scores of the GGAD test sweep")
             if not 0.0 < self.ap_level < 1.0:
                 raise ValueError(f"config key `ap_ci`: {args.ap_ci!r} is not a confidence level inside (0, 1) (0 = off)")
+        self.ap_comparison = None
+        self.compare_ap_level = float(getattr(args, "compare_ap", 0) or 0)      # config key `compare_ap`: the level, 0 = off
+        if self.compare_ap_level:
+            if getattr(args, "model", None) != "GCN":
+                raise ValueError("config key `compare_ap` needs `model: 'GCN'`: the test is made from the scores of the GGAD test sweep")
+            if not 0.0 < self.compare_ap_level < 1.0:
+                raise ValueError(f"config key `compare_ap`: {args.compare_ap!r} is not a confidence level inside (0, 1) (0 = off)")
         self.args, self.dataset = load_and_split(args, extra=("idx_anomaly",))
 
     @staticmethod
@@ -230,17 +240,24 @@ class ModelHandler(object):
     def _compare(self, scores, other, gnn_model, engine, ids, labels, sweep):
         """`score(compare=other)`: the same list scored under the weights of `other` -- by the same sweep, whose cached rows do not
         depend on the weights -- and DeLong's paired test of the two AUROCs, one `[compare]` line; kept in `self.auc_comparison`."""
-        from .metrics import compare_auc, format_compare
+        from .metrics import compare_ap, compare_auc, format_compare, format_compare_ap
         gnn_model.load_state_dict(torch.load(other))
         engine.sync_params()
+        boot = (self.compare_ap_level, self.boot_reps, self.boot_seed)
         if sweep is not None:
-            c = sweep.compare(sweep.scores(), scores=scores)
+            scores_b = sweep.scores()
+            c = sweep.compare(scores_b, scores=scores)
+            ca = sweep.compare_ap(scores_b, scores, *boot) if self.compare_ap_level else None
         else:
             lab = np.asarray(labels).reshape(-1).astype(np.uint8)
             scores_b = score_nodes(gnn_model, ids, self.args.batch_size, device=True)
-            c = compare_auc(scores, scores_b, torch.from_numpy(lab).to(scores.device), pos_cap=max(1, int(np.count_nonzero(lab == 1))))
-        self.auc_comparison = c
+            y, cap = torch.from_numpy(lab).to(scores.device), max(1, int(np.count_nonzero(lab == 1)))
+            c = compare_auc(scores, scores_b, y, pos_cap=cap)
+            ca = compare_ap(scores, scores_b, y, *boot, pos_cap=cap) if self.compare_ap_level else None
+        self.auc_comparison, self.ap_comparison = c, ca
         print(format_compare(c))
+        if ca is not None:                           # config key `compare_ap`: the paired bootstrap of the two APs, behind `[compare]`
+            print(format_compare_ap(ca))
         return c
 
     def _build_gcn(self):
@@ -317,7 +334,8 @@ class ModelHandler(object):
         its labels, which follows from the config alone (`split_dgraphfin` reseeds itself from `seed`).  With labels `test_sage`'s report
         is printed and its 5-tuple kept in `self.metrics`; with `k` (default: config key `top_k`) > 0 the scores are ranked (`_rank`).
         Honours `eval_cache`.  With labels, config key `auc_ci` prints the `[auc_ci]` line and `compare` (a second checkpoint) the
-        `[compare]` line; the model then holds the second checkpoint's weights.  Returns (device float32 scores, `Ranked` or None)."""
+        `[compare]` line (and, with config key `compare_ap`, the `[compare_ap]` line behind it); the model then holds the second checkpoint's
+        weights.  Returns (device float32 scores, `Ranked` or None)."""
         args = self.args
         if args.model != "GCN":
             raise NotImplementedError("ModelHandler.score serves model 'GCN' (GGAD)")

@@ -1340,6 +1340,36 @@ int ggad_rank_bootstrap_f32(const float *score, const uint8_t *label, int64_t n,
                             ggad_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Paired stratified bootstrap of two models' average precision and AUROC on the same labels (rank_metrics.hip).  The run-merge chain
+ * runs twice, into two halves of the workspace (out24[0..7] A's out8, [8..15] B's: ggad_rank_wide_f32's bits for the same
+ * arguments); one launch then stores, per element, where it falls under either model, and one more makes `reps` replicates, one
+ * workgroup each.  The scheme.  Positive number j is the j-th element with label 1 in POSITION order, negative number u the u-th
+ * with label 0: position order, not key order, makes an element the same thing under both models.  Replicate r draws P positive
+ * numbers on Philox stream 0 (m = P) and Nn negative numbers on stream 1 (m = Nn); generator, key, counter layout and draw rule are
+ * ggad_rank_bootstrap_f32's (above: call j gives draws 2j and 2j + 1, a draw over m outcomes is (x * m) >> 64).  For each model M,
+ * with pos_M its sorted positive keys,
+ *   w_M[rank_M(j)] += 1     rank_M(j) = #{pos_M <  key_M(j)}: a run of equal positives is counted at its FIRST rank (the same real
+ *                           AP*, since the bins strictly inside a run are empty; no tie order among equal keys is needed);
+ *   cU_M[ub_M(u)] += 1      ub_M(u) = #{pos_M <= key_M(u)}, and cE_M[ub_M(u) - 1] += 1 when the negative ties the positive there;
+ * and rep_ap / rep_auc_num follow from (w, cU, cE) by ggad_rank_bootstrap_f32's two formulas in its summation order.  rep_ap and
+ * rep_auc_num hold 2 reps words: A's replicates, then B's; replicate r of A and of B are the SAME drawn elements, so
+ * rep_ap[r] - rep_ap[reps + r] is a replicate of the difference.  With the same seed a model's replicates here are NOT those of
+ * ggad_rank_bootstrap_f32: that call draws sorted ranks and histogram bins, this one elements -- the same distribution, other bits.
+ * out24: [16] reps, [17] P, [18] Nn, [19..22] 0.0, [23] status: the first non-zero of [7] and [15]; 8 = fewer than two positives or
+ * two negatives; 9 = more positives than ggad_rank_bootstrap_max_pos() = 9216; else 0.  With a status other than 0 every rep_ap is
+ * NaN, every rep_auc_num 0.  hist_out: NULL, or reps rows of 6 (pos_cap + 1) int32 that receive w, cU, cE of A, then of B, zero
+ * beyond entry P (for tests).
+ * Limits, alignment, refusals and workspace rule of ggad_rank_bootstrap_f32 (ggad_rank_bootstrap_pair_workspace_elems(n, pos_cap)
+ * int32 elements, 0 = refused: two chains and 2 bytes per element and model).  No host synchronisation, LDS integer atomics only,
+ * nothing waits on another workgroup, every word a launch reads was written by an earlier launch of the same call: capturable and
+ * replayable; equal arguments give equal bits on any grid.
+ * ---------------------------------------------------------------------------------- */
+int64_t ggad_rank_bootstrap_pair_workspace_elems(int64_t n, int64_t pos_cap);   /* int32 elements; 0 = refused */
+int ggad_rank_bootstrap_pair_f32(const float *score_a, const float *score_b, const uint8_t *label, int64_t n, int64_t pos_cap,
+                                 float thres, uint64_t seed, int32_t reps, double *out24, double *rep_ap, int64_t *rep_auc_num,
+                                 int32_t *hist_out, int32_t *workspace, ggad_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * Keep the best epoch's weights on the device (select.hip): the hand-off "if this epoch's validation metric is the best so far,
  * snapshot the parameters" without a host round trip.  Neither call takes a workspace; each reads only words the host or an earlier
  * launch wrote, so both are capturable and replayable behind ggad_rank_metrics_f32 / ggad_rank_wide_f32 in a captured epoch.

@@ -17,7 +17,8 @@ the CPU generator are untouched.  `--save PATH` writes the weights (the best epo
 `--auc_ci [LEVEL]` (after training or with `--score`) prints the test AUROC with DeLong's standard error and interval; `--score A.pt
 --compare B.pt` tests the AUROCs of two checkpoints against each other on idx_test (`metrics.auc_ci` / `compare_auc`).
 `--ap_ci [LEVEL] [--boot_reps B] [--boot_seed S]` (at the same places) prints the test average precision and AUROC with the percentile
-intervals of a stratified bootstrap made on the device (`metrics.ap_ci`).
+intervals of a stratified bootstrap made on the device (`metrics.ap_ci`).  `--score A.pt --compare B.pt --compare_ap [LEVEL]` also tests
+the two average precisions against each other by a paired bootstrap (`metrics.compare_ap`; `--boot_reps`, `--boot_seed`).
 """
 import os
 import sys
@@ -30,10 +31,11 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from ggad_amd.fullgraph import FlatAdam, ggad_loss  # noqa: E402
 from ggad_amd.fullgraph_script import (SIZES, CapturedEpoch, add_bootstrap_options, add_compare_options, add_select_options,  # noqa: E402,F401
                                        add_threshold_options, bootstrap_options, check_bootstrap_options, check_compare_options,
-                                       check_select_options, check_threshold_options, choose_threshold, compare_options, init_process,
-                                       load_checkpoint, load_graph, make_parser, parse_with_defaults, prepare, print_ap_ci,
-                                       print_auc_ci, print_captured, print_compare, print_eval, print_median,
-                                       print_threshold_test, save_checkpoint, score_from_checkpoint, select_options, threshold_option)
+                                       check_select_options, check_threshold_options, choose_threshold, compare_ap_option,
+                                       compare_options, init_process, load_checkpoint, load_graph, make_parser, parse_with_defaults,
+                                       prepare, print_ap_ci, print_auc_ci, print_captured, print_compare, print_compare_ap, print_eval,
+                                       print_median, print_threshold_test, save_checkpoint, score_from_checkpoint, select_options,
+                                       threshold_option)
 from ggad_amd.metrics import average_precision, roc_auc  # noqa: E402
 from ggad_amd.model import Model  # noqa: E402
 
@@ -83,7 +85,10 @@ def main(argv=None):
             if other:                                    # the same model and graph under the second checkpoint's weights
                 model.load_state_dict(load_checkpoint(other, ft_size, args.embedding_dim)["state_dict"], strict=True)
                 model.eval()
-                print_compare(scores, model.score(feats, full), g.idx_test, g.ano_label, dev)
+                scores_b = model.score(feats, full)
+                print_compare(scores, scores_b, g.idx_test, g.ano_label, dev)
+                if compare_ap_option(args):
+                    print_compare_ap((compare_ap_option(args),) + bootstrap_options(args)[1:], scores, scores_b, g.idx_test, g.ano_label, dev)
         except ValueError as exc:
             sys.exit("run.py --score: {}".format(exc))
         return scores.cpu().numpy()

@@ -156,15 +156,23 @@ if __name__ == "__main__":
                     help="override the config's ap_ci (--handler ggad: after the closing test sweep, and with --score, print the test "
                          "average precision and AUROC with the percentile intervals of a stratified bootstrap at LEVEL, default 0.95; "
                          "0 = off)")
-    ap.add_argument("--boot_reps", type=int, default=None, metavar="B", help="override the config's boot_reps (replicates of --ap_ci)")
-    ap.add_argument("--boot_seed", type=int, default=None, metavar="S", help="override the config's boot_seed (Philox seed of --ap_ci)")
+    ap.add_argument("--boot_reps", type=int, default=None, metavar="B", help="override the config's boot_reps (replicates of --ap_ci and --compare_ap)")
+    ap.add_argument("--boot_seed", type=int, default=None, metavar="S", help="override the config's boot_seed (Philox seed of --ap_ci and --compare_ap)")
     ap.add_argument("--compare", type=str, default=None, metavar="CKPT_B",
                     help="with --score CKPT: score the test split under CKPT_B too and print DeLong's paired test of the two AUROCs")
+    ap.add_argument("--compare_ap", type=float, nargs="?", const=0.95, default=None, metavar="LEVEL",
+                    help="override the config's compare_ap (with --score CKPT --compare CKPT_B: behind the [compare] line, print the paired "
+                         "stratified bootstrap of the two average precisions, the interval of the difference at LEVEL, default 0.95; "
+                         "0 = off)")
     a = ap.parse_args()
     if a.compare is not None and a.score is None:
         ap.error("--compare CKPT_B compares with the checkpoint of --score CKPT: it needs --score")
     if a.compare is not None and a.score_ids is not None:
         ap.error("--compare tests two AUROCs against each other: the ids of --score_ids carry no labels")
+    if a.compare_ap is not None and a.compare is None:
+        ap.error("--compare_ap tests the average precisions of --score CKPT and --compare CKPT_B: it needs --compare")
+    if a.compare_ap is not None and not 0.0 <= a.compare_ap < 1.0:
+        ap.error("--compare_ap LEVEL: a confidence level inside (0, 1), as in --compare_ap 0.9 (0 = off)")
     if a.auc_ci and a.handler != "ggad":
         ap.error("--auc_ci serves --handler ggad only")
     if a.auc_ci is not None and not 0.0 <= a.auc_ci < 1.0:
@@ -203,7 +211,7 @@ if __name__ == "__main__":
         cfg["thres_select"] = a.thres_select
     if a.auc_ci is not None:
         cfg["auc_ci"] = a.auc_ci
-    for key in ("ap_ci", "boot_reps", "boot_seed"):
+    for key in ("ap_ci", "boot_reps", "boot_seed", "compare_ap"):
         if getattr(a, key) is not None:
             cfg[key] = getattr(a, key)
     SCORE, SCORE_IDS, COMPARE = a.score, a.score_ids, a.compare
